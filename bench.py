@@ -2,14 +2,23 @@
 """bench.py — headline metric of BASELINE.json: point-cloud blocks/s, forward + backward (+ Adam step),
 SPH3D_s3dis-shaped network on 8192-point S3DIS-like blocks, 16 blocks per GPU (weak scaling).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank
    per GPU, or run plainly — without WORLD_SIZE in the environment the script re-launches itself that way)
 
 A "step" = graph construction (nnquery, FPS, buildkernel: they depend on the input xyz, so they are part
 of every step) + forward + loss + backward + gradient all-reduce (N > 1) + optimiser update, on one batch
 of synthetic blocks already resident in HBM (two different batches alternate, so nothing a step computes can be
-left over from the step before).  Rank 0 prints ONE JSON line (contract in the task brief), with two extra objects:
+left over from the step before).  Rank 0 prints ONE JSON line (contract in the task brief).
+
+A plain run does only what that line's figure needs: set-up, priming and warm-up steps, the K timed steps, and, with
+--dump-outputs DIR, rank 0's results of the last timed step as DIR/<name>.npy (float32: the logits, the loss, the
+all-reduced flat gradient and the parameters after the optimiser update; the inputs are seeded, so two runs with the
+same arguments give the same outputs: the last timed step then starts from the seeded initial model and optimiser
+state, see main(); logits and loss repeat bit for bit, gradient and parameters to rounding).  --full adds what takes
+runs of its own: the GEMM accuracy check (config.gemm_check), an event pass over the same steps (kernels,
+families_ms_per_step, allreduce wait), the host-issue and sampling-chain probes (dist), conv_gather (the level-0
+depthwise forward against the HBM peak), and two extra objects:
   roofline     — the dominant libsph3d op family of the step (GEMM NN / NT / TN count as one family): algorithmic
                  bytes or flops of its largest call (SURVEY §8d formulas) / that call's mean device time, measured
                  with HIP events on the launching stream (avg_us: inside the running step, other streams busy;
@@ -46,6 +55,7 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measu
 FP32_MFMA_PEAK_TFLOPS = 157.3
 BF16_MFMA_PEAK_TFLOPS = 2500.0      # dense (MI355X_MICROARCH.md); the split products execute 6 bf16 piece products per fp32 product
 SPLIT_PRODUCTS = 6
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all arrays together
 
 
 def algorithmic_bytes(name, a):
@@ -109,20 +119,38 @@ def make_batch(rank, dev, which=0):
 _PTS_READY = {}
 
 
-def fwd_bwd(model, flat, pts, label, inner):
+def fwd_bwd(model, flat, pts, label, inner, keep=None):
     # graphs are built inside (GraphPlan) on two side streams that wait only for the INPUT batch (resident in HBM
     # since before the timed region), so a step's sampling / graph construction overlaps the previous step's backward
     pred, _ = model(pts, is_training=True, points_ready=_PTS_READY.get(pts.data_ptr()))
     loss = model.loss(pred, label, inner)
     flat.backward(loss)          # all parameter gradients -> the flat fp32 buffer (one concatenation, no per-parameter adds)
+    if keep is not None:         # (--dump-outputs: the step's logits, kept until the next step replaces them)
+        keep["logits"] = pred.detach()
     return loss
 
 
-def train_step(model, flat, opt, pts, label, inner):
-    loss = fwd_bwd(model, flat, pts, label, inner)
+def train_step(model, flat, opt, pts, label, inner, keep=None):
+    loss = fwd_bwd(model, flat, pts, label, inner, keep)
     flat.all_reduce()
     opt.step()
     return loss
+
+
+def write_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <outdir>/<name>.npy, float64 kept, everything else as float32; at most `limit` bytes in
+    all (checked before anything is written) -> bytes written"""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.array(a, dtype=np.float64 if a.dtype == np.float64 else np.float32, order="C")     # (shape kept, 0-d too)
+    total = sum(a.nbytes for a in out.values())
+    if total > limit:
+        raise ValueError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, limit))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return total
 
 
 def run_timed(one_step, steps, warmup, world, sync):
@@ -617,8 +645,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probes", action="store_true", help="skip the one-block host-issue and sampling-chain probes of `dist`")
+    ap.add_argument("--full", action="store_true",
+                    help="headline line: also the GEMM accuracy check, the per-kernel event pass, the probes, the roofline and "
+                         "conv_gather objects (with isolated calls) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline line: write rank 0's results of the last timed step to DIR/<name>.npy (float32, < 64 MiB); "
+                         "that step then starts from the seeded initial model and optimiser state, so that every run repeats it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline object")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: skip the one-block host-issue and sampling-chain probes of `dist`")
     ap.add_argument("--atan2", choices=("ocml", "shared"), default="ocml",
                     help="angle function of the spherical-kernel binning: 'ocml' = ROCm's device-library atan2f, the function the "
                          "reference's own kernel calls when built for this GPU (bins bit-identical to the reference build); "
@@ -634,6 +668,10 @@ def main():
                     help="SECONDARY line: forward only (is_training=False under no_grad: every separable layer is ONE kernel, "
                          "csrc/sepconv.hip) on the headline's batch; metric 'point-cloud blocks/sec (inference)'")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.config != "s3dis" or args.eval):
+        ap.error("--dump-outputs writes the headline line's outputs (not with --config or --eval)")
 
     if args.config == "scannet" or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # The runtime multiplexes a process's streams onto 4 hardware queues by default, and two streams on one queue run one
@@ -661,7 +699,7 @@ def main():
     if args.eval:
         return eval_main(args, rank, world, dev, pinned_cpus)
 
-    gemm_check = gemm_accuracy_check(dev) if is_rank0 else None
+    gemm_check = gemm_accuracy_check(dev) if is_rank0 and args.full else None
     batches = [make_batch(rank, dev, w) for w in range(NUM_BATCHES)]
     torch.cuda.synchronize()
     ev = torch.cuda.Event()
@@ -687,10 +725,24 @@ def main():
     #  eager — the GPU, not the host, is the bound — and the three-branch graph replays serialised, 12.1 against 10.7 ms)
     mode = "eager"
 
+    # --dump-outputs: the last timed step starts from the seeded initial parameters and a fresh optimiser state, so that its
+    # inputs are the same in every run.  (Not from the state the earlier steps left: a transposed graph lists a segment's
+    # edges in arrival order, so gradient sums differ in the last bits from run to run, and a hundred Adam steps make that
+    # a visible difference.  The forward pass is order-fixed.)  The reset is one copy of the parameter buffer and the
+    # zeroing of the optimiser's moments, inside the timed region, once per run.
+    keep, initial_state, last_step = None, None, PRIME_STEPS + args.warmup + args.steps - 1
+    if args.dump_outputs:
+        keep = {}
+        initial_state = (flat.flat_param.detach().clone(), opt.state_dict())
+
     def one_step():
+        if initial_state is not None and step_no[0] == last_step:
+            with torch.no_grad():
+                flat.flat_param.copy_(initial_state[0])
+            opt.load_state_dict(initial_state[1])
         p_, l_, i_ = batches[step_no[0] % NUM_BATCHES]        # a different resident batch every step
         step_no[0] += 1
-        return train_step(model, flat, opt, p_, l_, i_)
+        return train_step(model, flat, opt, p_, l_, i_, keep)
 
     # Priming (setup, not measurement): the first ~14 steps of a fresh process contain one-off host stalls — the caching
     # allocator still growing its pools (hipMalloc is synchronous) and one 80-90 ms pause at the 14th step (first
@@ -701,31 +753,39 @@ def main():
         one_step()
     torch.cuda.synchronize()
     elapsed, loss = run_timed(one_step, args.steps, args.warmup, world, torch.cuda.synchronize)
+    if args.dump_outputs and is_rank0:
+        write_outputs(args.dump_outputs, {"logits": keep["logits"].cpu().numpy(), "loss": loss.detach().cpu().numpy(),
+                                          "grad": flat.unpadded(flat.flat).cpu().numpy(),
+                                          "params": flat.unpadded(flat.flat_param.detach()).cpu().numpy()})
 
-    # Per-kernel device times: the same K steps are run once more, right after the timed region (same process, same
+    # --full: per-kernel device times: the same K steps are run once more, right after the timed region (same process, same
     # data, same kernels), with every C-ABI launch bracketed by two HIP events on its launching stream.  They are
     # not recorded inside the timed region because the eager step is host-bound and ~460 extra event records per
     # step would lengthen the very interval being measured.
-    ev_steps = min(args.steps, 20)
-    _lib.timing_start()
-    flat.time_wait_events = True            # + an event pair around the wait for the gradient all-reduce (main stream)
-    for _ in range(ev_steps):
-        one_step()
-    torch.cuda.synchronize()
-    events = _lib.timing_stop()
-    flat.time_wait_events = False
-    ar_wait_ms = [a.elapsed_time(b) for a, b in flat.wait_events]
+    ev_steps, events, ar_wait_ms = 0, [], []
+    if args.full:
+        ev_steps = min(args.steps, 20)
+        _lib.timing_start()
+        flat.time_wait_events = True            # + an event pair around the wait for the gradient all-reduce (main stream)
+        for _ in range(ev_steps):
+            one_step()
+        torch.cuda.synchronize()
+        events = _lib.timing_stop()
+        flat.time_wait_events = False
+        ar_wait_ms = [a.elapsed_time(b) for a, b in flat.wait_events]
 
-    # what this rank's Python needs to ISSUE a step, whatever the device does: the same step on ONE block (the same ~450 launches,
+    # --full: what this rank's Python needs to ISSUE a step, whatever the device does: the same step on ONE block (the same ~450 launches,
     # a sixteenth of the device work) and the per-rank time of the sampling chain alone —
     # a multi-GPU run whose ranks sit well above the 1-GPU ms/step is launch-bound where host_issue approaches that figure, and
     # device-bound where it does not
-    if args.no_probes:            # (the rocprofv3 run of tools/gpu_profile_round.sh: its kernel statistics must hold whole 16-block steps only)
-        host_issue_ms, fps_chain_ms = 0.0, 0.0
-    else:
-        host_issue_ms, fps_chain_ms = probe_host_issue(model, flat, opt, batches[0], dev), probe_fps_chain(batches[0][0], model.config)
-    per_rank_issue = hdist.gather_floats(host_issue_ms, world, dev)
-    per_rank_fps = hdist.gather_floats(fps_chain_ms, world, dev)
+    per_rank_issue, per_rank_fps = None, None
+    if args.full:
+        if args.no_probes:        # (a --full run under a profiler: its kernel statistics must hold whole 16-block steps only)
+            host_issue_ms, fps_chain_ms = 0.0, 0.0
+        else:
+            host_issue_ms, fps_chain_ms = probe_host_issue(model, flat, opt, batches[0], dev), probe_fps_chain(batches[0][0], model.config)
+        per_rank_issue = [round(x, 3) for x in hdist.gather_floats(host_issue_ms, world, dev)]
+        per_rank_fps = [round(x, 3) for x in hdist.gather_floats(fps_chain_ms, world, dev)]
 
     # every rank's own time for the K timed steps (diagnosis of a slow rank), then the contract's MAX over ranks
     per_rank_s = hdist.gather_floats(elapsed, world, dev)
@@ -832,7 +892,7 @@ def main():
             if iso:
                 conv_gather["isolated_us"] = round(iso * 1e6, 1)
                 conv_gather["isolated_frac"] = round(ab / 1e9 / iso / HBM_PEAK_GBS, 4)
-    sph3d_ms = sum(v[0] for v in per.values()) / ev_steps
+    sph3d_ms = round(sum(v[0] for v in per.values()) / ev_steps, 3) if args.full else None
 
     if is_rank0:
         blocks = world * BLOCKS_PER_GPU * args.steps
@@ -854,7 +914,7 @@ def main():
                        "global_batch": world * BLOCKS_PER_GPU, "points_per_block": NUM_POINT,
                        "parallelism": "dp%d (one cloud shard per GPU; flat gradient all-reduced over RCCL in %d buckets, "
                                       "overlapped with backward)" % (world, len(flat.buckets)),
-                       "resident_batches": NUM_BATCHES, "event_pass_steps": ev_steps,
+                       "resident_batches": NUM_BATCHES, "event_pass_steps": ev_steps if args.full else None,
                        "params": nparams, "launch_mode": mode, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "default (4)"),
                        "atan2": args.atan2,
                        "gemm": ("split: fp32 operands as three exact bf16 pieces, six bf16-MFMA piece products accumulated in fp32 "
@@ -874,24 +934,25 @@ def main():
             "dist": {"per_rank_ms_per_step": [round(x / args.steps * 1e3, 3) for x in per_rank_s],
                      "rank_ms_per_step_min_max": [round(min(per_rank_s) / args.steps * 1e3, 3),
                                                   round(max(per_rank_s) / args.steps * 1e3, 3)],
-                     "host_issue_ms_per_step_one_block": [round(x, 3) for x in per_rank_issue],
-                     "fps_chain_ms_per_step": [round(x, 3) for x in per_rank_fps],
+                     "host_issue_ms_per_step_one_block": per_rank_issue,
+                     "fps_chain_ms_per_step": per_rank_fps,
                      "cpus_per_rank": pinned_cpus,
                      "bucket_bytes": [4 * (f1 - f0) for (_i0, _i1, f0, f1) in flat.buckets],
                      "buckets_started_in_backward": flat.stats["buckets_started_in_backward"],
                      "buckets_started_after_backward": flat.stats["buckets_started_after_backward"],
-                     "allreduce_wait_stream_ms_per_step": (round(sum(ar_wait_ms) / max(1, len(ar_wait_ms)), 4) if ar_wait_ms else 0.0),
+                     "allreduce_wait_stream_ms_per_step": ((round(sum(ar_wait_ms) / max(1, len(ar_wait_ms)), 4) if ar_wait_ms else 0.0)
+                                                           if args.full else None),
                      "allreduce_wait_host_ms_per_step": round(flat.stats["allreduce_wait_host_s"] / max(1, flat.stats["allreduce_calls"]) * 1e3, 4),
                      "note": "rank 0's counters; allreduce_wait_stream = HIP events around the wait in FlatGradAllReduce.all_reduce() "
                              "on the main stream during the %d event-pass steps (0 at one GPU: no collective is issued)" % ev_steps},
             "loss": round(float(loss.detach()), 5),
-            "sph3d_calls_ms_per_step_summed_over_streams": round(sph3d_ms, 3),
-            "families_ms_per_step": families,
+            "sph3d_calls_ms_per_step_summed_over_streams": sph3d_ms,
+            "families_ms_per_step": families if args.full else None,
             "roofline": roofline,
             "conv_gather": conv_gather,
-            "kernels": kernels,
+            "kernels": kernels if args.full else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         else:
             out["cpu_baseline"] = None

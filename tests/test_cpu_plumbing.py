@@ -283,6 +283,25 @@ def test_bench_algorithmic_bytes_follow_the_survey_formulas():
     assert bwd == 336136192
 
 
+def test_bench_output_dump_writes_float32_npy_within_its_size_limit(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per array, float64 kept, everything else as float32; over the limit nothing
+    is written"""
+    import bench
+    out = str(tmp_path / "dump")
+    n = bench.write_outputs(out, {"logits": np.arange(12, dtype=np.float16).reshape(3, 4), "loss": np.float32(2.5),
+                                  "grad": np.linspace(0, 1, 5)})
+    got = {f: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["grad.npy", "logits.npy", "loss.npy"] and n == 12 * 4 + 4 + 5 * 8
+    assert got["logits.npy"].dtype == np.float32 and got["logits.npy"].shape == (3, 4)
+    assert np.array_equal(got["logits.npy"], np.arange(12).reshape(3, 4))
+    assert got["loss.npy"].dtype == np.float32 and got["loss.npy"].shape == () and got["loss.npy"].item() == 2.5
+    assert got["grad.npy"].dtype == np.float64 and np.array_equal(got["grad.npy"], np.linspace(0, 1, 5))
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "big"), {"a": np.zeros(10, np.float32)}, limit=39)
+    assert not os.path.exists(str(tmp_path / "big"))
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+
+
 def test_flat_adam_learning_rate_survives_a_resume_on_the_cpu_branch():
     """torch.optim.Optimizer.load_state_dict replaces param_groups; FlatAdam.lr / param_groups must keep writing
     to the list the wrapped optimiser actually reads"""

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -51,7 +52,7 @@ def test_bench_under_torchrun_runs_the_rccl_path_on_one_gpu():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -61,6 +62,34 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     r = out["roofline"]
     assert r["bound"] in ("hbm", "mfma") and 0 < r["frac"] < 1 and r["isolated_us"] and "family" in r
     assert out["steps"] == 3 and out["n_gpus"] == 1 and out["config"]["resident_batches"] == 2
+
+
+def _bench_dump(dump):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs", dump],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run (no --full) prints the headline line without the extra measurements, and --dump-outputs writes the last
+    timed step's logits, loss, gradient and parameters as float32 .npy files, 64 MiB at most; a second run with the same
+    arguments writes the same outputs (the forward pass bit for bit, the gradient sums to rounding: their order is not fixed)"""
+    out, got = _bench_dump(str(tmp_path / "out"))
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["unit"] == "blocks/s"
+    assert abs(out["value"] - 16 * 1e3 / out["ms_per_step"]) <= 1e-3 * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["kernels"] is None
+    assert sorted(got) == ["grad", "logits", "loss", "params"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["logits"].shape == (16, 8192, 13) and got["grad"].shape == got["params"].shape == (out["config"]["params"],)
+    assert abs(got["loss"].item() - out["loss"]) <= 1e-4 * abs(out["loss"])
+    again = _bench_dump(str(tmp_path / "again"))[1]
+    assert np.array_equal(again["logits"], got["logits"]) and np.array_equal(again["loss"], got["loss"])
+    for k in ("grad", "params"):
+        np.testing.assert_allclose(again[k], got[k], rtol=1e-5, atol=1e-6, err_msg=k)
 
 
 def test_bucket_collective_is_ordered_after_the_concatenation_on_a_side_stream(dev):

@@ -272,11 +272,11 @@ def test_fixed_radius_mode_runs_the_model_graph_through_the_plain_kernels():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    """the driver depends on `python bench.py` printing ONE JSON line on rank 0: run it (3 steps) as a subprocess and check the
-    contract fields, the roofline object and the conv_gather line"""
+    """the driver depends on `python bench.py` printing ONE JSON line on rank 0: run it (3 steps, --full) as a subprocess and check
+    the contract fields, the roofline object and the conv_gather line"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

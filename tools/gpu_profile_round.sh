@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py > $OUT/${TAG}_bench_default.log 2> $OUT/${TAG}_bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_default.log 2> $OUT/${TAG}_bench_default.err; echo "bench rc=$?"
 # secondary lines (BASELINE configs 2, 3, 5 and the inference forward): same contract, not the headline
 for c in modelnet shapenet scannet; do timeout 400 python bench.py --config $c --steps 20 --warmup 3 > $OUT/${TAG}_bench_$c.log 2> $OUT/${TAG}_bench_$c.err; done
 timeout 400 python bench.py --eval --steps 20 --warmup 3 > $OUT/${TAG}_bench_eval.log 2> $OUT/${TAG}_bench_eval.err
