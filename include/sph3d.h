@@ -48,6 +48,13 @@ int sph3d_abi_version(void);                 /* == SPH3D_ABI_VERSION of the head
 const char* sph3d_last_error(void);          /* thread-local text of the last non-OK status */
 const char* sph3d_build_info(void);          /* "gfx950 hipcc <ver> ..." */
 
+/* Test hooks, not modes: the library reads no other environment variable.  Tests set them to reach paths that small inputs
+ * do not take.
+ *   SPH3D_BWD_HUB_MIN_N=<points>  smallest cloud whose conv gradient takes the hub launches (default 32768; read on every call)
+ *   SPH3D_BWD_HUB_T=<edges>       in-edge threshold of a hub source (default 1024, values below 1 count as 1; read on every call)
+ *   SPH3D_FPS_FORCE_TIMEOUT=1     the co-operative farthest point sampling pass starts as if timed out, so its repair pass
+ *                                 recomputes the samples (any non-zero value; read once per process) */
+
 /* ---- nnquery ------------------------------------------------------------
  * replaces buildSphereNeighborLauncher (tf_ops/nnquery/tf_nnquery_gpu.cu:115-121;
  * kernel cal_nn_binidx :15-65; op BuildSphereNeighbor tf_nnquery.cpp:55-111).
@@ -72,7 +79,7 @@ const char* sph3d_build_info(void);          /* "gfx950 hipcc <ver> ..." */
  * hold no state between calls — what SURVEY 8b asks of every kernel entry; the Python ops of this package call only those.
  * workspace == NULL there: no grid.  sph3d_release_stream_scratch(stream) frees the convenience buffer of `stream` on the
  * current device (call it before destroying the stream), sph3d_release_all_scratch() every buffer of the current device;
- * both return the number of buffers freed.  Environment SPH3D_NNGRID=0 (read once) turns the grid off. */
+ * both return the number of buffers freed. */
 #define SPH3D_MAX_GROWTH_PASSES 4096
 /* diagnostic: calls so far in this process whose early positions went through the cell grid */
 long long sph3d_nngrid_launches(void);

@@ -7,14 +7,13 @@ to the tensors it was built from, so their storage (and therefore the data_ptr i
 recycled for a different graph while the entry is alive; in-place edits are caught by the version counter.
 """
 import collections
-import os
 
 import torch
 
 from . import _lib
 
 BALANCE_MIN_POINTS = 1024   # binned graphs with at least this many source points get a degree-balanced gradient order
-PACK_ENTRIES = os.environ.get("SPH3D_TG_PACK", "1") != "0"     # (False / SPH3D_TG_PACK=0: always separate key / scale arrays)
+PACK_ENTRIES = True     # (False: always separate key / scale arrays)
 _MAX_ENTRIES = 24      # one S3DIS step builds 16 (8 binned intra graphs, 4 un-pooling and 4 pooling graphs); entries pin ~150 MB each at level 0
 _cache = collections.OrderedDict()
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/sph3d.h"
 
 namespace sph3d {
@@ -48,6 +49,14 @@ static inline int check_hip(hipError_t e, const char* what)
 }
 
 static inline hipStream_t as_stream(sph3d_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The library reads no environment except the test hooks listed in sph3d.h; they reach code that ordinary inputs rarely do.
+// -> the variable's value as atoi() reads it, `unset` if it is not set.  Each caller decides when it reads (per call or once).
+static inline int test_hook(const char* name, int unset)
+{
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+}
 
 // graph.hip: stream-ordered zero fill of `bytes` bytes at `p` (4-byte aligned, bytes % 4 == 0).  hipMemsetAsync's fill kernel
 // runs 256 workgroups whatever the size: 245 us for the 17 MB of level-0 segment counters (70 GB/s; rocprofv3 trace of round 5);

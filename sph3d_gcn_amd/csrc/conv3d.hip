@@ -23,21 +23,14 @@
 //     (N*C*4 B, 4 MiB at N=8192,C=128) stay in that XCD's 4 MiB L2.
 //   * Numerics: sum_k in*filt in fp32 FMA order k = 0..cnt-1, one division by cnt at the end (the
 //     reference divides every term); agreement with the oracle is ~1e-7 relative, bound 1e-5.
-#include <cstdlib>
 #include "common.hpp"
 
 namespace sph3d {
 
 constexpr int kSlice = 256;       // output channels per wave pass (64 lanes x 4)
 constexpr int kFwdPointsPerWG = 32;
-#ifndef SPH3D_FWD_SB
-#define SPH3D_FWD_SB 4
-#endif
-constexpr int kFwdSB = SPH3D_FWD_SB;   // dwconv_fwd_multi: wave loads (each EPL neighbour rows) issued together
-#ifndef SPH3D_FWD_WAVES
-#define SPH3D_FWD_WAVES 4
-#endif
-constexpr int kMultiWaves = SPH3D_FWD_WAVES;          // dwconv_fwd_multi: waves per workgroup (they share one LDS filter table)
+constexpr int kFwdSB = 4;              // dwconv_fwd_multi: wave loads (each EPL neighbour rows) issued together
+constexpr int kMultiWaves = 4;                        // dwconv_fwd_multi: waves per workgroup (they share one LDS filter table)
 constexpr int kMultiPoints = 8 * kMultiWaves;         // output points per workgroup
 constexpr int kBatch = 8;               // dwconv_fwd_row: neighbours whose gathers are issued together
 
@@ -382,12 +375,8 @@ __global__ __launch_bounds__(256) void dwconv_fwd_generic(
 constexpr int kBwdTWaves = 4;
 constexpr int kBwdTPointsPerWG = 64;     // measured: 256 -> 1.90 ms, 128 -> 1.15, 64 -> 0.90, 32 -> 0.91, 16 -> 1.22 (tail / balance vs per-block setup)
 
-#ifndef SPH3D_BWD_NL2
-#define SPH3D_BWD_NL2 3     // wave loads per batch of the half-wave form (2 edges per load)
-#endif
-#ifndef SPH3D_BWD_NL4
-#define SPH3D_BWD_NL4 2     // ... of the quarter-wave form (4 edges per load)
-#endif
+constexpr int kBwdNL2 = 3;     // wave loads per batch of the half-wave form (2 edges per load)
+constexpr int kBwdNL4 = 2;     // ... of the quarter-wave form (4 edges per load)
 // PARTS = 2 (CR <= 128, V == 4): a grad_out row is at most 32 lanes wide, so the two halves of the wave take ALTERNATE edges of
 // a segment (one wave load = two rows) and keep separate partial sums, added across the halves once per source
 // (grad_input) / once per launch (the filter accumulators).  PARTS = 4 (CR <= 64): four quarter waves, four rows per load
@@ -574,7 +563,7 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
                     if (HALF) {
                         // the two half-waves take alternate edges: lane-half h reads edge e + 2u + h of the chunk through
                         // ds_bpermute (lane number modulo 64, scales masked to the segment: see the full-wave branch)
-                        constexpr int NL = PARTS == 2 ? SPH3D_BWD_NL2 : SPH3D_BWD_NL4;          // wave loads per batch = PARTS * NL edges
+                        constexpr int NL = PARTS == 2 ? kBwdNL2 : kBwdNL4;          // wave loads per batch = PARTS * NL edges
                         const float svh = ((unsigned)(lane - e0) < (unsigned)(e1 - e0)) ? sv : 0.f;
                         // (exact-count last batches, which pay in the full-wave branch, measured no gain here: 0.305 vs 0.319 ms)
                         // a batch that runs past lane 63 wraps (ds_bpermute takes the lane modulo 64) onto lanes 0.. of the chunk, which
@@ -959,10 +948,7 @@ static int vec_plan(int F, int CR, int r, int& V)
 //   * small levels (N = 128..768: the whole launch is a few hundred sources per XCD): the kernel is a chain of
 //     dependent gathers per source, so the sources are spread over enough workgroups to put two on every CU
 //     (down to 2 sources per wave) instead of leaving most CUs idle.
-#ifndef SPH3D_BWD_FILL
-#define SPH3D_BWD_FILL 128
-#endif
-constexpr int kBwdFillWG = SPH3D_BWD_FILL;   // workgroups per XCD that a small level is spread over (compact kernel: 4 fit a CU)
+constexpr int kBwdFillWG = 128;   // workgroups per XCD that a small level is spread over (compact kernel: 4 fit a CU)
 static void bwd_plan(int B, int N, int nslices, int wg_per_cu, int& parts, int& W)
 {
     int g = B & 7;                         // gcd(B, 8)
@@ -990,17 +976,11 @@ static int bwd_slices(int F, int CR, int r)
 
 // hub sources (dwconv_bwd_t_vec<..., HUB>): clouds of at least 32 768 points (measured: at 16 384 the two extra launches cost more
 // than the few hubs of that level give back, profiles/r06_ab_conv_hub.log), sources with more than 1024 in-edges; kHubWG
-// workgroups per channel slice in the hub launch.  SPH3D_BWD_HUB_MIN_N / SPH3D_BWD_HUB_T: read per call (tests, experiments)
-constexpr int kHubWG = 1024;       // slabs reserved for the hub launch (its workgroup count: hub_wgs() <= kHubWG)
-static int hub_wgs()
-{
-    const char* e = getenv("SPH3D_BWD_HUB_WG");
-    int w = e ? atoi(e) : 1024;
-    w = w < kHubGroup ? kHubGroup : (w > kHubWG ? kHubWG : w);
-    return w - w % kHubGroup;
-}
-static int hub_min_n() { const char* e = getenv("SPH3D_BWD_HUB_MIN_N"); return e ? atoi(e) : 32768; }
-static int hub_threshold() { const char* e = getenv("SPH3D_BWD_HUB_T"); const int t = e ? atoi(e) : 1024; return t < 1 ? 1 : t; }
+// workgroups per channel slice in the hub launch.  Test hooks SPH3D_BWD_HUB_MIN_N / SPH3D_BWD_HUB_T: read per call
+constexpr int kHubWG = 1024;       // workgroups of the hub launch (a multiple of kHubGroup) = slabs reserved for it
+static_assert(kHubWG % kHubGroup == 0, "hub workgroups come in groups of kHubGroup");
+static int hub_min_n() { return test_hook("SPH3D_BWD_HUB_MIN_N", 32768); }
+static int hub_threshold() { const int t = test_hook("SPH3D_BWD_HUB_T", 1024); return t < 1 ? 1 : t; }
 
 extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r)
 {
@@ -1051,7 +1031,6 @@ static int launch_bwd_t_vec(int B, int N, int M, int F, int C, const int* offset
             int rc = check_hip(hipMemsetAsync(hub_list, 0, sizeof(int), st), "conv3d grad: hub list");
             if (rc) return rc;
             const int T = hub_threshold();
-            const int HW = hub_wgs();
             auto kern1 = dwconv_bwd_t_vec<R, V, MAXF, PARTS, false, 1>;
             auto kern2 = dwconv_bwd_t_vec<R, V, MAXF, PARTS, false, 2>;
             auto kernc1 = dwconv_bwd_t_vec<R, V, kCompactBins, PARTS, true, 1>;
@@ -1066,18 +1045,18 @@ static int launch_bwd_t_vec(int B, int N, int M, int F, int C, const int* offset
                 hipLaunchKernelGGL(kernc1, dim3(8 * Wc * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, Wc, pc, nslices, offsets, ent_key,
                                    ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
                                    hub_list, T, 0);
-                hipLaunchKernelGGL(kernc2, dim3(HW * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, HW, 1, nslices, offsets,
+                hipLaunchKernelGGL(kernc2, dim3(kHubWG * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, kHubWG, 1, nslices, offsets,
                                    ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2,
                                    grad_input2, Ca, hub_list, T, 8 * Wc);
             }
             hipLaunchKernelGGL(kern1, dim3(8 * W * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, W, parts, nslices, offsets, ent_key,
                                ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
                                hub_list, T, 0);
-            hipLaunchKernelGGL(kern2, dim3(HW * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, HW, 1, nslices, offsets, ent_key,
+            hipLaunchKernelGGL(kern2, dim3(kHubWG * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, kHubWG, 1, nslices, offsets, ent_key,
                                ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
                                hub_list, T, 8 * W);
-            hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, 8 * W + HW, total, CR, partial,
-                               grad_filter, ab, kCompactBins, 8 * Wc + HW);
+            hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, 8 * W + kHubWG, total, CR, partial,
+                               grad_filter, ab, kCompactBins, 8 * Wc + kHubWG);
             return check_launch("sph3d_depthwise_conv3d_grad_t");
         }
     }

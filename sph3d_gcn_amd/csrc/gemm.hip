@@ -18,7 +18,7 @@
 // Ragged edges (Cin = 3, Cout = 13, R not a multiple of 128) take guarded scalar loads / stores.
 // TN splits R over workgroups; every split writes its partial tile to a workspace slab and a second kernel adds the
 // slabs in a fixed order (deterministic, no float atomics).
-#include <cstdlib>
+#include <atomic>
 #include "common.hpp"
 
 namespace sph3d {
@@ -30,13 +30,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 as_v4(const float4 v) { f32x4 r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; return r; }
 
-#ifndef SPH3D_GEMM_EXP
-#define SPH3D_GEMM_EXP 0      // diagnostic builds only (wrong results): 1 no global loads, 2 no LDS stores, 4 no barrier in the k loop
-#endif
-#ifndef SPH3D_GEMM_SETPRIO
-#define SPH3D_GEMM_SETPRIO 1
-#endif
-constexpr bool kSetPrio = SPH3D_GEMM_SETPRIO != 0;
 constexpr int BM = 128;
 constexpr int BKS = 16;      // k-tile for small grids (more workgroups per CU)
 constexpr int BKL = 32;      // k-tile for large grids (half the barriers)
@@ -221,18 +214,7 @@ struct Dma {
     }
 };
 
-#ifndef SPH3D_GEMM_DMA
-#define SPH3D_GEMM_DMA 1
-#endif
-#ifndef SPH3D_GEMM_NBUF
-#define SPH3D_GEMM_NBUF 2     // tile images of the LDS-DMA pipeline; 3 (tiles below 128 x 128): measured round 6, per shape and in the step: no change (profiles/r06_exp_gemm_nbuf.log)
-#endif
-#ifndef SPH3D_GEMM_SPLIT
-#define SPH3D_GEMM_SPLIT 1    // whole-tile products on the bf16 matrix pipe with three-way split operands (gemm_split_mfma); 0: fp32 MFMA
-#endif
-#ifndef SPH3D_GEMM_WGS
-#define SPH3D_GEMM_WGS 5      // workgroups per CU the unguarded BK = 16 kernels are built for
-#endif
+constexpr int kDmaWgs = 5;      // workgroups per CU the unguarded BK = 16 (LDS-DMA) kernels are built for
 constexpr int cmax_i(int a, int b) { return a > b ? a : b; }
 
 // epilogue shared by the fp32-MFMA kernel and the split-bf16 kernel (same C/D register layout: it is dtype-independent)
@@ -336,7 +318,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], float* lds,
 // per half tile of rows and per column, sum z and sum z*z with z = elu(y) — the partial sums the fused ELU+BN op's statistics
 // pass would otherwise produce by reading Y once more (norm.hip: norm_reduce_kernel, same [block][2][C] layout).
 template <bool AK, bool BKM, int BMT, int BN, int BK, bool SPLITK, bool GUARD, bool STATS = false>
-__global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 && SPH3D_GEMM_WGS > 4 ? SPH3D_GEMM_WGS : 4) : 2) void gemm_f32_mfma(int M, int N, int Kd, const float* __restrict__ A, int lda,
+__global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? kDmaWgs : 2) void gemm_f32_mfma(int M, int N, int Kd, const float* __restrict__ A, int lda,
                                                      const float* __restrict__ B, int ldb, float* __restrict__ Cmat,
                                                      int ldc, const float* __restrict__ bias, int act, int kchunk,
                                                      float* __restrict__ stats = nullptr, int nsplit = 1)
@@ -344,13 +326,11 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
     using SA = Stage<AK, BMT, BK>;
     using SB = Stage<BKM, BN, BK>;
     constexpr int LDK = BK + 4;
-    constexpr bool DMA = SPH3D_GEMM_DMA != 0 && !GUARD && BK == 16;       // LDS-DMA staging (see Dma)
+    constexpr bool DMA = !GUARD && BK == 16;       // LDS-DMA staging (see Dma)
     constexpr int WM = BMT / 2, WN = BN / 2;     // wave sub-tile
-    // LDS-DMA staging depth: tile t+2 is in flight while tile t is multiplied wherever three tile images still leave the
-    // occupancy alone (every tile but 128 x 128); with two images a k-tile iteration cannot be shorter than one memory round
-    // trip (the loads issued at its top are waited for at its bottom): SPH3D_GEMM_NBUF
-    constexpr int NBUF = DMA ? ((SPH3D_GEMM_NBUF >= 3 && (BMT + BN) <= 192) ? 3 : 2) : 2;
-    constexpr int LDSF = DMA ? cmax_i(NBUF * (BMT + BN) * BK, 4 * 32 * (WN == 64 ? WN : WN + 4)) : 2 * (SA::LDS_FLOATS + SB::LDS_FLOATS);
+    // LDS-DMA staging: two tile images.  (Three, with tile t+2 in flight while tile t is multiplied, for the tiles below 128 x 128
+    // where they leave the occupancy alone: measured round 6, per shape and in the step: no change; profiles/r06_exp_gemm_nbuf.log)
+    constexpr int LDSF = DMA ? cmax_i(2 * (BMT + BN) * BK, 4 * 32 * (WN == 64 ? WN : WN + 4)) : 2 * (SA::LDS_FLOATS + SB::LDS_FLOATS);
     __shared__ __attribute__((aligned(16))) float lds[LDSF];
     constexpr int TM = WM / 32, TN = WN / 32;    // MFMA tiles per wave
 
@@ -409,60 +389,6 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
         const size_t bstep = BKM ? (size_t)BK : (size_t)BK * ldb;
         da.issue(abase, lds);
         db.issue(bbase, lds + ABUF);
-        if constexpr (NBUF == 3) {
-            constexpr int NL = Dma<AK, BMT>::NI + Dma<BKM, BN>::NI;          // loads a wave has in flight per tile
-            const bool two = (k_begin + BK) < k_end;
-            if (two) {
-                abase += astep;
-                bbase += bstep;
-                da.issue(abase, lds + BUFD);
-                db.issue(bbase, lds + BUFD + ABUF);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");      // tile 0 has landed, tile 1 may still fly
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __syncthreads();
-            int buf = 0;
-            for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-                const bool more = (k0 + BK) < k_end, more2 = (k0 + 2 * BK) < k_end;
-                if (more2) {                  // tile t+2 -> the image tile t-1 was read from (every wave is past that iteration's barrier)
-                    const int nb = buf >= 1 ? buf - 1 : 2;
-                    abase += astep;
-                    bbase += bstep;
-                    da.issue(abase, lds + nb * BUFD);
-                    db.issue(bbase, lds + nb * BUFD + ABUF);
-                }
-                const float* ca = lds + buf * BUFD;
-                const float* cb = ca + ABUF;
-                if (kSetPrio) __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-                for (int g = 0; g < BK / 8; g++) {
-                    f32x4 af[TM], bf[TN];
-#pragma unroll
-                    for (int i = 0; i < TM; i++) af[i] = Dma<AK, BMT>::frag(ca, wm + i * 32 + li, g, lk);
-#pragma unroll
-                    for (int j = 0; j < TN; j++) bf[j] = Dma<BKM, BN>::frag(cb, wn + j * 32 + li, g, lk);
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; s4++) {
-#pragma unroll
-                        for (int i = 0; i < TM; i++)
-#pragma unroll
-                            for (int j = 0; j < TN; j++) {
-                                const float av = s4 == 0 ? af[i].x : (s4 == 1 ? af[i].y : (s4 == 2 ? af[i].z : af[i].w));
-                                const float bv = s4 == 0 ? bf[j].x : (s4 == 1 ? bf[j].y : (s4 == 2 ? bf[j].z : bf[j].w));
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-                            }
-                    }
-                }
-                if (kSetPrio) __builtin_amdgcn_s_setprio(0);
-                if (more) {                   // this wave's share of tile t+1 has landed (tile t+2 may still fly)
-                    if (more2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                __syncthreads();              // ONE barrier per k-tile
-                buf = buf == 2 ? 0 : buf + 1;
-            }
-        } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         int buf = 0;
@@ -476,7 +402,7 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
             }
             const float* ca = lds + buf * BUFD;
             const float* cb = ca + ABUF;
-            if (kSetPrio) __builtin_amdgcn_s_setprio(2);
+            __builtin_amdgcn_s_setprio(2);
 #pragma unroll
             for (int g = 0; g < BK / 8; g++) {
                 f32x4 af[TM], bf[TN];
@@ -496,11 +422,10 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
                         }
                 }
             }
-            if (kSetPrio) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of tile t+1 has landed
             __syncthreads();              // ONE barrier per k-tile
             buf ^= 1;
-        }
         }
     } else {
     SA sa;
@@ -526,7 +451,7 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
     int buf = 0;
     for (int k0 = k_begin; k0 < k_end; k0 += BK) {
         const bool more = (k0 + BK) < k_end;
-        if (more && !(SPH3D_GEMM_EXP & 1)) {                       // global -> registers for tile t+1 while tile t is multiplied
+        if (more) {                       // global -> registers for tile t+1 while tile t is multiplied
             if (GUARD) {
                 sa.template load<GUARD>(A, lda, m0, k0 + BK, M, k_end, a_vec);
                 sb.template load<GUARD>(B, ldb, n0, k0 + BK, N, k_end, b_vec);
@@ -539,7 +464,7 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
         }
         const float* ca = lds + buf * BUF;
         const float* cb = ca + SA::LDS_FLOATS;
-        if (kSetPrio) __builtin_amdgcn_s_setprio(2);
+        __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int g = 0; g < BK / 8; g++) {
             f32x4 af[TM], bf[TN];
@@ -559,12 +484,12 @@ __global__ __launch_bounds__(256, (BK == 16 && !GUARD) ? (SPH3D_GEMM_DMA != 0 &&
                     }
             }
         }
-        if (kSetPrio) __builtin_amdgcn_s_setprio(0);
-        if (more && !(SPH3D_GEMM_EXP & 2)) {                       // the other buffer: nobody reads it during this iteration
+        __builtin_amdgcn_s_setprio(0);
+        if (more) {                       // the other buffer: nobody reads it during this iteration
             sa.store(lds + (buf ^ 1) * BUF);
             sb.store(lds + (buf ^ 1) * BUF + SA::LDS_FLOATS);
         }
-        if (!(SPH3D_GEMM_EXP & 4)) __syncthreads();                  // ONE barrier per k-tile
+        __syncthreads();                  // ONE barrier per k-tile
         buf ^= 1;
     }
 
@@ -702,9 +627,6 @@ struct SplitStage {
     }
 };
 
-#ifndef SPH3D_SPLIT_DB
-#define SPH3D_SPLIT_DB 0      // 1: two plane images (one barrier per k-tile, 3 workgroups per CU at 128 x 128); 0: one image, two barriers, 4-5 per CU
-#endif
 __device__ int g_xs_fail = 0;      // exchange launches that gave up waiting (never expected)
 
 // XS (in-kernel split-K exchange, for products whose tile grid is too small to fill the chip and whose k loop is long): the grid holds
@@ -714,7 +636,7 @@ __device__ int g_xs_fail = 0;      // exchange launches that gave up waiting (ne
 // (deterministic), clears the counter and runs the ordinary epilogue (bias / ELU / BN statistics / float4 rows).  No slab-sum
 // launch, no float atomics.
 template <bool AK, bool BKM, int BMT, int BN, int BK, bool SPLITK, bool STATS, bool GUARD = false, bool XS = false>
-__global__ __launch_bounds__(256, SPH3D_SPLIT_DB ? 2 : 4) void gemm_split_mfma(int M, int N, int Kd, const float* __restrict__ A, int lda,
+__global__ __launch_bounds__(256, 4) void gemm_split_mfma(int M, int N, int Kd, const float* __restrict__ A, int lda,
                                                           const float* __restrict__ B, int ldb, float* __restrict__ Cmat, int ldc,
                                                           const float* __restrict__ bias, int act, int kchunk,
                                                           float* __restrict__ stats = nullptr, int nsplit = 1,
@@ -726,9 +648,9 @@ __global__ __launch_bounds__(256, SPH3D_SPLIT_DB ? 2 : 4) void gemm_split_mfma(i
     constexpr int WM = BMT / 2, WN = BN / 2;     // wave sub-tile
     constexpr int TM = WM / 32, TN = WN / 32;    // MFMA tiles per wave
     constexpr int BUFB = PA::BYTES + PB::BYTES;  // bytes of one plane image (A pieces, then B pieces)
-    constexpr bool DB = SPH3D_SPLIT_DB != 0;
     constexpr bool EPX = WN == 64;               // un-padded, XOR-swizzled epilogue slab (32 KB at 128 x 128)
-    constexpr int LDSF = cmax_i((DB ? 2 : 1) * BUFB / 4, 4 * 32 * (EPX ? WN : WN + 4));
+    // ONE plane image, two barriers per k-tile: 4-5 workgroups per CU (two images, one barrier: 3 per CU at 128 x 128)
+    constexpr int LDSF = cmax_i(BUFB / 4, 4 * 32 * (EPX ? WN : WN + 4));
     __shared__ __attribute__((aligned(16))) float lds[LDSF];
     char* img = reinterpret_cast<char*>(lds);
 
@@ -794,7 +716,6 @@ __global__ __launch_bounds__(256, SPH3D_SPLIT_DB ? 2 : 4) void gemm_split_mfma(i
     sb.store(img + PA::BYTES);
     __syncthreads();
 
-    int buf = 0;
     for (int k0 = k_begin; k0 < k_end; k0 += BK) {
         const bool more = (k0 + BK) < k_end;
         if (more) {                       // global -> registers for tile t+1 while tile t is multiplied
@@ -808,9 +729,9 @@ __global__ __launch_bounds__(256, SPH3D_SPLIT_DB ? 2 : 4) void gemm_split_mfma(i
                 sb.load(bbase, ldb, boff);
             }
         }
-        const char* ca = img + (DB ? buf * BUFB : 0);
+        const char* ca = img;
         const char* cb = ca + PA::BYTES;
-        if (kSetPrio) __builtin_amdgcn_s_setprio(2);
+        __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int s16 = 0; s16 < BK / 16; s16++) {
             const int g = 2 * s16 + lk;
@@ -835,22 +756,13 @@ __global__ __launch_bounds__(256, SPH3D_SPLIT_DB ? 2 : 4) void gemm_split_mfma(i
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][pa], bf[j][pb], acc[i][j], 0, 0, 0);
             }
         }
-        if (kSetPrio) __builtin_amdgcn_s_setprio(0);
-        if (DB) {
-            if (more) {                   // the other image: nobody reads it during this iteration
-                sa.store(img + (buf ^ 1) * BUFB);
-                sb.store(img + (buf ^ 1) * BUFB + PA::BYTES);
-            }
-            __syncthreads();              // ONE barrier per k-tile
-            buf ^= 1;
-        } else {
-            __syncthreads();              // every wave has its fragments of tile t in registers / the matrix pipe
-            if (more) {
-                sa.store(img);
-                sb.store(img + PA::BYTES);
-            }
-            __syncthreads();
+        __builtin_amdgcn_s_setprio(0);
+        __syncthreads();                  // every wave has its fragments of tile t in registers / the matrix pipe
+        if (more) {
+            sa.store(img);
+            sb.store(img + PA::BYTES);
         }
+        __syncthreads();
     }
     if (XS) {
         // The slabs and the counters are exchanged between workgroups on different XCDs (private L2s).  Every access to them is an
@@ -944,29 +856,24 @@ static unsigned gemm_grid(long long tiles_m, long long tiles_n, long long nsplit
 
 static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
-// whole-tile products on the bf16 pipe with split operands (gemm_split_mfma) unless SPH3D_GEMM_SPLIT=0 (A/B runs; the exact
-// fp32-MFMA kernels then); ragged shapes always take the fp32 kernels
-static int g_split_mode = -1;          // -1: not decided yet (environment / build default)
-static bool split_on()
-{
-    if (g_split_mode < 0) g_split_mode = getenv("SPH3D_GEMM_SPLIT") ? (atoi(getenv("SPH3D_GEMM_SPLIT")) != 0) : (SPH3D_GEMM_SPLIT != 0);
-    return g_split_mode != 0;
-}
+// whole-tile products on the bf16 pipe with split operands (gemm_split_mfma); sph3d_pointwise_gemm_mode(0) selects the exact
+// fp32-MFMA kernels instead.  Ragged shapes always take the fp32 kernels
+static std::atomic<int> g_split_mode{1};
+static bool split_on() { return g_split_mode.load(std::memory_order_relaxed) != 0; }
+
+// tile choice: the largest tile that still gives every CU TWO workgroups (measured: with >= 256 tiles as the rule the
+// mid-size levels ran 50 TF, with >= 512 they run 80-90 TF: one partial wave of workgroups leaves half the CUs idle)
+constexpr long long kMinTiles = 512;
 
 // In-kernel split-K exchange (gemm_split_mfma<..., XS>): splits per tile for a whole-tile product that would run as T 64 x 64 tiles
 // (grid Tg after XCD padding), 1 = do not split.  Up to ~1024 workgroups (4 per CU: all resident), at least 256 of k per split.
-// SPH3D_GEMM_XS: 0 off, n = at most n splits (experiments)
-static int xs_cap()
-{
-    static const int cap = getenv("SPH3D_GEMM_XS") ? atoi(getenv("SPH3D_GEMM_XS")) : 4;
-    return cap;
-}
+constexpr int kXsCap = 4;             // at most this many splits of a product (the weight gradient's short path: 8)
+constexpr int kXsMaxWgs = 1024;
+constexpr int kXsMaxTg = 384;
 static int xs_splits(long long Tg, int Kd, int bk, int cap)
 {
-    static const int max_wgs = getenv("SPH3D_GEMM_XS_WGS") ? atoi(getenv("SPH3D_GEMM_XS_WGS")) : 1024;      // (experiments)
-    static const int max_tg = getenv("SPH3D_GEMM_XS_TG") ? atoi(getenv("SPH3D_GEMM_XS_TG")) : 384;
-    int ns = (int)(max_wgs / (Tg > 0 ? Tg : 1));
-    if (Tg > max_tg) ns = 1;      // (512 tiles split in two: 22 vs 20 us at (2048, 512 -> 1024))
+    int ns = (int)(kXsMaxWgs / (Tg > 0 ? Tg : 1));
+    if (Tg > kXsMaxTg) ns = 1;      // (512 tiles split in two: 22 vs 20 us at (2048, 512 -> 1024))
     if (ns > cap) ns = cap;
     while (ns > 1 && (Kd % (bk * ns) != 0 || Kd / ns < 256)) ns--;
     return ns < 1 ? 1 : ns;
@@ -984,10 +891,8 @@ template <bool AK, bool BKM, bool GUARD>
 static void launch_gemm_tiles(int M, int N, int Kd, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                               const float* bias, int act, hipStream_t st)
 {
-    // tile choice: the largest tile that still gives every CU TWO workgroups (measured: with >= 256 tiles as the rule the
-    // mid-size levels ran 50 TF, with >= 512 they run 80-90 TF: one partial wave of workgroups leaves half the CUs idle)
+    // tile choice: see kMinTiles
     auto ntiles = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    static const long long kMinTiles = getenv("SPH3D_GEMM_MINTILES") ? atoi(getenv("SPH3D_GEMM_MINTILES")) : 512;      // (experiments)
     // (BK = 32 at two workgroups per CU for the big grids: measured slower than BK = 16 at four, before and after the
     //  round-2 register fix: 0.101 vs 0.094 ms at (131072, 256 -> 128))
     if constexpr (GUARD) {
@@ -1008,8 +913,7 @@ static void launch_gemm_tiles(int M, int N, int Kd, const float* A, int lda, con
     }
     if constexpr (!GUARD) {
         if (split_on()) {
-            // 64 x 64 tiles take two MFMA k-steps per barrier where K allows.  SPH3D_SPLIT_MINTILES: experiments
-            static const long long kMinTiles = getenv("SPH3D_SPLIT_MINTILES") ? atoi(getenv("SPH3D_SPLIT_MINTILES")) : 512;
+            // 64 x 64 tiles take two MFMA k-steps per barrier where K allows
             if (N > 64 && ntiles(128, 128) >= kMinTiles)
                 hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 128, 128, 16, false, false>), dim3(gemm_grid((M + 127) / 128, (N + 127) / 128)), dim3(256),
                                    0, st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
@@ -1018,7 +922,7 @@ static void launch_gemm_tiles(int M, int N, int Kd, const float* A, int lda, con
                                    st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
             else if (Kd % 32 == 0) {
                 const long long Tg = gemm_grid(M / 64, N / 64);
-                const int ns = xs_splits(Tg, Kd, 32, xs_cap());
+                const int ns = xs_splits(Tg, Kd, 32, kXsCap);
                 char* xb = ns > 1 ? xs_buffer(st, (long long)(M / 64) * (N / 64), ns, 64 * 64) : nullptr;
                 if (xb != nullptr)
                     hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 64, 64, 32, false, false, false, true>), dim3((unsigned)(Tg * ns)), dim3(256), 0, st,
@@ -1071,7 +975,6 @@ static int nn_stats_tile(int M, int N, int Kd, int& bm, int& bn)
     const bool whole = (M % 128 == 0) && (N % 64 == 0) && (N <= 64 || N % 128 == 0) && (Kd % BKS == 0) && (Kd % 4 == 0) && (N % 4 == 0);
     if (!whole) return 0;
     auto ntiles = [&](int a, int b) { return (long long)((M + a - 1) / a) * ((N + b - 1) / b); };
-    static const long long kMinTiles = getenv("SPH3D_GEMM_MINTILES") ? atoi(getenv("SPH3D_GEMM_MINTILES")) : 512;      // (experiments)
     if (N > 64 && ntiles(128, 128) >= kMinTiles) { bm = 128; bn = 128; }
     else if (ntiles(128, 64) >= kMinTiles) { bm = 128; bn = 64; }      // (N > 64 too: 32768 x 1024 -> 128 measured 81 vs 90 us with 64 x 64)
     else { bm = 64; bn = 64; }
@@ -1087,12 +990,11 @@ static void tn_plan(int R, int Cin, int Cout, int& bn, int& tiles, int& nsplit, 
     // ~2 workgroups per CU in total: measured round 2 over the 13 S3DIS shapes, 512 workgroups 0.97 ms against 1.10 ms
     // with 1024 (twice the partial tiles to write and re-read, half the k-loop to amortise prologue and epilogue) and
     // 1.11 ms with 256
-    // SPH3D_TN_WGS: experiments.  Round 5 sweep over 256 / 384 / 512 / 768 / 1024 (tools/exp_gemm_knobs.py,
-    // profiles/r05_exp_gemm_knobs.log): 512 is the best single value (0.79 ms over the 13 shapes; per-shape optimum 0.77);
-    // only the short products with few tiles ((12288, 512 -> 256), (6144, 512 -> 512): <= 16 tiles, <= 12288 rows) want fewer,
-    // fatter splits: 38 / 40 us at 256 workgroups against 46 / 46
-    static const int forced = getenv("SPH3D_TN_WGS") ? atoi(getenv("SPH3D_TN_WGS")) : 0;
-    const int target = forced > 0 ? forced : ((R <= 12288 && tiles <= 16) ? 256 : 512);
+    // Round 5 sweep over 256 / 384 / 512 / 768 / 1024 (tools/exp_gemm_knobs.py, profiles/r05_exp_gemm_knobs.log): 512 is the
+    // best single value (0.79 ms over the 13 shapes; per-shape optimum 0.77); only the short products with few tiles
+    // ((12288, 512 -> 256), (6144, 512 -> 512): <= 16 tiles, <= 12288 rows) want fewer, fatter splits: 38 / 40 us at 256
+    // workgroups against 46 / 46
+    const int target = (R <= 12288 && tiles <= 16) ? 256 : 512;
     int want = (target + tiles - 1) / tiles;   // (re-measured with the LDS-DMA kernel: 512 -> 2.25 ms over the 13 shapes, 768 2.46, 1024 2.31, 2048 2.28)
     int maxsplit = (R + 255) / 256;                   // at least 256 rows of k per split
     nsplit = want < maxsplit ? want : maxsplit;
@@ -1115,9 +1017,8 @@ extern "C" int sph3d_pointwise_gemm_exchange_failures(void)
 
 extern "C" int sph3d_pointwise_gemm_mode(int mode)
 {
-    const int prev = split_on() ? 1 : 0;
-    if (mode == 0 || mode == 1) g_split_mode = mode;
-    return prev;
+    if (mode == 0 || mode == 1) return g_split_mode.exchange(mode);
+    return g_split_mode.load();
 }
 
 extern "C" int sph3d_pointwise_gemm(int R, int Cin, int Cout, const float* X, const float* W, const float* bias, int act,
@@ -1158,7 +1059,7 @@ extern "C" int sph3d_pointwise_gemm_bnstats(int R, int Cin, int Cout, const floa
             hipLaunchKernelGGL((gemm_split_mfma<true, false, 128, 64, 16, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X, Cin, W,
                                Cout, Y, Cout, bias, 0, 0, partial);
         else if (Cin % 32 == 0) {
-            const int ns = xs_splits(tiles, Cin, 32, xs_cap());
+            const int ns = xs_splits(tiles, Cin, 32, kXsCap);
             char* xb = ns > 1 ? xs_buffer(st, (long long)(R / 64) * (Cout / 64), ns, 64 * 64) : nullptr;
             if (xb != nullptr)
                 hipLaunchKernelGGL((gemm_split_mfma<true, false, 64, 64, 32, false, true, false, true>), dim3(tiles * ns), dim3(256), 0, st, R, Cout,
@@ -1216,9 +1117,9 @@ extern "C" int sph3d_pointwise_gemm_tn(int R, int Cin, int Cout, const float* X,
     // short products (few rows of k, many output tiles): 64 x 64 tiles with the in-kernel exchange — up to 8 splits whose slabs are
     // 16 KB — instead of 128 x 128 tiles + slab-sum launch.  (The exchange with 128 x 128 tiles and 8-16 splits was measured and is
     // SLOWER than the slab-sum kernel: 72 vs 38, 82 vs 50, 84 vs 62 us — split 0 reads 7-15 64-KB slabs past the cache, one dword per
-    // lane and instruction; profiles/r06_exp_gemm_xs.log.)  SPH3D_GEMM_TN_XS: largest R that takes this path (experiments)
-    static const int tn_xs_rows = getenv("SPH3D_GEMM_TN_XS") ? atoi(getenv("SPH3D_GEMM_TN_XS")) : 2048;
-    if (split_on() && R <= tn_xs_rows && Cin % 64 == 0 && Cout % 64 == 0 && R % 32 == 0 && aligned16(X) && aligned16(dY) && aligned16(dW)) {
+    // lane and instruction; profiles/r06_exp_gemm_xs.log.)  kTnXsRows: largest R that takes this path
+    constexpr int kTnXsRows = 2048;
+    if (split_on() && R <= kTnXsRows && Cin % 64 == 0 && Cout % 64 == 0 && R % 32 == 0 && aligned16(X) && aligned16(dY) && aligned16(dW)) {
         const long long Tg = gemm_grid(Cin / 64, Cout / 64);
         const int ns = xs_splits(Tg, R, 32, 8);
         char* xb = ns > 1 ? xs_buffer(st, (long long)(Cin / 64) * (Cout / 64), ns, 64 * 64) : nullptr;

@@ -17,7 +17,6 @@
 //     bit patterns (6 rounds) and the inner loop is sub/mul/add/compare only: no sqrt per pair,
 //     bit-identical decisions.
 //   * -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz must round exactly like the oracle.
-#include <cstdlib>
 #include "common.hpp"
 #include "sphere_bin.hpp"
 #include "nnquery.hpp"
@@ -500,15 +499,12 @@ static int sphere_neighbor(int fixed, int B, int N, int M, int nn_sample, float 
     // (device flag `gate`) the chain kernel below recomputes the call, after the fused counters have been cleared again.
     const int* gate = nullptr;
     int grid_done = 0;
-    static const bool grid_on = !(getenv("SPH3D_NNGRID") && atoi(getenv("SPH3D_NNGRID")) == 0);
-    if (grid_on) {
-        const int g = nngrid_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
-                                    &grid_done, search_ws, search_ws_bytes, library_scratch);
-        if (g < 0) return g;
-        if (g > 0 && fuse != nullptr && fuse->deg != nullptr) {
-            const long long cnt = (long long)B * N * fuse->F + fuse->F;
-            hipLaunchKernelGGL(gated_zero_kernel, dim3(256), dim3(256), 0, st, gate, fuse->deg, cnt);
-        }
+    const int g = nngrid_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
+                                &grid_done, search_ws, search_ws_bytes, library_scratch);
+    if (g < 0) return g;
+    if (g > 0 && fuse != nullptr && fuse->deg != nullptr) {
+        const long long cnt = (long long)B * N * fuse->F + fuse->F;
+        hipLaunchKernelGGL(gated_zero_kernel, dim3(256), dim3(256), 0, st, gate, fuse->deg, cnt);
     }
 #define SPH3D_NN(CP, MU)                                                                                          \
     return hb ? launch_sphere<CP, MU, true>(B, N, M, nn_sample, radius, chunkN, database, query, nn_index, nn_count, nn_dist, st, fixed, fuse, gate, grid_done) \

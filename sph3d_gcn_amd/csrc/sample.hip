@@ -19,7 +19,6 @@
 // caller-provided workspace (the reference's `temp`) and re-reads xyz from L2.
 // -ffp-contract=off: d = (dx*dx + dy*dy) + dz*dz must round like the oracle.
 #include <atomic>
-#include <cstdlib>
 #include "common.hpp"
 
 namespace sph3d {
@@ -164,7 +163,7 @@ __global__ __launch_bounds__(1024) void fps_reg_kernel(int b, int n, int m,
 //     code instead of branching per slot (0.95, 1.10 with the blobs dealt in turn); a wave owning P CONSECUTIVE blobs (0.97).
 //     This form (with the atomic-max exchange and the winning lane publishing its own coordinates, below): 0.82 us per round at
 //     8192 points (plain 1.09), 0.87 at 10 000 (1.39), 0.70 at 4096 (0.77), 0.69 at 2500 (0.77); at 2048 the plain kernel stays
-//     ahead (0.61 against 0.69).  Two diagnostic builds (-DSPH3D_FPS_EXP) bound what is left: a round WITHOUT any update (box
+//     ahead (0.61 against 0.69).  Two diagnostic builds (wrong samples) bound what is left: a round WITHOUT any update (box
 //     test, publish, barrier, exchange) takes 0.24 us; the rest is the dependent path of the waves with work — above all of the
 //     wave that owned the winner: its candidate just became the sample, so it updates, rescans and re-elects every round;
 //   * the reference's tie-break (tf_sample_gpu.cu:49,56-66: larger distance, then lower thread id k mod 1024, then lower k)
@@ -209,14 +208,6 @@ struct __attribute__((aligned(16))) FpsSlotP {
 };
 
 constexpr int kPruneCells = 4096;
-
-// -DSPH3D_FPS_PROF (diagnostic builds only, tools/gpu_fps_prof.sh): cycle counts of the round loop's phases, per wave of cloud 0
-#ifdef SPH3D_FPS_PROF
-__device__ unsigned long long g_fps_prof[16][8];
-#define FPS_CLK() __builtin_readcyclecounter()
-#else
-#define FPS_CLK() 0ull
-#endif
 
 // P points per lane (lane p < P holds slot p's box), NW waves per workgroup
 template <int P, int NW>
@@ -354,21 +345,14 @@ __global__ __launch_bounds__(64 * NW) void fps_prune_kernel(int b, int n, int m,
         if (t < 3) cell[t] = 0ull;
         __syncthreads();
 
-#ifdef SPH3D_FPS_PROF
-        unsigned long long pf[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // own work (active / idle rounds), their counts, publish + barrier, post, rescans, their own cycles
-#endif
         for (int j = 1; j < m; j++) {
-            const unsigned long long tk0 = FPS_CLK(); (void)tk0;
             // ---- which slots can the new sample change? (lane p tests slot p; v_med3_f32 = the clamp into [lo, hi]) ----
             const float qx = __builtin_amdgcn_fmed3f(x1, blx, bhx), qy = __builtin_amdgcn_fmed3f(y1, bly, bhy),
                         qz = __builtin_amdgcn_fmed3f(z1, blz, bhz);
             const float ex = qx - x1, ey = qy - y1, ez = qz - z1;
             const float dbox = (ex * ex + ey * ey) + ez * ez;
             const bool need = lane < P && !(dbox >= g);        // NaN on either side: update
-#ifndef SPH3D_FPS_EXP
-#define SPH3D_FPS_EXP 0        // diagnostic builds only (WRONG samples): 1 = never rescan after round 1, 2 = never update after round 1
-#endif
-            const unsigned mask = (SPH3D_FPS_EXP == 2 && j > 1) ? 0u : (unsigned)__ballot(need);
+            const unsigned mask = (unsigned)__ballot(need);
             u64 stale = j == 1 ? ~0ull : 0ull;                 // lanes whose cached arg-max was lowered this round
             if (mask != 0u) {
 #pragma unroll
@@ -387,7 +371,6 @@ __global__ __launch_bounds__(64 * NW) void fps_prune_kernel(int b, int n, int m,
                     }
                 }
             }
-            if (SPH3D_FPS_EXP == 1 && j > 1) stale = 0ull;
             if (stale != 0ull) {
                 // ---- some lane's arg-max moved: every lane rescans its points (a tournament: log2 P dependent steps), the
                 // wave re-elects its candidate ----
@@ -427,7 +410,6 @@ __global__ __launch_bounds__(64 * NW) void fps_prune_kernel(int b, int n, int m,
                 c_vb = wmb;
                 dirty = 2;                                     // both parities of the wave's slot take the new coordinates
             }
-            const unsigned long long tk1 = FPS_CLK(); (void)tk1;
             // ---- exchange: every wave publishes its candidate's coordinates and raises the round's cell to its key with ONE LDS
             // atomic max: (distance bits) << 32 | sec << 4 | wave — the largest key is the reference's winner (sec is unique per
             // point, so the wave bits never decide) and names the slot that holds its coordinates.  After the barrier a wave reads
@@ -455,7 +437,6 @@ __global__ __launch_bounds__(64 * NW) void fps_prune_kernel(int b, int n, int m,
                 __hip_atomic_fetch_max(&cell[c3], ((u64)c_vb << 32) | ((u64)c_sec << 4) | (u64)wave, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_WORKGROUP);
             __syncthreads();
-            const unsigned long long tk2 = FPS_CLK(); (void)tk2;
             const u64 win = cell[c3];                              // the same address in every lane: a broadcast read
             const int c3n = c3 == 2 ? 0 : c3 + 1;
             if (t == 0) cell[c3n == 2 ? 0 : c3n + 1] = 0ull;       // = (c3 + 2) % 3
@@ -471,34 +452,9 @@ __global__ __launch_bounds__(64 * NW) void fps_prune_kernel(int b, int n, int m,
                 const int k = gsec != 0u ? (((255 - (int)(gsec & 255u)) << 10) | (1023 - (int)(gsec >> 8))) : 0;
                 idxs[(size_t)i * m + j] = k;
             }
-#ifdef SPH3D_FPS_PROF
-            {
-                const unsigned long long tk3 = FPS_CLK();
-                const bool active = mask != 0u;
-                pf[active ? 0 : 1] += tk1 - tk0;
-                pf[active ? 2 : 3] += 1;
-                pf[4] += tk2 - tk1;
-                pf[5] += tk3 - tk2;
-                pf[6] += stale != 0ull ? 1 : 0;
-                pf[7] += (stale != 0ull) ? (tk1 - tk0) : 0ull;       // own cycles of the rounds with a rescan
-            }
-#endif
         }
-#ifdef SPH3D_FPS_PROF
-        if (i == 0 && lane == 0)
-            for (int q = 0; q < 8; q++) g_fps_prof[wave][q] = pf[q];
-#endif
     }
 }
-
-#ifdef SPH3D_FPS_PROF
-}  // namespace sph3d
-extern "C" int sph3d_debug_fps_prof(unsigned long long* out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(sph3d::g_fps_prof), sizeof(unsigned long long) * 16 * 8) == hipSuccess ? 0 : -3;
-}
-namespace sph3d {
-#endif
 
 // Fallback for very large clouds: running distance in global workspace (the reference's temp[32][n]),
 // xyz re-read from L2 each round.  Same arithmetic and tie-break.
@@ -584,17 +540,9 @@ __global__ __launch_bounds__(1024) void fps_big_kernel(int b, int n, int m, cons
 // correctness: the launcher queues fps_big_kernel behind it, gated on the error word, which recomputes every cloud's samples
 // the slow way when (and only when) the co-operative pass gave up.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef SPH3D_FPS_COOP_P
-#define SPH3D_FPS_COOP_P 4
-#endif
-constexpr int kCoopP = SPH3D_FPS_COOP_P;   // points per thread
+constexpr int kCoopP = 4;                  // points per thread
 constexpr int kCoopPts = kRefBlock * kCoopP;
-#ifndef SPH3D_FPS_COOP_ERRPOLL
-#define SPH3D_FPS_COOP_ERRPOLL 0
-#endif
-#ifndef SPH3D_FPS_COOP_SLOAD
-#define SPH3D_FPS_COOP_SLOAD 1
-#endif
+constexpr int kCoopErrPoll = 0;            // the failed poll (mod 16) that also looks at the error word
 
 __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int xcd_local, int n, int m, int G, const float* __restrict__ dataset,
                                                         unsigned long long* __restrict__ slots, int* __restrict__ err,
@@ -680,7 +628,7 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int xcd_local, in
                 if (__ballot(ok) == ~0ull) break;
                 // (the error word is looked at every 16th poll only: a second fabric round trip in EVERY failed poll doubled the
                 //  period of the poll, i.e. the mean delay between a granule's arrival and its detection)
-                if (++spins > (1 << 22) || ((spins & 15) == SPH3D_FPS_COOP_ERRPOLL && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                if (++spins > (1 << 22) || ((spins & 15) == kCoopErrPoll && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                     if (lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     v = ~0ull;                                                   // poison: the round loop ends below
                     break;
@@ -710,11 +658,7 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int xcd_local, in
             }
         }
         __syncthreads();
-#if SPH3D_FPS_COOP_SLOAD
         const int k = uniform(win_k[buf]);                                       // scalar loads of the winner's point (read-only cloud)
-#else
-        const int k = win_k[buf];
-#endif
         if (k < 0) break;                                                        // time-out: give up (err is set)
         x1 = pts[(size_t)k * 3];
         y1 = pts[(size_t)k * 3 + 1];
@@ -739,30 +683,15 @@ static int coop_groups(int b, int n)
 static size_t coop_slot_bytes(int b, int G) { return (256 + sizeof(unsigned long long) * (size_t)b * 2 * G + 255) & ~(size_t)255; }
 
 // test hook: SPH3D_FPS_FORCE_TIMEOUT=1 starts the co-operative kernel with its error word already set, so the repair pass runs
-static int fps_force_timeout()
+// (read once)
+static bool fps_force_timeout()
 {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("SPH3D_FPS_FORCE_TIMEOUT");
-        v = (e && atoi(e) != 0) ? 1 : 0;
-    }
+    static const bool v = test_hook("SPH3D_FPS_FORCE_TIMEOUT", 0) != 0;
     return v;
 }
 
-// cloud size from which the pruned kernel is used (SPH3D_FPS_PRUNE=<points>, 0 = never; read once)
-#ifndef SPH3D_FPS_PRUNE_MIN
-#define SPH3D_FPS_PRUNE_MIN 2049
-#endif
-static int fps_prune_min_points()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("SPH3D_FPS_PRUNE");
-        v = e ? atoi(e) : SPH3D_FPS_PRUNE_MIN;
-        if (v <= 0) v = 1 << 30;
-    }
-    return v;
-}
+// cloud size from which the pruned kernel is used
+constexpr int kFpsPruneMin = 2049;
 
 extern "C" size_t sph3d_farthest_point_sample_workspace(int b, int n, int m)
 {
@@ -788,15 +717,14 @@ extern "C" int sph3d_farthest_point_sample(int b, int n, int m, const float* inp
     const dim3 grid(b), block(bs);
 #define SPH3D_FPS(PP) hipLaunchKernelGGL(fps_reg_kernel<PP>, grid, block, 0, st, b, n, m, inp, out)
     // clouds of 2049 .. 16384 points: the pruned kernel (same samples bit for bit; at 2048 points it only ties with the plain
-    // kernel: 0.620 vs 0.614 us per round).  SPH3D_FPS_PRUNE=0 switches it off, =<n>: for clouds of at least n points
-    if (n >= fps_prune_min_points() && n > kRefBlock && n <= 16384 && m > 1) {
+    // kernel: 0.620 vs 0.614 us per round)
+    if (n >= kFpsPruneMin && n > kRefBlock && n <= 16384 && m > 1) {
         const int need = (n + kRefBlock - 1) / kRefBlock;
         const dim3 pblock(kRefBlock);
 #define SPH3D_FPSP(PP) hipLaunchKernelGGL((fps_prune_kernel<PP, 16>), grid, pblock, 0, st, b, n, m, inp, out)
         if (need <= 4) SPH3D_FPSP(4);
         else if (need <= 8) SPH3D_FPSP(8);
         else SPH3D_FPSP(16);
-#undef SPH3D_FPSPN
 #undef SPH3D_FPSP
     }
     else if (P <= 1) SPH3D_FPS(1);
@@ -824,11 +752,10 @@ extern "C" int sph3d_farthest_point_sample(int b, int n, int m, const float* inp
             }
             unsigned long long* slots = (unsigned long long*)((char*)workspace + 256);
             // all workgroups of a cloud on one XCD while they take at most half of its 32 CUs (one 1024-thread workgroup per CU)
-            static const int xcd_env = getenv("SPH3D_FPS_COOP_XCD") ? atoi(getenv("SPH3D_FPS_COOP_XCD")) : 1;      // (experiments)
             const int rounds8 = (b + 7) / 8;
             // (launches rotate over the XCDs: two sampling streams' kernels of one-cloud batches would share XCD 0 otherwise)
             static std::atomic<unsigned> rotate{0};
-            const int xcd_local = (xcd_env != 0 && rounds8 * G <= 16) ? 1 + (int)(rotate.fetch_add(1, std::memory_order_relaxed) & 7u) : 0;      // (32 per XCD measured slower than spread: 2.88 vs 2.46 us per round at 131 072 points)
+            const int xcd_local = rounds8 * G <= 16 ? 1 + (int)(rotate.fetch_add(1, std::memory_order_relaxed) & 7u) : 0;      // (32 per XCD measured slower than spread: 2.88 vs 2.46 us per round at 131 072 points)
             const unsigned nblk = xcd_local ? (unsigned)(8 * rounds8 * G) : (unsigned)(b * G);
             hipLaunchKernelGGL(fps_coop_kernel, dim3(nblk), dim3(kRefBlock), 0, st, b, xcd_local, n, m, G, inp, slots, err, out);
             rc = check_launch("sph3d_farthest_point_sample (co-operative pass)");

@@ -15,7 +15,6 @@
 // k-order of the product: lane (i = lane % 16, kq = lane / 16) supplies A[i][16t + 4kq + u] and B[16t + 4kq + u][j] at step
 // (t, u): any pairing is legal as long as A and B use the same one, and this one makes a lane's four A values of a t ONE
 // ds_read_b128.  fp32 MFMA is exact fp32 FMA arithmetic; results differ from the separate kernels by summation order only.
-#include <cstdlib>
 #include "common.hpp"
 
 namespace sph3d {
@@ -525,9 +524,8 @@ extern "C" int sph3d_separable_conv3d_fused(int B, int N, int M, int F, int C, i
     }
     if (B == 0 || M == 0) return SPH3D_OK;
     hipStream_t st = as_stream(stream);
-    // SPH3D_SC_RING: 1 (default) the barrier-free kernel wherever it covers the shape, 0 never (A/B measurements)
-    static const bool use_ring = !(getenv("SPH3D_SC_RING") && atoi(getenv("SPH3D_SC_RING")) == 0);
-    if (use_ring && sepring_infer_ok(N, F, C, r, K, Cout))
+    // the barrier-free kernel wherever it covers the shape
+    if (sepring_infer_ok(N, F, C, r, K, Cout))
         return sepring_infer(B, N, M, F, C, r, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
                              pointwise_weights, bias, scale, shift, output, st);
     if (!small) {

@@ -23,7 +23,6 @@
 // one wave execute in order, so "row written, then counter raised" needs no fence, only a compiler barrier.
 // Spins are bounded: a wave that polls ~2^22 times raises a device flag and the workgroup drains (results wrong, no hang);
 // sph3d_separable_conv3d_ring_failures() reads the flag (tests).
-#include <cstdlib>
 #include "common.hpp"
 
 namespace sph3d {
@@ -325,8 +324,6 @@ static int sr_ring_depth(int F, int C, int r)
     const size_t fixed = sizeof(float) * sr_filter_floats(F, C, r) + 256;
     if (fixed + 3 * rb > 160 * 1024) return 0;
     size_t nb = (160 * 1024 - fixed) / rb;
-    static const int forced = getenv("SPH3D_SR_NB") ? atoi(getenv("SPH3D_SR_NB")) : 0;      // (experiments)
-    if (forced >= 3 && (size_t)forced <= nb) return forced;
     return nb > 8 ? 8 : (int)nb;
 }
 

@@ -226,7 +226,7 @@ class FlatGradAllReduce:
             # backward on the ISSUING thread: handing the pass to the engine's device thread and waking up again when it is done
             # costs 0.1-1.3 ms per step of host time depending on the box (tools/exp_host_floor.py: 7.85 -> 6.56 ms to issue a
             # one-block step), and the ~400 launches of a step are what a rank's host has to keep ahead of its GPU
-            with torch.autograd.set_multithreading_enabled(os.environ.get("SPH3D_AUTOGRAD_THREAD", "0") == "1"):
+            with torch.autograd.set_multithreading_enabled(False):
                 grads = torch.autograd.grad(loss, self.params, allow_unused=True)
         finally:
             self._armed = False

@@ -14,7 +14,6 @@ libsph3d's HIP kernels.  TF1-isms are mapped as follows:
 """
 import contextlib
 import math
-import os
 
 import torch
 import torch.nn.functional as F
@@ -519,8 +518,8 @@ FUSE_SEPARABLE_INFERENCE = "auto"
 #       waves per CU a wave's MFMA block sits on the same dependent path as its gathers, and in training the depthwise tensor is
 #       written anyway (the weight gradient's operand); headline 1911 vs 1918 blocks/s in three alternating pairs;
 #   "auto": layers of at least _FUSED_TRAIN_MIN_ROWS output points;  True: wherever the kernel covers the shape.
-FUSE_SEPARABLE_TRAINING = {"0": False, "1": True, "auto": "auto"}.get(os.environ.get("SPH3D_FUSE_TRAIN", ""), False)      # (env: A/B runs of bench.py)
-_FUSED_TRAIN_MIN_ROWS = int(os.environ.get("SPH3D_FUSE_TRAIN_MIN_ROWS", "16384"))
+FUSE_SEPARABLE_TRAINING = False
+_FUSED_TRAIN_MIN_ROWS = 16384
 
 
 def _fused_train_pays(rows, C, r, Cout):

@@ -129,3 +129,37 @@ def test_product_never_imports_oracle():
             if f.endswith(".py"):
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(import|from)\s+oracle\b", src, flags=re.M), f
+
+
+def test_no_environment_switches():
+    """The library runs one configuration: it reads the environment only inside common.hpp's test_hook(), for the three test
+    hooks sph3d.h lists, and no SPH3D_* macro selects code.  The package reads only the loader override, the collectives switch
+    and the launcher / thread-count variables of harness/dist.py."""
+    csrc = os.path.join(ROOT, "sph3d_gcn_amd", "csrc")
+    hooks = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cpp", ".hpp")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        if f == "common.hpp":
+            helper = re.search(r"static inline int test_hook\(.*?\n\}", src, flags=re.S).group(0)
+            src = src.replace(helper, "")
+            assert "getenv" in helper
+        assert "getenv" not in src, f
+        assert not re.search(r"^\s*#\s*(ifdef|ifndef|if|elif)\b.*\bSPH3D_", src, flags=re.M), f
+        hooks |= set(re.findall(r'test_hook\("(\w+)"', src))
+    assert hooks == {"SPH3D_BWD_HUB_MIN_N", "SPH3D_BWD_HUB_T", "SPH3D_FPS_FORCE_TIMEOUT"}
+    header = open(HEADER).read()
+    assert all(h in header for h in hooks)
+
+    allowed = {"SPH3D_LIB", "SPH3D_FORCE_COLLECTIVES", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
+               "OMP_NUM_THREADS", "MKL_NUM_THREADS"}
+    pkg = os.path.join(ROOT, "sph3d_gcn_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(dirpath, f)).read()
+                uses = re.findall(r"\bos\.(?:environ|getenv)\b", src)
+                named = re.findall(r"""\bos\.(?:environ(?:\.get|\.setdefault|\.pop)?\s*[\[(]|getenv\s*\()\s*["'](\w+)["']""", src)
+                assert len(named) == len(uses), (f, "os.environ used without a literal variable name")
+                assert set(named) <= allowed, (f, sorted(set(named) - allowed))

@@ -1,7 +1,6 @@
 """Training-mode separable layer, per layer shape of the S3DIS plan the ring kernel covers (16 blocks x 8192 points):
 separate ops (depthwise kernel + GEMM with statistics epilogue) vs the one-kernel layer (csrc/sepring.hip), forward only (the
-backward passes are identical), isolated on the GPU; then the inference layer: barrier kernel (sepconv.hip) vs ring kernel
-(run the script with SPH3D_SC_RING=0 / 1).  usage: python tools/exp_sepconv_training.py"""
+backward passes are identical), isolated on the GPU; then the inference layer.  usage: python tools/exp_sepconv_training.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,7 +18,6 @@ def timeit(fn, n=20):
 xyz = torch.from_numpy(synth.s3dis_batch(1000, B, 8192)[0]).to(dev)
 levels = [(8192, 0.1, [(64, 128), (128, 128)]), (2048, 0.2, [(128, 256), (128, 128)])]
 cur = xyz
-print("SPH3D_SC_RING=%s SPH3D_SR_NB=%s" % (os.environ.get("SPH3D_SC_RING", "(default 1)"), os.environ.get("SPH3D_SR_NB", "(auto)")))
 with torch.no_grad():
     for n, rad, shapes in levels:
         while cur.shape[1] > n:

@@ -51,7 +51,7 @@ def busy(tag):
 
 mb = t.setdefault("mfma_pipe_busy", {})
 mb["_note"] = ("SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE/8) per launch: the fraction of the time the matrix pipe of a SIMD is busy; "
-               "v_mfma_f32_32x32x16_bf16 (split products, the default) = 32 busy cycles each, v_mfma_f32_32x32x2_f32 (SPH3D_GEMM_SPLIT=0) = 64")
+               "v_mfma_f32_32x32x16_bf16 (split products, the default) = 32 busy cycles each, v_mfma_f32_32x32x2_f32 (sph3d_pointwise_gemm_mode(0)) = 64")
 for key, tag in (("sph3d_pointwise_gemm[131072, 256, 128, 0, 0]", "nn"), ("sph3d_pointwise_gemm_bnstats[131072, 256, 128]", "nn"),
                  ("sph3d_pointwise_gemm[131072, 128, 256, 0, 1]", "nt"), ("sph3d_pointwise_gemm_tn[32768, 1024, 128]", "tn"),
                  ("sph3d_pointwise_gemm_tn[131072, 256, 128]", "tn0")):
@@ -109,7 +109,7 @@ if prev != TAG:
 t["_round_of_notes"] = TAG
 t["_note"] = ("Round %d (tools/gpu_profile_round.sh %s; raw per-kernel CSVs: profiles/%s_pmc_{fwd,bwd}_{FET,WRI,TCC}.csv, "
               "profiles/%s_pmc_sq{1,2}_{fwd,bwd}.csv, profiles/%s_pmc_mfma_{nn,nt,tn,tn0}.csv, profiles/%s_pmc_gemm{nn,tn,tn0}_{FET,WRI}.csv, "
-              "profiles/%s_pmc_nnquery_{after,chain}.csv).  Separate --pmc passes per counter group.  traffic bytes per launch = "
+              "profiles/%s_pmc_nnquery_after.csv).  Separate --pmc passes per counter group.  traffic bytes per launch = "
               "FETCH_SIZE[KB]*2*1024 + WRITE_SIZE[KB]*1024 (the x2 is the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md for "
               "16-B-per-lane reads, which is what all of these kernels issue)." % ((int(TAG[1:]),) + (TAG,) * 6))
 t["trace_us"]["_note"] = ("rocprofv3 --kernel-trace of `python bench.py --steps 10` (profiles/%s_kernel_trace_by_launch_shape.csv): mean "
