@@ -465,6 +465,19 @@ int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int Ca, int Cb
 int sph3d_adam_step(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                     float beta2, float eps, int step, sph3d_stream_t stream);
 
+/* ---- the input side of the S3DIS training loop (train_s3dis.py:114-142,343-347) on the device: one launch assembles a batch
+ * from a resident pool of parsed blocks.  rows [T,8] fp32: all blocks back to back, a row = xyz, rgb, label, inner (what
+ * parse_fn builds); offsets [P+1] int64; block_ids [B] int32 (device): the blocks of this batch in batch order.  Per cloud b
+ * with n rows: n >= num_point -> num_point DISTINCT rows in random order (a keyed bijection, cycle-walked), else num_point rows
+ * with replacement.  augment = 1: clouds [0, B/3) are turned about z by a uniform angle and then by the small random rotation,
+ * clouds [B/3, 2(B/3)) get clipped normal noise on xyz; colours, labels and the rest pass through.  Every draw is a pure
+ * function of (seed, step, b, slot, purpose): no generator state, the same batch on any rank (csrc/feed.hip states the draws).
+ * -> points [B,num_point,6] fp32, label / inner [B,num_point] int32, index [B,num_point] int32 (nullable): the row of its block
+ * each point came from.  A block id outside [0, P) or an offset pair outside [0, T] reads nothing: zeros and index -1. */
+int sph3d_feed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                        const int* block_ids, unsigned long long seed, unsigned long long step, int augment, float* points,
+                        int* label, int* inner, int* index, sph3d_stream_t stream);
+
 /* the segmentation nets' training loss (models/SPH3D_s3dis.py:116-133: per block the mean over the points with inner_label > 0
  * of the sparse softmax cross-entropy, summed over the batch by the caller) and its gradient in one launch:
  *   loss_part[b * S + s], S = sph3d_masked_softmax_xent_parts(N): the shares of S slices of block b's points in

@@ -1,0 +1,171 @@
+// feed.hip — a training batch assembled on the device from a resident pool of parsed S3DIS blocks: the per-step work of the
+// reference's input loop (train_s3dis.py:114-142,343-347; host statement: harness/blockio.py sample_points / augment_batch) in ONE
+// launch, one thread per output point.  The draws are counter-based — pure functions of (seed, step, cloud, slot, purpose) — and
+// harness/feed.py:assemble_reference states them in numpy; the integer outputs equal that statement bit for bit.
+//
+//   cloud key   ck = mix(mix(mix(seed + G) + step + G) + b + G)           mix = the splitmix64 finaliser, G = 0x9e3779b97f4a7c15
+//   a draw      w(purpose, counter) = mix(ck ^ (purpose << 56 | counter))    64 bits; "bits" = its high word
+//   n >= N      slot j takes pi(j): a 6-round balanced Feistel network over 2 * ceil(k / 2) bits (2^k >= n > 2^(k-1)), walked
+//               until it lands below n (a bijection of the domain, so the walk returns to [0, n): 2^(2 ceil(k/2)) < 4 n,
+//               fewer than 4 steps expected).  N distinct rows in an exchangeable order, no sort, no cross-thread traffic.
+//   n <  N      slot j takes mulhi(bits, n)
+//   augment     third = B / 3: clouds [0, third) are turned by Rz(theta) * (Rz Ry Rx)(three clipped normal angles), clouds
+//               [third, 2 third) get clipped normal noise per coordinate.  Uniforms are (bits >> 8) * 2^-24, normals Box-Muller
+//               in fp32 with u1 = ((hi >> 8) + 1) * 2^-24 (never 0) and u2 from the low word of the same draw.
+// Traffic: two 16-byte loads of a random 32-byte row and 36 bytes of stores per point — bound by the launch and the row reads.
+#include "common.hpp"
+
+namespace sph3d {
+
+constexpr unsigned long long kFeedGold = 0x9e3779b97f4a7c15ull;
+constexpr int kFeedRounds = 6;
+enum : unsigned long long { kFeedPerm = 1, kFeedRepl = 2, kFeedTurn = 3, kFeedTilt = 4, kFeedJitter = 5 };
+
+__host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long long z)
+{
+    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27; z *= 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ unsigned long long feed_cloud_key(unsigned long long seed, unsigned long long step, unsigned b)
+{
+    return feed_mix(feed_mix(feed_mix(seed + kFeedGold) + step + kFeedGold) + b + kFeedGold);
+}
+__device__ __forceinline__ unsigned long long feed_draw(unsigned long long ck, unsigned long long purpose, unsigned counter)
+{
+    return feed_mix(ck ^ (purpose << 56 | counter));
+}
+__device__ __forceinline__ unsigned feed_fmix32(unsigned x)
+{
+    x ^= x >> 16; x *= 0x85ebca6bu;
+    x ^= x >> 13; x *= 0xc2b2ae35u;
+    return x ^ (x >> 16);
+}
+__device__ __forceinline__ float feed_uniform(unsigned bits) { return (float)(bits >> 8) * 0x1p-24f; }
+
+// two independent N(0,1) from one 64-bit draw
+__device__ __forceinline__ void feed_normal_pair(unsigned long long w, float& z0, float& z1)
+{
+    const float u1 = (float)(((unsigned)(w >> 32) >> 8) + 1u) * 0x1p-24f;
+    const float u2 = feed_uniform((unsigned)w);
+    const float r = sqrtf(-2.0f * logf(u1));
+    float s, c;
+    sincosf(6.283185307179586f * u2, &s, &c);
+    z0 = r * c;
+    z1 = r * s;
+}
+__device__ __forceinline__ float feed_clip(float v, float lim) { return fminf(fmaxf(v, -lim), lim); }
+
+__global__ __launch_bounds__(256) void feed_assemble_kernel(int B, int N, int P, long long T, const float* __restrict__ rows,
+                                                            const long long* __restrict__ offsets, const int* __restrict__ block_ids,
+                                                            unsigned long long seed, unsigned long long step, int augment,
+                                                            float* __restrict__ points, int* __restrict__ label,
+                                                            int* __restrict__ inner, int* __restrict__ index)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * N) return;
+    const int b = (int)(i / N);
+    const unsigned slot = (unsigned)(i - (long long)b * N);
+    float2* out = reinterpret_cast<float2*>(points + i * 6);
+
+    // the cloud's rows; a block id or an offset pair that does not describe rows of the pool reads nothing (index -1, zeros)
+    const int id = block_ids[b];
+    long long lo = 0, n64 = 0;
+    if (id >= 0 && id < P) {
+        lo = offsets[id];
+        n64 = offsets[id + 1] - lo;
+    }
+    if (n64 <= 0 || n64 > 0x7fffffffll || lo < 0 || lo + n64 > T) {
+        out[0] = out[1] = out[2] = make_float2(0.f, 0.f);
+        label[i] = 0;
+        inner[i] = 0;
+        if (index != nullptr) index[i] = -1;
+        return;
+    }
+    const unsigned n = (unsigned)n64;
+    const unsigned long long ck = feed_cloud_key(seed, step, (unsigned)b);
+
+    unsigned r;
+    if (n >= (unsigned)N) {
+        const int k = n > 1 ? 32 - __builtin_clz(n - 1) : 0;        // 2^k >= n > 2^(k-1)
+        const int half = (k + 1) >> 1;
+        const unsigned mask = (1u << half) - 1u;                       // (half <= 16)
+        unsigned rk[kFeedRounds];
+#pragma unroll
+        for (int t = 0; t < kFeedRounds; ++t) rk[t] = (unsigned)(feed_draw(ck, kFeedPerm, (unsigned)t) >> 32);
+        r = slot;
+        do {
+            unsigned L = r >> half, R = r & mask;
+#pragma unroll
+            for (int t = 0; t < kFeedRounds; ++t) {
+                const unsigned f = feed_fmix32(R ^ rk[t]) & mask;
+                const unsigned nl = R;
+                R = L ^ f;
+                L = nl;
+            }
+            r = (L << half) | R;
+        } while (r >= n);
+    } else {
+        r = __umulhi((unsigned)(feed_draw(ck, kFeedRepl, slot) >> 32), n);
+    }
+
+    const float4* src = reinterpret_cast<const float4*>(rows + (lo + (long long)r) * 8);
+    const float4 a = src[0], c = src[1];            // x y z r | g b label inner
+    float x = a.x, y = a.y, z = a.z;
+    const int third = B / 3;
+    if (augment && b < third) {
+        // xyz . Rz(theta) . (Rz(az) Ry(ay) Rx(ax)), row vector times matrix (utils/data_util.py:47-61,140-163); the nine
+        // numbers are the same for every point of the cloud: each thread recomputes them (4 sincos)
+        const float th = 6.283185307179586f * feed_uniform((unsigned)(feed_draw(ck, kFeedTurn, 0u) >> 32));
+        float ax, ay, az, unused;
+        feed_normal_pair(feed_draw(ck, kFeedTilt, 0u), ax, ay);
+        feed_normal_pair(feed_draw(ck, kFeedTilt, 1u), az, unused);
+        ax = feed_clip(0.06f * ax, 0.18f); ay = feed_clip(0.06f * ay, 0.18f); az = feed_clip(0.06f * az, 0.18f);
+        float st, ct, sx, cx, sy, cy, sz, cz;
+        sincosf(th, &st, &ct); sincosf(ax, &sx, &cx); sincosf(ay, &sy, &cy); sincosf(az, &sz, &cz);
+        const float x1 = x * ct + y * st, y1 = y * ct - x * st;        // . Rz(theta) = [[c,-s,0],[s,c,0],[0,0,1]]
+        // M = Rz Ry Rx
+        const float m00 = cz * cy, m01 = cz * sy * sx - sz * cx, m02 = cz * sy * cx + sz * sx;
+        const float m10 = sz * cy, m11 = sz * sy * sx + cz * cx, m12 = sz * sy * cx - cz * sx;
+        const float m20 = -sy, m21 = cy * sx, m22 = cy * cx;
+        x = x1 * m00 + y1 * m10 + a.z * m20;
+        y = x1 * m01 + y1 * m11 + a.z * m21;
+        z = x1 * m02 + y1 * m12 + a.z * m22;
+    } else if (augment && b < 2 * third) {
+        float j0, j1, j2, unused;
+        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot), j0, j1);
+        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot + 1u), j2, unused);
+        x += feed_clip(0.01f * j0, 0.02f);
+        y += feed_clip(0.01f * j1, 0.02f);
+        z += feed_clip(0.01f * j2, 0.02f);
+    }
+    out[0] = make_float2(x, y);
+    out[1] = make_float2(z, a.w);
+    out[2] = make_float2(c.x, c.y);
+    label[i] = (int)c.z;
+    inner[i] = (int)c.w;
+    if (index != nullptr) index[i] = (int)r;
+}
+
+}  // namespace sph3d
+
+using namespace sph3d;
+
+extern "C" int sph3d_feed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows,
+                                   const long long* offsets, const int* block_ids, unsigned long long seed, unsigned long long step,
+                                   int augment, float* points, int* label, int* inner, int* index, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B > 0, "feed_assemble: batch B>0 required, got %d", B);
+    SPH3D_REQUIRE(num_point > 0, "feed_assemble: num_point>0 required, got %d", num_point);
+    SPH3D_REQUIRE(num_blocks > 0 && total_rows > 0, "feed_assemble: empty pool (num_blocks=%d total_rows=%lld)", num_blocks, total_rows);
+    SPH3D_REQUIRE(augment == 0 || augment == 1, "feed_assemble: augment must be 0 or 1, got %d", augment);
+    SPH3D_REQUIRE(rows != nullptr && offsets != nullptr && block_ids != nullptr, "feed_assemble: null input pointer");
+    SPH3D_REQUIRE(points != nullptr && label != nullptr && inner != nullptr, "feed_assemble: null output pointer");
+    SPH3D_REQUIRE((reinterpret_cast<size_t>(rows) & 15) == 0 && (reinterpret_cast<size_t>(points) & 7) == 0,
+                  "feed_assemble: rows must be 16-byte and points 8-byte aligned");
+    const long long total = (long long)B * num_point;
+    SPH3D_REQUIRE(total <= 0x7fffffffll, "feed_assemble: B*num_point=%lld too large", total);
+    hipLaunchKernelGGL(feed_assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), B, num_point,
+                       num_blocks, total_rows, rows, offsets, block_ids, seed, step, augment, points, label, inner, index);
+    return check_launch("sph3d_feed_assemble");
+}

@@ -12,8 +12,11 @@ sampling / augmentation of its training loop — without TensorFlow.
   * ``augment_batch``: shuffle the blocks and the point order, rotate about z + small random rotation on the first third
     of the batch, jitter the second third (:124-141, utils/data_util.py:47-61,140-176).
 
-There is no S3DIS data in this environment; bench.py keeps its synthetic generator (harness/synth.py) and these
-functions are exercised by round-trip / known-answer tests (tests/test_blockio.py).
+This module is the host path and the statement of what the reference does, draw for draw (tests/test_blockio.py: round-trip and
+known-answer tests against the reference's recorded results).  The per-step half — sampling and augmentation — also exists on
+the device: harness/feed.py keeps the parsed blocks in HBM (BlockPool.from_records reads them through read_records /
+parse_block, once) and assembles a batch with one kernel on a side stream (csrc/feed.hip; its own counter-based draws, the
+same arithmetic).  Record decoding and the CRC stay here.  bench.py keeps its synthetic generator (harness/synth.py).
 """
 import struct
 

@@ -1,0 +1,394 @@
+"""Training batches assembled on the device: the per-step half of the input side (blockio.sample_points / augment_batch) as one
+kernel over a pool of parsed blocks that lives in HBM (csrc/feed.hip, include/sph3d.h: sph3d_feed_assemble).
+
+  * ``assemble_reference``: the SPECIFICATION of the draws, in numpy, no GPU.  Every draw is a pure function of
+    (seed, step, cloud, slot, purpose), so a batch is reproduced from two integers on any rank.  The kernel's integer outputs
+    (index, label, inner) and everything it copies equal this statement bit for bit; what it computes in fp32 (angles, noise,
+    rotated / jittered xyz) is held to the project's 1e-5 bound against the float64 evaluation given here;
+  * ``BlockPool``: the parsed blocks [n, 8] of a dataset back to back on the device, uploaded once;
+  * ``DeviceFeed``: one epoch of batches, assembled on the feed's own stream into two alternating output sets, each item with
+    the event a GraphPlan takes as ``points_ready``;
+  * ``assemble``: the C entry for callers who bring their own block ids.
+
+What differs from the reference's loop, on purpose: its two shuffles (the blocks of a batch, the point order) are not separate
+steps — the block ids arrive in random order and the sample is in random order already — and the random numbers are this
+module's counter-based ones, not numpy's Mersenne twister.  The arithmetic (rotation about z, then Rz Ry Rx of three clipped
+normal angles, on the first third; clipped normal noise on the second third; third = B // 3) is the reference's, checked against
+its recorded results (tests/test_feed.py, tests/golden/blockio_ref.npz).
+"""
+import collections
+
+import numpy as np
+
+_U64 = np.uint64
+_GOLD = _U64(0x9e3779b97f4a7c15)
+ROUNDS = 6
+PERM, REPL, TURN, TILT, JITTER = 1, 2, 3, 4, 5          # the `purpose` of a draw
+
+ANGLE_SIGMA, ANGLE_CLIP = 0.06, 0.18                    # utils/data_util.py:140
+JITTER_SIGMA, JITTER_CLIP = 0.01, 0.02                  # utils/data_util.py:166
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the draws (csrc/feed.hip computes the same integers)
+# ---------------------------------------------------------------------------------------------------------------
+def _mix(z):
+    """the splitmix64 finaliser on uint64 arrays (arithmetic modulo 2^64)"""
+    z = np.asarray(z, dtype=_U64)
+    z = (z ^ (z >> _U64(30))) * _U64(0xbf58476d1ce4e5b9)
+    z = (z ^ (z >> _U64(27))) * _U64(0x94d049bb133111eb)
+    return z ^ (z >> _U64(31))
+
+
+def cloud_key(seed, step, b):
+    with np.errstate(over="ignore"):
+        k = _mix(_U64(seed & 0xffffffffffffffff) + _GOLD)
+        k = _mix(k + _U64(step & 0xffffffffffffffff) + _GOLD)
+        return _mix(k + np.asarray(b, dtype=_U64) + _GOLD)
+
+
+def draw(ck, purpose, counter):
+    """-> uint64 words w(purpose, counter) of the cloud with key ck; `counter` < 2^32 may be an array"""
+    with np.errstate(over="ignore"):
+        return _mix(_U64(ck) ^ (_U64(purpose << 56) | np.asarray(counter, dtype=_U64)))
+
+
+def _hi(w):
+    return (w >> _U64(32)).astype(np.uint32)
+
+
+def _fmix32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x85ebca6b)
+    x = x ^ (x >> np.uint32(13))
+    x = x * np.uint32(0xc2b2ae35)
+    return x ^ (x >> np.uint32(16))
+
+
+def feistel_bits(n):
+    """half the width of the permutation's domain: 2^k >= n > 2^(k-1), half = ceil(k / 2); the domain 2^(2 half) is < 4 n"""
+    k = int(n - 1).bit_length()
+    return (k + 1) >> 1
+
+
+def sample_without_replacement(ck, n, num_point):
+    """slot j -> pi(j), cycle-walked into [0, n): num_point distinct rows of n >= num_point, in an exchangeable order"""
+    half = feistel_bits(n)
+    mask = np.uint32((1 << half) - 1)
+    sh = np.uint32(half)
+    rk = _hi(draw(ck, PERM, np.arange(ROUNDS)))
+    r = np.arange(num_point, dtype=np.uint32)
+    todo = np.arange(num_point)
+    with np.errstate(over="ignore"):
+        while todo.size:
+            v = r[todo]
+            L, R = v >> sh, v & mask
+            for t in range(ROUNDS):
+                L, R = R, L ^ (_fmix32(R ^ rk[t]) & mask)
+            v = (L << sh) | R
+            r[todo] = v
+            todo = todo[v >= np.uint32(n)]
+    return r.astype(np.int32)
+
+
+def sample_with_replacement(ck, n, num_point):
+    """slot j -> floor(u n), u from 32 random bits (multiply-high)"""
+    bits = _hi(draw(ck, REPL, np.arange(num_point))).astype(_U64)
+    return ((bits * _U64(n)) >> _U64(32)).astype(np.int32)
+
+
+def uniform(bits32):
+    """(bits >> 8) * 2^-24 in [0, 1) — exact in fp32 and in float64"""
+    return (np.asarray(bits32, dtype=np.uint32) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def normal_pair(w):
+    """Box-Muller on one 64-bit draw: u1 = ((hi >> 8) + 1) 2^-24 in (0, 1], u2 from the low word -> two N(0,1), float64 (the
+    kernel evaluates the same expression in fp32)"""
+    w = np.asarray(w, dtype=_U64)
+    u1 = ((_hi(w) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u2 = uniform((w & _U64(0xffffffff)).astype(np.uint32))
+    r = np.sqrt(-2.0 * np.log(u1))
+    return r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)
+
+
+def turn_angle(ck):
+    return 2.0 * np.pi * float(uniform(_hi(draw(ck, TURN, 0))))
+
+
+def tilt_angles(ck):
+    ax, ay = normal_pair(draw(ck, TILT, 0))
+    az, _ = normal_pair(draw(ck, TILT, 1))
+    return np.clip(ANGLE_SIGMA * np.array([ax, ay, az], dtype=np.float64), -ANGLE_CLIP, ANGLE_CLIP)
+
+
+def jitter_noise(ck, num_point):
+    j = np.arange(num_point, dtype=np.int64)
+    z0, z1 = normal_pair(draw(ck, JITTER, 2 * j))
+    z2, _ = normal_pair(draw(ck, JITTER, 2 * j + 1))
+    return np.clip(JITTER_SIGMA * np.stack([z0, z1, z2], axis=1), -JITTER_CLIP, JITTER_CLIP)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the transform, in float64 (row vectors times matrices, as utils/data_util.py:47-61,140-176 write it)
+# ---------------------------------------------------------------------------------------------------------------
+def turn_matrix(theta):
+    c, s = np.cos(theta), np.sin(theta)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def tilt_matrix(ax, ay, az):
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+    return np.dot(rz, np.dot(ry, rx))
+
+
+def turn(xyz, theta):
+    return np.dot(np.asarray(xyz, dtype=np.float64), turn_matrix(theta))
+
+
+def tilt(xyz, angles):
+    return np.dot(np.asarray(xyz, dtype=np.float64), tilt_matrix(*angles))
+
+
+def jitter(xyz, noise):
+    return np.asarray(xyz, dtype=np.float64) + noise
+
+
+Reference = collections.namedtuple("Reference", "index kind theta tilt noise")
+
+
+def assemble_reference(sizes, block_ids, num_point, seed, step, augment):
+    """The draws of one batch.  sizes: rows per block of the pool; block_ids [B]: the blocks of the batch in batch order.
+    -> Reference(index [B, N] int32 — the row of its block each output point takes;
+                 kind [B] — 1 rotated, 2 jittered, 0 passed through;
+                 theta [B], tilt [B, 3] — float64 angles of the rotated clouds (0 elsewhere);
+                 noise [B, N, 3] — float64 noise of the jittered clouds (0 elsewhere))
+    A pure function of its arguments."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    block_ids = np.asarray(block_ids, dtype=np.int64).reshape(-1)
+    B, N = block_ids.shape[0], int(num_point)
+    if B <= 0 or N <= 0:
+        raise ValueError("assemble_reference: B>0 and num_point>0 required")
+    if block_ids.min() < 0 or block_ids.max() >= sizes.shape[0]:
+        raise ValueError("block id outside the pool")
+    index = np.zeros((B, N), dtype=np.int32)
+    kind = np.zeros((B,), dtype=np.int32)
+    theta = np.zeros((B,), dtype=np.float64)
+    tilts = np.zeros((B, 3), dtype=np.float64)
+    noise = np.zeros((B, N, 3), dtype=np.float64)
+    third = B // 3
+    for b in range(B):
+        n = int(sizes[block_ids[b]])
+        if n <= 0:
+            raise ValueError("empty block")
+        if n >= 1 << 31:
+            raise ValueError("block with 2^31 rows or more")
+        ck = cloud_key(seed, step, b)
+        index[b] = sample_without_replacement(ck, n, N) if n >= N else sample_with_replacement(ck, n, N)
+        if augment and b < third:
+            kind[b], theta[b], tilts[b] = 1, turn_angle(ck), tilt_angles(ck)
+        elif augment and b < 2 * third:
+            kind[b], noise[b] = 2, jitter_noise(ck, N)
+    return Reference(index, kind, theta, tilts, noise)
+
+
+def apply_reference(blocks, block_ids, ref):
+    """the batch `ref` describes, from host blocks [n, 8]: -> points [B, N, 6] float64, label, inner [B, N] int32"""
+    B, N = ref.index.shape
+    points = np.zeros((B, N, 6), dtype=np.float64)
+    label = np.zeros((B, N), dtype=np.int32)
+    inner = np.zeros((B, N), dtype=np.int32)
+    for b in range(B):
+        rows = np.asarray(blocks[int(block_ids[b])])[ref.index[b]]
+        xyz = rows[:, 0:3].astype(np.float64)
+        if ref.kind[b] == 1:
+            xyz = tilt(turn(xyz, ref.theta[b]), ref.tilt[b])
+        elif ref.kind[b] == 2:
+            xyz = jitter(xyz, ref.noise[b])
+        points[b, :, 0:3], points[b, :, 3:6] = xyz, rows[:, 3:6]
+        label[b], inner[b] = rows[:, 6].astype(np.int32), rows[:, 7].astype(np.int32)
+    return points, label, inner
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the epoch plan (host, no device)
+# ---------------------------------------------------------------------------------------------------------------
+def batches_per_epoch(num_blocks, batch_size):
+    return (num_blocks + batch_size - 1) // batch_size
+
+
+def epoch_order(num_blocks, seed, epoch):
+    """the epoch's block order: one permutation from (seed, epoch), the same on every rank"""
+    key = np.array([seed & 0xffffffff, (seed >> 32) & 0xffffffff, epoch & 0xffffffff], dtype=np.uint32)
+    return np.random.RandomState(key).permutation(num_blocks).astype(np.int32)
+
+
+def epoch_plan(num_blocks, batch_size, seed, epoch, rank=0, world=1):
+    """-> [(step, block_ids int32 [b])] of rank `rank`: the epoch's order cut into batches of batch_size (the last one may be
+    smaller, like blockio.training_batches'), of which rank r takes r, r + world, ...; `step` is the batch's number counted
+    over all ranks and epochs — the `step` of its draws, so a batch does not depend on how many ranks share the epoch"""
+    if num_blocks <= 0 or batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+        raise ValueError("epoch_plan: bad num_blocks / batch_size / rank / world")
+    order = epoch_order(num_blocks, seed, epoch)
+    per = batches_per_epoch(num_blocks, batch_size)
+    return [(epoch * per + i, order[i * batch_size:(i + 1) * batch_size]) for i in range(rank, per, world)]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the device side
+# ---------------------------------------------------------------------------------------------------------------
+def assemble(rows, offsets, block_ids, num_point, seed, step, augment=True, out=None, want_index=False):
+    """sph3d_feed_assemble on torch's current stream.  rows [T, 8] fp32, offsets [P+1] int64, block_ids [B] int32, all on the
+    device.  out: (points [B, N, 6] fp32, label [B, N] i32, inner [B, N] i32) to write into, else new tensors.
+    -> points, label, inner (and index [B, N] i32 with want_index)"""
+    import torch
+    from .. import _lib
+    _lib.require_device(rows, offsets, block_ids)
+    if rows.dtype != torch.float32 or offsets.dtype != torch.int64 or block_ids.dtype != torch.int32:
+        raise TypeError("assemble: rows fp32, offsets int64, block_ids int32")
+    if rows.dim() != 2 or rows.shape[1] != 8 or not (rows.is_contiguous() and offsets.is_contiguous() and block_ids.is_contiguous()):
+        raise ValueError("assemble: rows must be a contiguous [T, 8], offsets and block_ids contiguous")
+    B, N = int(block_ids.shape[0]), int(num_point)
+    if out is None:
+        out = (torch.empty((B, N, 6), dtype=torch.float32, device=rows.device),
+               torch.empty((B, N), dtype=torch.int32, device=rows.device),
+               torch.empty((B, N), dtype=torch.int32, device=rows.device))
+    points, label, inner = out
+    for t, shape, dt in ((points, (B, N, 6), torch.float32), (label, (B, N), torch.int32), (inner, (B, N), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != rows.device:
+            raise ValueError("assemble: output of the wrong shape, type, layout or device")
+    index = torch.empty((B, N), dtype=torch.int32, device=rows.device) if want_index else None
+    _lib.check(_lib.lib().sph3d_feed_assemble(B, N, int(offsets.shape[0]) - 1, int(rows.shape[0]), _lib.ptr(rows), _lib.ptr(offsets),
+                                              _lib.ptr(block_ids), seed & 0xffffffffffffffff, step & 0xffffffffffffffff,
+                                              1 if augment else 0, _lib.ptr(points), _lib.ptr(label), _lib.ptr(inner),
+                                              _lib.ptr(index), _lib.stream_ptr()))
+    return (points, label, inner, index) if want_index else (points, label, inner)
+
+
+class BlockPool:
+    """The parsed blocks of a dataset, resident on the device: rows [T, 8] fp32 (blockio.parse_block's layout) back to back and
+    offsets [P+1] int64, uploaded once; `sizes` stays on the host."""
+
+    def __init__(self, blocks, device=None):
+        import torch
+        blocks = [np.ascontiguousarray(b, dtype=np.float32) for b in blocks]
+        if not blocks:
+            raise ValueError("empty pool")
+        for b in blocks:
+            if b.ndim != 2 or b.shape[1] != 8:
+                raise ValueError("a block is [n, 8]: xyz, rgb, label, inner")
+            if b.shape[0] == 0:
+                raise ValueError("empty block")
+        self.sizes = np.array([b.shape[0] for b in blocks], dtype=np.int64)
+        self.host_offsets = np.concatenate(([0], np.cumsum(self.sizes))).astype(np.int64)
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.rows = torch.from_numpy(np.concatenate(blocks, axis=0)).to(self.device)
+        self.offsets = torch.from_numpy(self.host_offsets).to(self.device)
+
+    @classmethod
+    def from_blocks(cls, blocks, device=None):
+        return cls(blocks, device)
+
+    @classmethod
+    def from_records(cls, paths, device=None, verify=True):
+        from . import blockio
+        return cls([blockio.parse_block(r) for p in paths for r in blockio.read_records(p, verify=verify)], device)
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+
+class DeviceFeed:
+    """One epoch of training batches per iteration, assembled on the device.
+
+        feed = DeviceFeed(pool, 16, 8192, seed=1)
+        for points, label, inner, ready in feed:                 # epoch 0; the next `for` is epoch 1
+            pred, _ = model(points, is_training=True, points_ready=ready)
+            loss = model.loss(pred, label, inner)
+            feed.done(ready)                                     # the batch's last reader is issued (see below)
+            ...                                                  # backward, optimiser
+
+    The epoch's block order is one host permutation from (seed, epoch), identical on every rank; rank r takes batches
+    r, r + world, ...; the last batch may be smaller.  The kernel runs on the feed's own stream (`stream`, else one the feed
+    creates); `ready` is recorded behind it: hand it to the model as `points_ready`, or `wait_event` it on the consuming stream
+    (label and inner are consumed by the loss on the main stream: it must wait too — the model's plan does that for the
+    streams it uses when it gets `points_ready`, see s3dis_net.GraphPlan).
+
+    OWNERSHIP.  The tensors of an item are views of one of TWO preallocated output sets used alternately (no per-step
+    allocation crosses streams), so item i is overwritten by item i+2: the consumer must have ISSUED all its work on item i
+    before it asks for item i+2, and must not keep the tensors (clone what has to outlive the next step).  Before the feed
+    overwrites a set it waits, on its stream, for the event handed back with `done(ready[, event])` for that set — or, when
+    none was handed back, for everything issued so far on the stream that is current when the next item is asked for.  The
+    second form is safe and slow: item i+2 is then assembled behind ALL of step i+1, so the plan of step i+2 no longer overlaps
+    the step before it (+20 % per step); hand the event back, as early as the last reader of the batch."""
+
+    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None):
+        import torch
+        if batch_size <= 0 or num_point <= 0:
+            raise ValueError("DeviceFeed: batch_size>0 and num_point>0 required")
+        if world <= 0 or not 0 <= rank < world:
+            raise ValueError("DeviceFeed: bad rank / world")
+        self.pool, self.batch_size, self.num_point, self.seed = pool, int(batch_size), int(num_point), int(seed)
+        self.augment, self.rank, self.world = bool(augment), int(rank), int(world)
+        self.epoch = 0
+        dev = pool.device
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
+        self._sets = []
+        for _ in range(2):
+            self._sets.append({
+                "out": (torch.empty((self.batch_size, self.num_point, 6), dtype=torch.float32, device=dev),
+                        torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev),
+                        torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev)),
+                "ready": torch.cuda.Event(), "released": None, "used": False})
+        self._turn = 0
+
+    def __len__(self):
+        """batches of this rank per epoch"""
+        return len(range(self.rank, batches_per_epoch(len(self.pool), self.batch_size), self.world))
+
+    def done(self, ready, event=None):
+        """the consumer is finished with the item whose event is `ready`: after `event` (default: one recorded now on the current
+        stream) its set may be overwritten"""
+        import torch
+        for s in self._sets:
+            if s["ready"] is ready:
+                if event is None:
+                    event = torch.cuda.Event()
+                    event.record()
+                s["released"] = event
+                return
+        raise ValueError("done(): not the ready event of a live item")
+
+    def _assemble(self, step, ids_dev, b):
+        import torch
+        s = self._sets[self._turn]
+        self._turn ^= 1
+        if s["used"]:
+            if s["released"] is not None:
+                self.stream.wait_event(s["released"])
+            else:
+                self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))
+        s["released"], s["used"] = None, True
+        out = tuple(t[:b] for t in s["out"])
+        with torch.cuda.stream(self.stream):
+            assemble(self.pool.rows, self.pool.offsets, ids_dev, self.num_point, self.seed, step, self.augment, out=out)
+            s["ready"].record(self.stream)
+        return out + (s["ready"],)
+
+    def __iter__(self):
+        import torch
+        plan = epoch_plan(len(self.pool), self.batch_size, self.seed, self.epoch, self.rank, self.world)
+        self.epoch += 1
+        if not plan:
+            return
+        # the block ids of the whole epoch go up in one copy (a row per batch, the last one padded): no host copy per step
+        table = np.zeros((len(plan), self.batch_size), dtype=np.int32)
+        for i, (_step, ids) in enumerate(plan):
+            table[i, :len(ids)] = ids
+        self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))      # (the pool's upload, a previous epoch's table)
+        with torch.cuda.stream(self.stream):
+            table_dev = torch.from_numpy(table).to(self.pool.device)
+        for i, (step, ids) in enumerate(plan):
+            yield self._assemble(step, table_dev[i, :len(ids)], len(ids))
