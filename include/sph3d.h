@@ -478,6 +478,38 @@ int sph3d_feed_assemble(int B, int num_point, int num_blocks, long long total_ro
                         const int* block_ids, unsigned long long seed, unsigned long long step, int augment, float* points,
                         int* label, int* inner, int* index, sph3d_stream_t stream);
 
+/* ---- overlap-voting evaluation of the segmentation nets on the device (s3dis_seg/evaluate_s3dis_with_overlap.py:253-286 the
+ * per-pass sample counts and coverage, :301-302 the vote, :314-325 arg-max and the per-class counts; the ScanNet script,
+ * evaluate_scannet_withoverlap.py:280, differs in the coverage threshold).  A batch is B blocks of the pool sph3d_feed_assemble
+ * reads (rows [T,8], offsets [P+1], block_ids [B], all on the device) whose rows lie inside the pool rows
+ * [row_base, row_base + batch_rows); votes [batch_rows, C] fp32, count / pred [batch_rows] int32 and the workspace's stamps are
+ * indexed by (pool row - row_base); covered / inner_size [B] int32; remaining [1] int32.  The block ids of a batch are distinct.
+ * A block id outside [0, P), or a block that is not inside that range, takes no part: it votes nothing and its inner_size is 0.
+ * Every buffer is the caller's (the workspace holds sph3d_vote_workspace(batch_rows) bytes, 8-byte aligned, and belongs to the
+ * batch from begin to the last accumulate); nothing is allocated, no floating-point atomic is used, and every output is a pure
+ * function of the inputs (harness/evalvote.py:vote_reference states it in numpy, bit for bit, the fp32 sums included).
+ *   begin       zeroes votes, count, covered and the stamps; inner_size[b] = rows of block b with inner == 1;
+ *               remaining = blocks with inner_size > 0.
+ *   accumulate  one pass: index [B,num_point] (what sph3d_feed_assemble returned; -1 or a row outside its block votes nothing),
+ *               logits [B,num_point,C] fp32.  numpy's `sum[index] += logits` keeps the LAST of several slots that drew the same
+ *               row; so does this: per pass a drawn row gets one logits vector added to its sums and one count.  An inner row
+ *               whose count reaches min_votes adds one to covered[b]; remaining = blocks with covered < inner_size.
+ *               pass = 0, 1, ... must increase from call to call within a batch (it orders the stamps), pass < 2^20.
+ *   finalize    pred[row] = first maximum of the row's C sums (a NaN counts as a maximum, as np.argmax); for inner rows with a
+ *               label in [0, C): confusion[label * C + pred] += 1 (int64, accumulated, not zeroed here); *nonfinite += rows of
+ *               the batch's blocks whose sums are not all finite.  C <= 64. */
+size_t sph3d_vote_workspace(long long batch_rows);
+int sph3d_vote_begin(int B, int C, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                     const int* block_ids, long long row_base, long long batch_rows, float* votes, int* count, int* covered,
+                     int* inner_size, int* remaining, void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+int sph3d_vote_accumulate(int B, int num_point, int C, int num_blocks, long long total_rows, const float* rows,
+                          const long long* offsets, const int* block_ids, long long row_base, long long batch_rows, int pass,
+                          const int* index, const float* logits, int min_votes, float* votes, int* count, int* covered,
+                          const int* inner_size, int* remaining, void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+int sph3d_vote_finalize(int B, int C, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                        const int* block_ids, long long row_base, long long batch_rows, const float* votes, int* pred,
+                        long long* confusion, long long* nonfinite, sph3d_stream_t stream);
+
 /* the segmentation nets' training loss (models/SPH3D_s3dis.py:116-133: per block the mean over the points with inner_label > 0
  * of the sparse softmax cross-entropy, summed over the batch by the caller) and its gradient in one launch:
  *   loss_part[b * S + s], S = sph3d_masked_softmax_xent_parts(N): the shares of S slices of block b's points in
