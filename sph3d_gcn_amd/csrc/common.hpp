@@ -50,6 +50,24 @@ static inline int check_hip(hipError_t e, const char* what)
 
 static inline hipStream_t as_stream(sph3d_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Launch of a kernel whose dynamic LDS may exceed what a kernel gets without asking: above kOptIn bytes (64 KB; the separable
+// convolutions ask from 48 KB, as they always have) the kernel's limit is raised first, on every such launch: nothing is cached.
+// -> SPH3D_OK once the launch is queued; the caller still ends its launches with check_launch().  `who` heads the error message.
+template <size_t kOptIn = 64 * 1024, class... Params, class... Args>
+static inline int launch_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const char* who,
+                             Args... args)
+{
+    if (lds > kOptIn) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+            return SPH3D_ELAUNCH;
+        }
+    }
+    kern<<<grid, block, lds, stream>>>(args...);
+    return SPH3D_OK;
+}
+
 // The library reads no environment except the test hooks listed in sph3d.h; they reach code that ordinary inputs rarely do.
 // -> the variable's value as atoi() reads it, `unset` if it is not set.  Each caller decides when it reads (per call or once).
 static inline int test_hook(const char* name, int unset)
@@ -87,6 +105,32 @@ static inline TgWs tg_ws(void* workspace, int B, int N, int M, int K, int F)
     w.slot_pos = w.deg + w.zero_words;
     w.total_words = w.zero_words + (size_t)B * M * K;
     return w;
+}
+
+// ---- the transposed graph itself inside a caller's workspace (the one-call gradients of conv3d.hip and pool3d.hip): the arrays
+// sph3d_graph_transpose writes, each on a 256-byte boundary, then the build's scratch (tg_ws above).  workspace == nullptr:
+// null pointers, `bytes` is what the size functions report.
+struct TgLayout {
+    int* offsets; int* key; float* scale; int* active; void* scratch; size_t scratch_bytes; size_t bytes;
+};
+static inline TgLayout tg_layout(void* workspace, int B, int N, int M, int K, int F)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = workspace ? (char*)workspace + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    TgLayout t;
+    t.offsets = (int*)take(sizeof(int) * (size_t)B * ((size_t)N * F + 1));
+    t.key = (int*)take(sizeof(int) * (size_t)B * M * K);
+    t.scale = (float*)take(sizeof(float) * (size_t)B * M * K);
+    t.active = (int*)take(sizeof(int) * ((size_t)F + 1));
+    const size_t scratch_off = off;
+    t.scratch = take(sph3d_graph_transpose_workspace(B, N, M, K, F));
+    t.scratch_bytes = off - scratch_off;
+    t.bytes = off;
+    return t;
 }
 
 // ---- packed entries of the transposed graph (round 6) ----------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 //     (N*C*4 B, 4 MiB at N=8192,C=128) stay in that XCD's 4 MiB L2.
 //   * Numerics: sum_k in*filt in fp32 FMA order k = 0..cnt-1, one division by cnt at the end (the
 //     reference divides every term); agreement with the oracle is ~1e-7 relative, bound 1e-5.
+#include <type_traits>
 #include "common.hpp"
 
 namespace sph3d {
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(256) void dwconv_fwd_row(
     int B, int N, int M, int F, int C, int K, int mblocks, int nslices,
     const int* __restrict__ nnIndex, const int* __restrict__ nnCount, const int* __restrict__ binIndex,
     const float* __restrict__ input, const float* __restrict__ filter, float* __restrict__ output,
-    const int* __restrict__ order, const float* __restrict__ input2 = nullptr, int Ca = 0)
+    const float* __restrict__ input2 = nullptr, int Ca = 0)
 {
     extern __shared__ __attribute__((aligned(16))) float lfilt[];   // [F][SL]
     const int CR = C * R;
@@ -204,7 +205,6 @@ __global__ __launch_bounds__(256) void dwconv_fwd_row(
     const int cin0 = (slice0 + cl0) / R;      // first input channel of this lane
     const int clc = act ? cl0 : 0;            // clamped copies for branch-free loads
     const int cinc = act ? cin0 : slice0 / R;
-    (void)cin0;
     const int m_begin = mb * kFwdPointsPerWG;
     const int m_end = (m_begin + kFwdPointsPerWG) < M ? (m_begin + kFwdPointsPerWG) : M;
     // input2 != nullptr: the input is the channel concatenation [input (Ca channels) | input2 (C - Ca)] of two tensors that were
@@ -216,10 +216,9 @@ __global__ __launch_bounds__(256) void dwconv_fwd_row(
     const int cshift = second ? Ca : 0;
     const float* inb = (second ? input2 : input) + (size_t)b * N * Cs - cshift;
 
-    for (int mi = m_begin + wave; mi < m_end; mi += 4) {
-        // optional processing order: measured in round 1 (Morton order of the output points): no gain, the rows
-        // come from L2 either way (profiles/); kept as a hook for the LDS-tiled variant
-        const int m = order ? uniform(order[(size_t)b * M + mi]) : mi;
+    // (measured in round 1 and dropped: visiting the output points in Morton order: no gain, the rows come from L2 either way,
+    // profiles/)
+    for (int m = m_begin + wave; m < m_end; m += 4) {
         const size_t row = (size_t)b * M + m;
         const int cnt = uniform(nnCount[row]);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -823,6 +822,20 @@ static int conv_dims_ok(int B, int N, int M, int F, int C, int r, int K, const c
 
 using namespace sph3d;
 
+// dwconv_fwd_row over 256-output slices; input2 / Ca: the second tensor of a channel concatenation (sph3d_depthwise_conv3d_cat)
+static int launch_fwd_row(int B, int N, int M, int F, int C, int r, int K, const int* nn_index, const int* nn_count,
+                          const int* bin_index, const float* input, const float* filter, float* output, const float* input2, int Ca,
+                          hipStream_t st)
+{
+    const int CR = C * r;
+    const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
+    const int nslices = (CR + kSlice - 1) / kSlice;
+    const int SLmax = CR < kSlice ? CR : kSlice;
+    const size_t lds = (size_t)(F + 1) * SLmax * sizeof(float);      // + the zero row of the padding slots
+    return launch_lds(r == 2 ? dwconv_fwd_row<2> : dwconv_fwd_row<1>, dim3(xcd_grid(B, mblocks * nslices)), dim3(256), lds, st, "conv3d",
+                      B, N, M, F, C, K, mblocks, nslices, nn_index, nn_count, bin_index, input, filter, output, input2, Ca);
+}
+
 extern "C" int sph3d_depthwise_conv3d(int B, int N, int M, int F, int C, int r, int K,
                                       const int* nn_index, const int* nn_count, const int* bin_index,
                                       const float* input, const float* filter, float* output,
@@ -831,107 +844,37 @@ extern "C" int sph3d_depthwise_conv3d(int B, int N, int M, int F, int C, int r, 
     int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3d");
     if (rc) return rc;
     if (B == 0 || M == 0) return SPH3D_OK;
-    const int CR = C * r;
-    const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
     hipStream_t st = as_stream(stream);
     const bool vec = (C % 4 == 0) && (r == 1 || r == 2);
-#define SPH3D_BIG_LDS(kern)                                                                                       \
-    if (lds > 64 * 1024) {                                                                                        \
-        rc = check_hip(hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), \
-                       "conv3d: hipFuncSetAttribute");                                                            \
-        if (rc) return rc;                                                                                        \
-    }
-    const int mmblocks = (M + kMultiPoints - 1) / kMultiPoints;
-    const dim3 mgrid(xcd_grid(B, mmblocks));
     const bool multi_ok = vec && N <= (1 << 24) && F <= 254 && (unsigned long long)N * C * 4ull + 1024ull < (1ull << 32);
-    if (multi_ok && C > 64 && C <= 128) {
+    if (multi_ok && C <= 128) {
         // 65..128 channels: 32 lanes per edge, TWO neighbour rows per wave load.  (Round 1 had measured this shape slower than one
         // row per load, 0.353 vs 0.297 ms at C = 128; with the zero-row padding and vector-side offsets of round 2 it is
         // 0.202 vs 0.240 ms = 16.6 % of the roofline, ahead of the LDS-tiled kernel and without a plan.  64 lanes per edge for
         // C >= 256 — one pass over the edges instead of one per 128-channel slice, but 70 KB of filter table per workgroup —
         // stays behind the row kernel: 0.069 vs 0.060 ms at 2048 x 256.)
-        const int nslices = 1;
-        const size_t lds = (size_t)(F + 1) * 128 * r * sizeof(float);    // + the zero row of the padding slots; rows of 128 * r
-        const dim3 grid(xcd_grid(B, mblocks * nslices));
-        if (r == 2) {
-            SPH3D_BIG_LDS((dwconv_fwd_multi<2, 32, kFwdSB>))
-            hipLaunchKernelGGL((dwconv_fwd_multi<2, 32, kFwdSB>), mgrid, dim3(64 * kMultiWaves), lds, st, B, N, M, F, C, K, mmblocks,
-                               nslices, nn_index, nn_count, bin_index, input, filter, output);
-        } else {
-            SPH3D_BIG_LDS((dwconv_fwd_multi<1, 32, kFwdSB>))
-            hipLaunchKernelGGL((dwconv_fwd_multi<1, 32, kFwdSB>), mgrid, dim3(64 * kMultiWaves), lds, st, B, N, M, F, C, K, mmblocks,
-                               nslices, nn_index, nn_count, bin_index, input, filter, output);
-        }
-    } else
-    if (multi_ok && C <= 64) {
-        // narrow layers: 16 lanes per edge, four neighbour rows per wave load (measured at C = 64, r = 2: 0.254 -> 0.145 ms;
-        // at C >= 128 the one-edge-per-load kernel below is faster: 0.297 vs 0.353 ms with two edges per load)
-        const int nslices = 1;
-        const size_t lds = (size_t)(F + 1) * 64 * r * sizeof(float);     // + the zero row of the padding slots; rows of 64 * r
-        const dim3 grid(xcd_grid(B, mblocks * nslices));
-        if (r == 2) {
-            SPH3D_BIG_LDS((dwconv_fwd_multi<2, 16, kFwdSB>))
-            hipLaunchKernelGGL((dwconv_fwd_multi<2, 16, kFwdSB>), mgrid, dim3(64 * kMultiWaves), lds, st, B, N, M, F, C, K, mmblocks,
-                               nslices, nn_index, nn_count, bin_index, input, filter, output);
-        } else {
-            SPH3D_BIG_LDS((dwconv_fwd_multi<1, 16, kFwdSB>))
-            hipLaunchKernelGGL((dwconv_fwd_multi<1, 16, kFwdSB>), mgrid, dim3(64 * kMultiWaves), lds, st, B, N, M, F, C, K, mmblocks,
-                               nslices, nn_index, nn_count, bin_index, input, filter, output);
-        }
+        // narrow layers (C <= 64): 16 lanes per edge, four neighbour rows per wave load (measured at C = 64, r = 2:
+        // 0.254 -> 0.145 ms; at C >= 128 the one-edge-per-load kernel below is faster: 0.297 vs 0.353 ms with two edges per load)
+        const bool wide = C > 64;
+        auto kern = wide ? (r == 2 ? dwconv_fwd_multi<2, 32, kFwdSB> : dwconv_fwd_multi<1, 32, kFwdSB>)
+                         : (r == 2 ? dwconv_fwd_multi<2, 16, kFwdSB> : dwconv_fwd_multi<1, 16, kFwdSB>);
+        const int mmblocks = (M + kMultiPoints - 1) / kMultiPoints;
+        const size_t lds = (size_t)(F + 1) * (wide ? 128 : 64) * r * sizeof(float);   // + the zero row of the padding slots; rows of 128 * r or 64 * r
+        rc = launch_lds(kern, dim3(xcd_grid(B, mmblocks)), dim3(64 * kMultiWaves), lds, st, "conv3d", B, N, M, F, C, K, mmblocks,
+                        /*nslices=*/1, nn_index, nn_count, bin_index, input, filter, output);
     } else if (vec && (unsigned long long)N * C + 256ull < (1ull << 32)) {       // (32-bit row offsets in the kernel)
-        const int nslices = (CR + kSlice - 1) / kSlice;
-        const int SLmax = CR < kSlice ? CR : kSlice;
-        const size_t lds = (size_t)(F + 1) * SLmax * sizeof(float);      // + the zero row of the padding slots
-        const dim3 grid(xcd_grid(B, mblocks * nslices));
-        if (r == 2) {
-            SPH3D_BIG_LDS(dwconv_fwd_row<2>)
-            hipLaunchKernelGGL(dwconv_fwd_row<2>, grid, dim3(256), lds, st, B, N, M, F, C, K, mblocks, nslices,
-                               nn_index, nn_count, bin_index, input, filter, output, nullptr);
-        } else {
-            SPH3D_BIG_LDS(dwconv_fwd_row<1>)
-            hipLaunchKernelGGL(dwconv_fwd_row<1>, grid, dim3(256), lds, st, B, N, M, F, C, K, mblocks, nslices,
-                               nn_index, nn_count, bin_index, input, filter, output, nullptr);
-        }
+        rc = launch_fwd_row(B, N, M, F, C, r, K, nn_index, nn_count, bin_index, input, filter, output, nullptr, 0, st);
     } else {
+        const int CR = C * r;
+        const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
         const int nslices = (CR + kSlice - 1) / kSlice;
         const int SLmax = CR < kSlice ? CR : kSlice;
         const size_t lds = (size_t)F * SLmax * sizeof(float);
-        const dim3 grid(xcd_grid(B, mblocks * nslices));
-        SPH3D_BIG_LDS(dwconv_fwd_generic)
-        hipLaunchKernelGGL(dwconv_fwd_generic, grid, dim3(256), lds, st, B, N, M, F, C, r, K, mblocks, nslices,
-                           nn_index, nn_count, bin_index, input, filter, output);
+        rc = launch_lds(dwconv_fwd_generic, dim3(xcd_grid(B, mblocks * nslices)), dim3(256), lds, st, "conv3d", B, N, M, F, C, r, K,
+                        mblocks, nslices, nn_index, nn_count, bin_index, input, filter, output);
     }
+    if (rc) return rc;
     return check_launch("sph3d_depthwise_conv3d");
-}
-
-// layout of the transposed graph inside a caller-provided workspace
-struct TGraphWs {
-    int* offsets; int* key; float* scale; int* active; void* scratch; size_t scratch_bytes;
-};
-static size_t tgraph_ws_bytes(int B, int N, int M, int K, int F)
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al(sizeof(int) * (size_t)B * ((size_t)N * F + 1)) + 2 * al(sizeof(int) * (size_t)B * M * K) +
-           al(sizeof(int) * ((size_t)F + 1)) + al(sph3d_graph_transpose_workspace(B, N, M, K, F));
-}
-static TGraphWs tgraph_carve(void* ws, int B, int N, int M, int K, int F)
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    char* p = (char*)ws;
-    TGraphWs t;
-    t.offsets = (int*)p; p += al(sizeof(int) * (size_t)B * ((size_t)N * F + 1));
-    t.key = (int*)p; p += al(sizeof(int) * (size_t)B * M * K);
-    t.scale = (float*)p; p += al(sizeof(int) * (size_t)B * M * K);
-    t.active = (int*)p; p += al(sizeof(int) * ((size_t)F + 1));
-    t.scratch = p; t.scratch_bytes = al(sph3d_graph_transpose_workspace(B, N, M, K, F));
-    return t;
-}
-
-extern "C" size_t sph3d_scatter_grad_workspace(int B, int N, int M, int K) { return tgraph_ws_bytes(B, N, M, K, 1); }
-extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r);
-extern "C" size_t sph3d_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K)
-{
-    return tgraph_ws_bytes(B, N, M, K, F) + sph3d_depthwise_conv3d_grad_t_workspace(B, N, F, C, r);
 }
 
 static int vec_plan(int F, int CR, int r, int& V)
@@ -949,14 +892,19 @@ static int vec_plan(int F, int CR, int r, int& V)
 //     dependent gathers per source, so the sources are spread over enough workgroups to put two on every CU
 //     (down to 2 sources per wave) instead of leaving most CUs idle.
 constexpr int kBwdFillWG = 128;   // workgroups per XCD that a small level is spread over (compact kernel: 4 fit a CU)
-static void bwd_plan(int B, int N, int nslices, int wg_per_cu, int& parts, int& W)
+struct BwdTable {
+    int parts, W;      // position ranges per cloud; workgroups per XCD and channel slice
+    int slabs;         // 8 * W partial tables, one per workgroup of a slice; the hub launch's kHubWG slabs follow them
+};
+static BwdTable bwd_plan(int B, int N, int nslices, int wg_per_cu)
 {
+    BwdTable t;
     int g = B & 7;                         // gcd(B, 8)
     g = g == 0 ? 8 : (g & -g);
-    parts = 8 / g;
-    if (parts > N) parts = 1;
-    const long long items_per_xcd = ((long long)B * parts + 7) / 8;
-    const long long src = items_per_xcd * ((N + parts - 1) / parts);
+    t.parts = 8 / g;
+    if (t.parts > N) t.parts = 1;
+    const long long items_per_xcd = ((long long)B * t.parts + 7) / 8;
+    const long long src = items_per_xcd * ((N + t.parts - 1) / t.parts);
     const long long w_work = (src + kBwdTPointsPerWG - 1) / kBwdTPointsPerWG;
     long long w_fill = (wg_per_cu >= 4 ? kBwdFillWG : 64) / (nslices < 1 ? 1 : nslices);
     if (w_fill < 1) w_fill = 1;
@@ -964,14 +912,9 @@ static void bwd_plan(int B, int N, int nslices, int wg_per_cu, int& parts, int& 
     long long w = w_fill < w_min ? w_fill : w_min;
     if (w < w_work) w = w_work;
     const long long cap = 32LL * wg_per_cu;
-    W = (int)(w < 1 ? 1 : (w > cap ? cap : w));
-}
-
-static int bwd_slices(int F, int CR, int r)
-{
-    int V = 0;
-    if (!vec_plan(F, CR, r, V)) return 0;
-    return (CR + 64 * V - 1) / (64 * V);
+    t.W = (int)(w < 1 ? 1 : (w > cap ? cap : w));
+    t.slabs = 8 * t.W;
+    return t;
 }
 
 // hub sources (dwconv_bwd_t_vec<..., HUB>): clouds of at least 32 768 points (measured: at 16 384 the two extra launches cost more
@@ -982,97 +925,120 @@ static_assert(kHubWG % kHubGroup == 0, "hub workgroups come in groups of kHubGro
 static int hub_min_n() { return test_hook("SPH3D_BWD_HUB_MIN_N", 32768); }
 static int hub_threshold() { const int t = test_hook("SPH3D_BWD_HUB_T", 1024); return t < 1 ? 1 : t; }
 
-extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r)
+// The vector gradient's launch plan and workspace: the slabs of F x CR partial filter gradients, then the hub list.  A call
+// runs the full table's launches, the compact table's, or both (the device chooses, see the kernel); both write slabs 0 ..,
+// so the slab area holds the larger of the two plans and the hub launch's kHubWG slabs behind either.  Nothing here depends
+// on the per-call switches: a workspace sized once serves every call of the shape.
+struct BwdLayout {
+    int V;                     // channels per lane (vec_plan); 0: the shape takes the generic kernel, no workspace
+    int nslices;               // channel slices of 64 * V outputs
+    BwdTable full, compact;    // 3 and 4 workgroups per CU
+    size_t hub_list_offset;    // bytes from the workspace's start to the hub list [count, b * N + n ...]
+    size_t bytes;
+};
+static BwdLayout bwd_layout(int B, int N, int F, int C, int r)
 {
-    int V = 0;
-    if (!vec_plan(F, C * r, r, V)) return 0;
-    int parts, W;
-    bwd_plan(B, N, bwd_slices(F, C * r, r), 4, parts, W);      // sized for the compact variant (4 workgroups per CU)
-    // + the hub launch's slabs and the hub list (always: the size must not depend on the per-call switches)
-    return sizeof(float) * ((size_t)8 * W + kHubWG) * F * C * r + sizeof(int) * ((size_t)B * N + 4);
+    BwdLayout L = {};
+    if (!vec_plan(F, C * r, r, L.V)) return L;
+    L.nslices = (C * r + 64 * L.V - 1) / (64 * L.V);
+    L.full = bwd_plan(B, N, L.nslices, 3);
+    L.compact = bwd_plan(B, N, L.nslices, 4);
+    const size_t slabs = (size_t)(L.full.slabs > L.compact.slabs ? L.full.slabs : L.compact.slabs) + kHubWG;
+    L.hub_list_offset = sizeof(float) * slabs * F * C * r;
+    L.bytes = L.hub_list_offset + sizeof(int) * ((size_t)B * N + 4);
+    return L;
+}
+
+extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r) { return bwd_layout(B, N, F, C, r).bytes; }
+extern "C" size_t sph3d_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K)
+{
+    return tg_layout(nullptr, B, N, M, K, F).bytes + bwd_layout(B, N, F, C, r).bytes;
 }
 
 constexpr int kCompactBins = 17;     // accumulator rows of the compact variant
 
 template <int R, int V, int MAXF, int PARTS>
-static int launch_bwd_t_vec(int B, int N, int M, int F, int C, const int* offsets, const int* ent_key,
+static int launch_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int C, const int* offsets, const int* ent_key,
                             const float* ent_scale, const int* order, const int* active_bins, const float* input,
                             const float* filter, const float* grad_output, float* grad_input, float* grad_filter,
-                            float* partial, hipStream_t st, const float* input2 = nullptr, float* grad_input2 = nullptr, int Ca = 0)
+                            void* workspace, hipStream_t st, const float* input2, float* grad_input2, int Ca)
 {
     const int CR = C * R;
-    const int SLW = 64 * V;
-    const int nslices = (CR + SLW - 1) / SLW;
-    int parts, W, Wc = 0;
-    bwd_plan(B, N, nslices, 3, parts, W);
-    const int SLmax = CR < SLW ? CR : SLW;
+    const int SLmax = CR < 64 * V ? CR : 64 * V;
     const size_t lds = (size_t)F * SLmax * sizeof(float);
+    const int total = F * CR;
+    float* partial = (float*)workspace;
     // the compact launch exists for the 4-channels-per-lane plans with at most 63 bins (one register of segment bounds)
     const bool compact = active_bins != nullptr && V == 4 && MAXF > kCompactBins && F <= 63;
-    auto kern = dwconv_bwd_t_vec<R, V, MAXF, PARTS, false>;
-    auto kernc = dwconv_bwd_t_vec<R, V, (V == 4 ? kCompactBins : MAXF), PARTS, (V == 4)>;
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "conv3d: hipFuncSetAttribute");
-        if (rc) return rc;
-        rc = check_hip(hipFuncSetAttribute((const void*)kernc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                       "conv3d: hipFuncSetAttribute");
-        if (rc) return rc;
-    }
     const int* ab = compact ? active_bins : nullptr;
-    const int total = F * CR;
-    if constexpr (V == 4) {
-        if (N >= hub_min_n()) {
-            // big clouds: hub sources are left out of the sweep and shared among the waves of the hub launch (see the kernel)
-            int pc = parts;
-            if (compact) bwd_plan(B, N, nslices, 4, pc, Wc);
-            const int wmax = W > Wc ? W : Wc;
-            int* hub_list = reinterpret_cast<int*>(partial + ((size_t)8 * wmax + kHubWG) * total);
-            int rc = check_hip(hipMemsetAsync(hub_list, 0, sizeof(int), st), "conv3d grad: hub list");
-            if (rc) return rc;
-            const int T = hub_threshold();
-            auto kern1 = dwconv_bwd_t_vec<R, V, MAXF, PARTS, false, 1>;
-            auto kern2 = dwconv_bwd_t_vec<R, V, MAXF, PARTS, false, 2>;
-            auto kernc1 = dwconv_bwd_t_vec<R, V, kCompactBins, PARTS, true, 1>;
-            auto kernc2 = dwconv_bwd_t_vec<R, V, kCompactBins, PARTS, true, 2>;
-            if (lds > 64 * 1024) {
-                for (const void* k : {(const void*)kern1, (const void*)kern2, (const void*)kernc1, (const void*)kernc2}) {
-                    rc = check_hip(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "conv3d: hipFuncSetAttribute");
-                    if (rc) return rc;
-                }
+    // big clouds: hub sources are left out of the sweep and shared among the waves of the hub launch (see the kernel)
+    const bool hubs = V == 4 && N >= hub_min_n();
+    int* hub_list = nullptr;
+    int T = 0;
+    if (hubs) {
+        hub_list = reinterpret_cast<int*>((char*)workspace + L.hub_list_offset);
+        int rc = check_hip(hipMemsetAsync(hub_list, 0, sizeof(int), st), "conv3d grad: hub list");
+        if (rc) return rc;
+        T = hub_threshold();
+    }
+    // one launch: `wgs` workgroups per slice, W of them per XCD (the hub launch: W = wgs in all)
+    auto launch = [&](auto kern, int wgs, int W, int parts, int slab_base) {
+        return launch_lds(kern, dim3(wgs * L.nslices), dim3(kBwdTWaves * 64), lds, st, "conv3d", B, N, M, F, C, W, parts, L.nslices,
+                          offsets, ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial,
+                          input2, grad_input2, Ca, hub_list, T, slab_base);
+    };
+    // one table's sweep over all sources and, when hubs apply, the hub launch behind it (HUB = 1, 2 exist for V == 4 only)
+    auto sweep = [&](auto compact_table, const BwdTable& t) {
+        constexpr bool CT = decltype(compact_table)::value;
+        constexpr int MF = CT ? kCompactBins : MAXF;
+        if constexpr (V == 4) {
+            if (hubs) {
+                int rc = launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 1>, t.slabs, t.W, t.parts, 0);
+                if (rc) return rc;
+                return launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 2>, kHubWG, kHubWG, 1, t.slabs);
             }
-            if (compact) {
-                hipLaunchKernelGGL(kernc1, dim3(8 * Wc * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, Wc, pc, nslices, offsets, ent_key,
-                                   ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
-                                   hub_list, T, 0);
-                hipLaunchKernelGGL(kernc2, dim3(kHubWG * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, kHubWG, 1, nslices, offsets,
-                                   ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2,
-                                   grad_input2, Ca, hub_list, T, 8 * Wc);
-            }
-            hipLaunchKernelGGL(kern1, dim3(8 * W * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, W, parts, nslices, offsets, ent_key,
-                               ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
-                               hub_list, T, 0);
-            hipLaunchKernelGGL(kern2, dim3(kHubWG * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C, kHubWG, 1, nslices, offsets, ent_key,
-                               ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial, input2, grad_input2, Ca,
-                               hub_list, T, 8 * W);
-            hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, 8 * W + kHubWG, total, CR, partial,
-                               grad_filter, ab, kCompactBins, 8 * Wc + kHubWG);
-            return check_launch("sph3d_depthwise_conv3d_grad_t");
         }
+        return launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 0>, t.slabs, t.W, t.parts, 0);
+    };
+    int rc = SPH3D_OK;
+    if constexpr (V == 4) {
+        if (compact) rc = sweep(std::true_type{}, L.compact);
     }
-    if (compact) {
-        int pc;
-        bwd_plan(B, N, nslices, 4, pc, Wc);
-        hipLaunchKernelGGL(kernc, dim3(8 * Wc * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C,
-                           Wc, pc, nslices, offsets, ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output,
-                           grad_input, partial, input2, grad_input2, Ca, (int*)nullptr, 0, 0);
-    }
-    hipLaunchKernelGGL(kern, dim3(8 * W * nslices), dim3(kBwdTWaves * 64), lds, st, B, N, M, F, C,
-                       W, parts, nslices, offsets, ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output,
-                       grad_input, partial, input2, grad_input2, Ca, (int*)nullptr, 0, 0);
-    hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, 8 * W, total, CR, partial,
-                       grad_filter, ab, kCompactBins, 8 * Wc);
+    if (rc == SPH3D_OK) rc = sweep(std::false_type{}, L.full);
+    if (rc) return rc;
+    const int hub_slabs = hubs ? kHubWG : 0;
+    hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, L.full.slabs + hub_slabs, total, CR, partial,
+                       grad_filter, ab, kCompactBins, (compact ? L.compact.slabs : 0) + hub_slabs);
     return check_launch("sph3d_depthwise_conv3d_grad_t");
+}
+
+// the vector gradient of one or (input2: sph3d_depthwise_conv3d_grad_t_cat) two inputs: workspace check, then the instantiation
+// for the depth multiplier, the channels per lane and the row width
+static int run_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int C, int r, const int* offsets, const int* ent_key,
+                         const float* ent_scale, const int* order, const int* active_bins, const float* input, const float* filter,
+                         const float* grad_output, float* grad_input, float* grad_filter, void* workspace, size_t workspace_bytes,
+                         hipStream_t st, const float* input2 = nullptr, float* grad_input2 = nullptr, int Ca = 0)
+{
+    if (workspace == nullptr || workspace_bytes < L.bytes) {
+        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, L.bytes);
+        return SPH3D_EWORKSPACE;
+    }
+    auto go = [&](auto R, auto V, auto PARTS) {
+        return launch_bwd_t_vec<R(), V(), (V() == 4 ? 33 : 65), PARTS()>(L, B, N, M, F, C, offsets, ent_key, ent_scale, order, active_bins,
+                                                                       input, filter, grad_output, grad_input, grad_filter,
+                                                                       workspace, st, input2, grad_input2, Ca);
+    };
+    using std::integral_constant;
+    auto with_r = [&](auto R) {
+        const int CR = C * r;
+        if (L.V == 2) return go(R, integral_constant<int, 2>{}, integral_constant<int, 1>{});
+        // rows of at most 128 (64) outputs: two half (four quarter) waves take alternate edges; a narrower row leaves lanes of
+        // each part idle, but fewer than the full-wave form would (the ModelNet plan's 36-, 64- and 68-channel layers)
+        if (CR <= 64) return go(R, integral_constant<int, 4>{}, integral_constant<int, 4>{});
+        if (CR <= 128) return go(R, integral_constant<int, 4>{}, integral_constant<int, 2>{});
+        return go(R, integral_constant<int, 4>{}, integral_constant<int, 1>{});
+    };
+    return r == 2 ? with_r(integral_constant<int, 2>{}) : with_r(integral_constant<int, 1>{});
 }
 
 extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, int r,
@@ -1087,34 +1053,11 @@ extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, 
     hipStream_t st = as_stream(stream);
     const int CR = C * r;
     if (B == 0) return check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
-    int V = 0;
+    const BwdLayout L = bwd_layout(B, N, F, C, r);
     // (the vector kernels address a cloud's grad_out rows with 32-bit element offsets)
-    if (vec_plan(F, CR, r, V) && (unsigned long long)M * CR + 256ull < (1ull << 32)) {
-        const size_t need = sph3d_depthwise_conv3d_grad_t_workspace(B, N, F, C, r);
-        if (workspace == nullptr || workspace_bytes < need) {
-            set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, need);
-            return SPH3D_EWORKSPACE;
-        }
-        float* partial = (float*)workspace;
-#define SPH3D_GO(RR, VV, MF) \
-    return launch_bwd_t_vec<RR, VV, MF, 1>(B, N, M, F, C, offsets, ent_key, ent_scale, source_order, active_bins, input, \
-                                        filter, grad_output, grad_input, grad_filter, partial, st)
-        // rows of at most 128 (64) outputs: two half (four quarter) waves take alternate edges; a narrower row leaves lanes of
-        // each part idle, but fewer than the full-wave form would (the ModelNet plan's 36-, 64- and 68-channel layers)
-#define SPH3D_GO_PARTS(RR, PP) \
-    return launch_bwd_t_vec<RR, 4, 33, PP>(B, N, M, F, C, offsets, ent_key, ent_scale, source_order, active_bins, input, \
-                                           filter, grad_output, grad_input, grad_filter, partial, st)
-        if (V == 4 && CR <= 64 && r == 2) SPH3D_GO_PARTS(2, 4);
-        if (V == 4 && CR <= 64 && r == 1) SPH3D_GO_PARTS(1, 4);
-        if (V == 4 && CR <= 128 && r == 2) SPH3D_GO_PARTS(2, 2);
-        if (V == 4 && CR <= 128 && r == 1) SPH3D_GO_PARTS(1, 2);
-#undef SPH3D_GO_PARTS
-        if (V == 4 && r == 2) SPH3D_GO(2, 4, 33);
-        if (V == 4 && r == 1) SPH3D_GO(1, 4, 33);
-        if (V == 2 && r == 2) SPH3D_GO(2, 2, 65);
-        SPH3D_GO(1, 2, 65);
-#undef SPH3D_GO
-    }
+    if (L.V && (unsigned long long)M * CR + 256ull < (1ull << 32))
+        return run_bwd_t_vec(L, B, N, M, F, C, r, offsets, ent_key, ent_scale, source_order, active_bins, input, filter, grad_output,
+                             grad_input, grad_filter, workspace, workspace_bytes, st);
     // generic path (odd channel counts, other multipliers, F > 64): LDS float atomics, slow but general
     rc = check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
     if (rc) return rc;
@@ -1125,14 +1068,9 @@ extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, 
     const int nslices = (C + sliceC - 1) / sliceC;
     const int nblocks = (N + 63) / 64;
     const size_t lds = (size_t)F * sliceC * r * sizeof(float);
-    if (lds > 64 * 1024) {
-        rc = check_hip(hipFuncSetAttribute((const void*)dwconv_bwd_t_generic, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds), "conv3d: hipFuncSetAttribute");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(dwconv_bwd_t_generic, dim3(xcd_grid(B, nblocks * nslices)), dim3(256), lds, st, B, N, M, F, C, r,
-                       nblocks, nslices, sliceC, offsets, ent_key, ent_scale, input, filter, grad_output, grad_input,
-                       grad_filter);
+    rc = launch_lds(dwconv_bwd_t_generic, dim3(xcd_grid(B, nblocks * nslices)), dim3(256), lds, st, "conv3d", B, N, M, F, C, r,
+                    nblocks, nslices, sliceC, offsets, ent_key, ent_scale, input, filter, grad_output, grad_input, grad_filter);
+    if (rc) return rc;
     return check_launch("sph3d_depthwise_conv3d_grad_t");
 }
 
@@ -1144,20 +1082,19 @@ extern "C" int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, in
 {
     int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3dGrad");
     if (rc) return rc;
-    const size_t tg = tgraph_ws_bytes(B, N, M, K, F);
-    const size_t need = tg + sph3d_depthwise_conv3d_grad_t_workspace(B, N, F, C, r);
+    const TgLayout t = tg_layout(workspace, B, N, M, K, F);
+    const size_t need = t.bytes + bwd_layout(B, N, F, C, r).bytes;
     if (B > 0 && (workspace == nullptr || workspace_bytes < need)) {
         set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, need);
         return SPH3D_EWORKSPACE;
     }
     if (B == 0) return sph3d_depthwise_conv3d_grad_t(B, N, M, F, C, r, nullptr, nullptr, nullptr, nullptr, nullptr, input, filter,
                                                      grad_output, grad_input, grad_filter, nullptr, 0, stream);
-    TGraphWs t = tgraph_carve(workspace, B, N, M, K, F);
     rc = sph3d_graph_transpose(B, N, M, K, F, nn_index, nn_count, bin_index, nullptr, t.offsets, t.key, t.scale, t.active,
                                t.scratch, t.scratch_bytes, stream);
     if (rc) return rc;
     return sph3d_depthwise_conv3d_grad_t(B, N, M, F, C, r, t.offsets, t.key, t.scale, nullptr, t.active, input, filter, grad_output,
-                                         grad_input, grad_filter, (char*)workspace + tg, workspace_bytes - tg, stream);
+                                         grad_input, grad_filter, (char*)workspace + t.bytes, workspace_bytes - t.bytes, stream);
 }
 
 
@@ -1186,22 +1123,7 @@ extern "C" int sph3d_depthwise_conv3d_cat(int B, int N, int M, int F, int Ca, in
         return SPH3D_EUNSUPPORTED;
     }
     if (B == 0 || M == 0) return SPH3D_OK;
-    hipStream_t st = as_stream(stream);
-    const int CR = C * r;
-    const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
-    const int nslices = (CR + kSlice - 1) / kSlice;
-    const size_t lds = (size_t)(F + 1) * kSlice * sizeof(float);
-    const dim3 grid(xcd_grid(B, mblocks * nslices));
-    auto launch = [&](auto kern) -> int {
-        if (lds > 64 * 1024) {
-            int e = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "conv3d: hipFuncSetAttribute");
-            if (e) return e;
-        }
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, B, N, M, F, C, K, mblocks, nslices, nn_index, nn_count, bin_index, input_a,
-                           filter, output, nullptr, input_b, Ca);
-        return 0;
-    };
-    rc = r == 2 ? launch(dwconv_fwd_row<2>) : launch(dwconv_fwd_row<1>);
+    rc = launch_fwd_row(B, N, M, F, C, r, K, nn_index, nn_count, bin_index, input_a, filter, output, input_b, Ca, as_stream(stream));
     if (rc) return rc;
     return check_launch("sph3d_depthwise_conv3d_cat");
 }
@@ -1221,15 +1143,7 @@ extern "C" int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int
     }
     hipStream_t st = as_stream(stream);
     if (B == 0) return check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * C * r, st), "conv3d grad: memset");
-    const size_t need = sph3d_depthwise_conv3d_grad_t_workspace(B, N, F, C, r);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
-    float* partial = (float*)workspace;
-    if (r == 2)
-        return launch_bwd_t_vec<2, 4, 33, 1>(B, N, M, F, C, offsets, ent_key, ent_scale, source_order, active_bins, input_a, filter,
-                                                 grad_output, grad_a, grad_filter, partial, st, input_b, grad_b, Ca);
-    return launch_bwd_t_vec<1, 4, 33, 1>(B, N, M, F, C, offsets, ent_key, ent_scale, source_order, active_bins, input_a, filter,
-                                             grad_output, grad_a, grad_filter, partial, st, input_b, grad_b, Ca);
+    // (cat_ok: four channels per lane and more than 128 outputs, so the full-wave form)
+    return run_bwd_t_vec(bwd_layout(B, N, F, C, r), B, N, M, F, C, r, offsets, ent_key, ent_scale, source_order, active_bins, input_a,
+                         filter, grad_output, grad_a, grad_filter, workspace, workspace_bytes, st, input_b, grad_b, Ca);
 }

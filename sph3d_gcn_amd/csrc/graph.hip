@@ -324,13 +324,8 @@ extern "C" int sph3d_spatial_order(int B, int N, const float* xyz, int* order, s
     int bpa = 4;                                   // buckets ~ 4 N, between 2^12 and 2^15
     while (bpa < 5 && (1 << (3 * bpa)) < 4 * N) bpa++;
     const size_t lds = sizeof(int) * ((size_t)1 << (3 * bpa));
-    int rc = SPH3D_OK;
-    if (lds > 64 * 1024) {
-        rc = check_hip(hipFuncSetAttribute((const void*)spatial_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                       "spatial_order: hipFuncSetAttribute");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(spatial_order_kernel, dim3(B), dim3(1024), lds, as_stream(stream), N, bpa, xyz, order);
+    int rc = launch_lds(spatial_order_kernel, dim3(B), dim3(1024), lds, as_stream(stream), "spatial_order", N, bpa, xyz, order);
+    if (rc) return rc;
     return check_launch("sph3d_spatial_order");
 }
 

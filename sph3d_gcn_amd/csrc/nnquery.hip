@@ -441,25 +441,15 @@ static int launch_sphere(int B, int N, int M, int K, float radius, int chunkN,
     const size_t lds = (size_t)3 * ((chunkN + 127) & ~127) * sizeof(float) + (DEFER ? hits_bytes(CPW, K) : 0) + kThrTable * sizeof(float);
     if constexpr (DEFER) {
         if (fuse != nullptr) {
-            auto kernf = nnquery_sphere_kernel<CPW, MULTI, DEFER, true>;
-            if (lds > 64 * 1024) {
-                int rc = check_hip(hipFuncSetAttribute((const void*)kernf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                                   "nnquery: hipFuncSetAttribute");
-                if (rc) return rc;
-            }
-            hipLaunchKernelGGL(kernf, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream,
-                               B, N, M, K, radius, chunkN, groups, fixed, *fuse, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
+            int rc = launch_lds(nnquery_sphere_kernel<CPW, MULTI, DEFER, true>, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream, "nnquery",
+                                B, N, M, K, radius, chunkN, groups, fixed, *fuse, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
+            if (rc) return rc;
             return check_launch("sph3d_build_sphere_graph");
         }
     }
-    auto kern = nnquery_sphere_kernel<CPW, MULTI, DEFER, false>;
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "nnquery: hipFuncSetAttribute");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(kern, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream,
-                       B, N, M, K, radius, chunkN, groups, fixed, GraphFuse{}, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
+    int rc = launch_lds(nnquery_sphere_kernel<CPW, MULTI, DEFER, false>, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream, "nnquery",
+                        B, N, M, K, radius, chunkN, groups, fixed, GraphFuse{}, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
+    if (rc) return rc;
     return check_launch("sph3d_build_sphere_neighbor");
 }
 

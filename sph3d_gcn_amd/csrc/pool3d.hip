@@ -523,6 +523,8 @@ extern "C" int sph3d_scatter_grad_t(int B, int Nin, int Mout, int C, const int* 
                         as_stream(stream));
 }
 
+extern "C" size_t sph3d_scatter_grad_workspace(int B, int N, int M, int K) { return tg_layout(nullptr, B, N, M, K, 1).bytes; }
+
 static int grad_via_transpose(const char* who, int B, int Nin, int Mout, int C, int K, const int* nn_index,
                               const int* nn_count, const float* weight, const float* grad_output, float* grad_input,
                               void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
@@ -530,20 +532,15 @@ static int grad_via_transpose(const char* who, int B, int Nin, int Mout, int C, 
     SPH3D_REQUIRE(B >= 0 && Nin > 0 && Mout >= 0 && C > 0 && K > 0, "%s: bad dims B=%d N=%d M=%d C=%d K=%d", who, B,
                   Nin, Mout, C, K);
     if (B == 0) return SPH3D_OK;
-    const size_t need = sph3d_scatter_grad_workspace(B, Nin, Mout, K);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, need);
+    const TgLayout t = tg_layout(workspace, B, Nin, Mout, K, 1);          // one bin; the list of active bins is not asked for
+    if (workspace == nullptr || workspace_bytes < t.bytes) {
+        set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, t.bytes);
         return SPH3D_EWORKSPACE;
     }
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    char* p = (char*)workspace;
-    int* offsets = (int*)p; p += al(sizeof(int) * (size_t)B * (Nin + 1));
-    int* key = (int*)p; p += al(sizeof(int) * (size_t)B * Mout * K);
-    float* scale = (float*)p; p += al(sizeof(int) * (size_t)B * Mout * K);
-    int rc = sph3d_graph_transpose(B, Nin, Mout, K, 1, nn_index, nn_count, nullptr, weight, offsets, key, scale, nullptr, p,
-                                   al(sph3d_graph_transpose_workspace(B, Nin, Mout, K, 1)), stream);
+    int rc = sph3d_graph_transpose(B, Nin, Mout, K, 1, nn_index, nn_count, nullptr, weight, t.offsets, t.key, t.scale, nullptr,
+                                   t.scratch, t.scratch_bytes, stream);
     if (rc) return rc;
-    return launch_bwd_t(who, B, Nin, Mout, C, offsets, key, scale, grad_output, grad_input, as_stream(stream));
+    return launch_bwd_t(who, B, Nin, Mout, C, t.offsets, t.key, t.scale, grad_output, grad_input, as_stream(stream));
 }
 
 extern "C" int sph3d_avg_pool3d_grad(int B, int N, int M, int C, int K, const int* nn_index, const int* nn_count,

@@ -433,21 +433,10 @@ static int sc_launch_general(int B, int N, int M, int F, int C, int K, int Cout,
     while (rbk > 1 && sc_general_lds(F, C, R, rbk) > 160 * 1024) rbk >>= 1;      // many bins: a lower tile beside the larger filter slice
     const size_t lds = sizeof(float) * ((size_t)(F + 1) * 4 * LPE * R + (size_t)(16 * rbk) * (4 * LPE * R + 4));
     SPH3D_REQUIRE(lds <= 160 * 1024, "SeparableConv3dFused: %zu B of LDS needed", lds);
-#define SPH3D_SCG(RB)                                                                                                        \
-    {                                                                                                                        \
-        auto kern = sepconv_general_kernel<R, LPE, RB>;                                                                      \
-        if (lds > 48 * 1024) {                                                                                               \
-            int rc = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), \
-                               "SeparableConv3dFused: hipFuncSetAttribute");                                                 \
-            if (rc) return rc;                                                                                               \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kern, dim3(256), dim3(1024), lds, st, B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, \
-                           dw_filter, W, bias, scale, shift, output);                                                        \
-    }
-    if (rbk == 4) SPH3D_SCG(4)
-    else if (rbk == 2) SPH3D_SCG(2)
-    else SPH3D_SCG(1)
-#undef SPH3D_SCG
+    auto kern = rbk == 4 ? sepconv_general_kernel<R, LPE, 4> : (rbk == 2 ? sepconv_general_kernel<R, LPE, 2> : sepconv_general_kernel<R, LPE, 1>);
+    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dFused", B, N, M, F, C, K, Cout, act, nn_index,
+                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output);
+    if (rc) return rc;
     return check_launch("sph3d_separable_conv3d_fused (general)");
 }
 
@@ -474,21 +463,10 @@ static int sc_launch(int B, int N, int M, int F, int C, int K, int Cout, int act
     const int KTP = KT <= 4 ? 4 : (KT <= 8 ? 8 : 16);           // the k extent the kernel is instantiated for
     const size_t lds = sizeof(float) * ((size_t)(F + 1) * 4 * LPE * R + 2 * (size_t)kScTile * (KTP * 16 + 4));
     SPH3D_REQUIRE(lds <= 160 * 1024, "SeparableConv3dFused: %zu B of LDS needed", lds);
-#define SPH3D_SC(KTT)                                                                                                        \
-    {                                                                                                                        \
-        auto kern = sepconv_fused_kernel<R, LPE, KTT>;                                                                       \
-        if (lds > 48 * 1024) {                                                                                               \
-            int rc = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), \
-                               "SeparableConv3dFused: hipFuncSetAttribute");                                                 \
-            if (rc) return rc;                                                                                               \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kern, dim3(256), dim3(1024), lds, st, B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, \
-                           dw_filter, W, bias, scale, shift, output);                                                        \
-    }
-    if (KTP == 4) SPH3D_SC(4)
-    else if (KTP == 8) SPH3D_SC(8)
-    else SPH3D_SC(16)
-#undef SPH3D_SC
+    auto kern = KTP == 4 ? sepconv_fused_kernel<R, LPE, 4> : (KTP == 8 ? sepconv_fused_kernel<R, LPE, 8> : sepconv_fused_kernel<R, LPE, 16>);
+    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dFused", B, N, M, F, C, K, Cout, act, nn_index,
+                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output);
+    if (rc) return rc;
     return check_launch("sph3d_separable_conv3d_fused");
 }
 

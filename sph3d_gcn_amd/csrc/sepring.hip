@@ -344,21 +344,10 @@ static int sr_launch(int B, int N, int M, int F, int C, int K, int Cout, int act
     const int NB = sr_ring_depth(F, C, R);
     const size_t lds = sizeof(float) * (sr_filter_floats(F, C, R) + (size_t)NB * kSrRows * (KTP * 16 + 4)) + sizeof(int) * (2 + 2 * NB);
     SPH3D_REQUIRE(NB >= 3 && lds <= 160 * 1024, "SeparableConv3dRing: %zu B of LDS needed", lds);
-#define SPH3D_SR(KTT)                                                                                                        \
-    {                                                                                                                        \
-        auto kern = sepconv_ring_kernel<R, LPE, KTT, TRAIN>;                                                                 \
-        if (lds > 48 * 1024) {                                                                                               \
-            int rc = check_hip(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), \
-                               "SeparableConv3dRing: hipFuncSetAttribute");                                                  \
-            if (rc) return rc;                                                                                               \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kern, dim3(256), dim3(1024), lds, st, B, N, M, F, C, K, Cout, act, NB, nn_index, nn_count, bin_index, \
-                           input, dw_filter, W, bias, scale, shift, output, dw_out, stats);                                  \
-    }
-    if (KTP == 4) SPH3D_SR(4)
-    else if (KTP == 8) SPH3D_SR(8)
-    else SPH3D_SR(16)
-#undef SPH3D_SR
+    auto kern = KTP == 4 ? sepconv_ring_kernel<R, LPE, 4, TRAIN> : (KTP == 8 ? sepconv_ring_kernel<R, LPE, 8, TRAIN> : sepconv_ring_kernel<R, LPE, 16, TRAIN>);
+    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dRing", B, N, M, F, C, K, Cout, act, NB, nn_index,
+                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output, dw_out, stats);
+    if (rc) return rc;
     return check_launch("sph3d_separable_conv3d_ring");
 }
 
