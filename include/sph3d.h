@@ -510,6 +510,44 @@ int sph3d_vote_finalize(int B, int C, int num_blocks, long long total_rows, cons
                         const int* block_ids, long long row_base, long long batch_rows, const float* votes, int* pred,
                         long long* confusion, long long* nonfinite, sph3d_stream_t stream);
 
+/* ---- scene-level evaluation (post-merging/s3dis_merge.m:42-82, scannet_merge.m:28-55; csrc/scene.hip): the blocks' vote sums are
+ * normalised per row, merged into a per-scene array through the records' index_label, and the arg-max is lifted to the
+ * full-resolution cloud through a nearest-neighbour search.  harness/scenemerge.py states every entry in numpy, bit for bit, the
+ * fp32 probabilities included.  Every buffer is the caller's; nothing is allocated and no floating-point atomic is used.
+ *   scene_merge     the batch of sph3d_vote_* (same rows / offsets / block_ids / row_base / batch_rows, votes [batch_rows, C] as
+ *                   the voter left them); index [T] int32: the pool rows' index_label.  Blocks are taken in the order of block_ids
+ *                   (pass them ascending: the statement merges in pool order), one launch each.  Per INNER row: s = sum of v*v
+ *                   (ascending c, separate fp32 multiply and add), r = sqrt(s), u = v / r, e = exp32(u) (include/sph3d_exp32.h),
+ *                   z = sum of e, merged[index[row], c] += e_c / z and hits[index[row]] += 1.  A row with s == 0 or s not finite
+ *                   adds nothing and counts in counters[0] (skipped_rows); then an index outside [0, V) counts in counters[1]
+ *                   (out_of_scene).  merged [V, C] fp32, hits [V] int32 and counters [2] int64 are accumulated, not zeroed.
+ *                   The inner indices of one block must be distinct (harness/feed.py refuses a pool where they are not).
+ *   scene_finalize  pred_voxel[i] = first maximum of merged[i, :], 0 for a row with hits == 0, which counts in *unseen_rows;
+ *                   with voxel_label [V] (nullable, together with confusion): confusion[label * C + pred] += 1 for labels in [0, C).
+ *   nn1             idx[f] = the reference point that minimises the fp32 d2 = (dx*dx + dy*dy) + dz*dz, dx = q.x - r.x; ties go to
+ *                   the lowest index; a d2 that is not finite never wins (so a reference point with a non-finite coordinate is
+ *                   never chosen); -1 for a query with a non-finite coordinate or without any candidate.  ref_xyz [V, 3],
+ *                   query_xyz [F, 3].  mode SPH3D_NN1_GRID: counting sort of the reference into a cell grid and an exact ring walk
+ *                   per query, falling back to brute force on the device for clouds the grid cannot index (fewer than 64 finite
+ *                   points, a non-finite or zero extent); SPH3D_NN1_BRUTE: tiled brute force.  Both give the same idx.
+ *                   The workspace holds sph3d_nn1_workspace(V, F) bytes, 16-byte aligned.
+ *   scene_lift      pred_full[f] = pred_voxel[idx[f]] (-1 where idx is outside [0, V)), mapped through label_map [C] when given
+ *                   (ScanNet's labelid_set); with label_full [F] (nullable, together with confusion):
+ *                   confusion[label * C + unmapped prediction] += 1 for labels in [0, C) and idx >= 0.
+ * C <= 64; V, F < 2^31. */
+#define SPH3D_NN1_GRID 0
+#define SPH3D_NN1_BRUTE 1
+int sph3d_scene_merge(int B, int C, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                      const int* index, const int* block_ids, long long row_base, long long batch_rows, const float* votes,
+                      long long V, float* merged, int* hits, long long* counters, sph3d_stream_t stream);
+int sph3d_scene_finalize(int C, long long V, const float* merged, const int* hits, const int* voxel_label, int* pred_voxel,
+                         long long* unseen_rows, long long* confusion, sph3d_stream_t stream);
+size_t sph3d_nn1_workspace(long long V, long long F);
+int sph3d_nn1(long long V, long long F, const float* ref_xyz, const float* query_xyz, int mode, int* idx, void* workspace,
+              size_t workspace_bytes, sph3d_stream_t stream);
+int sph3d_scene_lift(int C, long long V, long long F, const int* pred_voxel, const int* idx, const int* label_map,
+                     const int* label_full, int* pred_full, long long* confusion, sph3d_stream_t stream);
+
 /* the segmentation nets' training loss (models/SPH3D_s3dis.py:116-133: per block the mean over the points with inner_label > 0
  * of the sparse softmax cross-entropy, summed over the batch by the caller) and its gradient in one launch:
  *   loss_part[b * S + s], S = sph3d_masked_softmax_xent_parts(N): the shares of S slices of block b's points in

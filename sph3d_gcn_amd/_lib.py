@@ -19,7 +19,7 @@ _c_size_t = ctypes.c_size_t
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); one entry per declaration in include/sph3d.h
-_I, _F, _P, _S = _c_int, _c_float, _vp, _c_size_t
+_I, _F, _P, _S, _L = _c_int, _c_float, _vp, _c_size_t, ctypes.c_longlong
 SIGNATURES = {
     "sph3d_abi_version": (_I, []),
     "sph3d_last_error": (ctypes.c_char_p, []),
@@ -84,6 +84,11 @@ SIGNATURES = {
     "sph3d_vote_accumulate": (_I, [_I, _I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _I, _P, _P, _I]
                               + [_P] * 5 + [_P, _S, _P]),
     "sph3d_vote_finalize": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong] + [_P] * 4 + [_P]),
+    "sph3d_scene_merge": (_I, [_I, _I, _I, _L, _P, _P, _P, _P, _L, _L, _P, _L, _P, _P, _P, _P]),
+    "sph3d_scene_finalize": (_I, [_I, _L] + [_P] * 6 + [_P]),
+    "sph3d_nn1_workspace": (_S, [_L, _L]),
+    "sph3d_nn1": (_I, [_L, _L, _P, _P, _I, _P, _P, _S, _P]),
+    "sph3d_scene_lift": (_I, [_I, _L, _L] + [_P] * 6 + [_P]),
     "sph3d_pointwise_gemm_skinny_supported": (_I, [_I] * 4),
     "sph3d_pointwise_gemm_skinny": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_pointwise_gemm_skinny_tn_workspace": (_S, [_I] * 4),

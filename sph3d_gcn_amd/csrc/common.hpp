@@ -159,6 +159,21 @@ __device__ __forceinline__ float uniformf(float v)
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
+// vote.hip, scene.hip — the rows of cloud b of a batch inside the pool and inside the batch's row range: -> n (0: the cloud takes no part), lo = its first pool row
+__device__ __forceinline__ long long vote_cloud(int b, int P, long long T, const long long* __restrict__ offsets,
+                                                const int* __restrict__ block_ids, long long row_base, long long batch_rows,
+                                                long long& lo)
+{
+    const int id = block_ids[b];
+    lo = 0;
+    if (id < 0 || id >= P) return 0;
+    lo = offsets[id];
+    const long long n = offsets[id + 1] - lo;
+    if (n <= 0 || n > 0x7fffffffll || lo < 0 || lo + n > T) return 0;
+    if (lo < row_base || lo + n > row_base + batch_rows) return 0;
+    return n;
+}
+
 // XCD-affine work decode.  Workgroup `bid` runs on XCD (bid % 8) (observed placement, used for
 // L2 locality only, never for correctness).  Clouds are dealt to XCDs round-robin so that all
 // workgroups of one cloud share one L2: returns (cloud, part) for this block or cloud = -1.

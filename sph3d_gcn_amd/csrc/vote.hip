@@ -25,21 +25,6 @@ namespace sph3d {
 constexpr int kVoteMaxClasses = 64;
 constexpr int kVoteFinalizeParts = 64;          // workgroups per cloud in the row-strided kernels
 
-// the rows of cloud b inside the pool and inside the batch's range: -> n (0: the cloud takes no part), lo = its first pool row
-__device__ __forceinline__ long long vote_cloud(int b, int P, long long T, const long long* __restrict__ offsets,
-                                                const int* __restrict__ block_ids, long long row_base, long long batch_rows,
-                                                long long& lo)
-{
-    const int id = block_ids[b];
-    lo = 0;
-    if (id < 0 || id >= P) return 0;
-    lo = offsets[id];
-    const long long n = offsets[id + 1] - lo;
-    if (n <= 0 || n > 0x7fffffffll || lo < 0 || lo + n > T) return 0;
-    if (lo < row_base || lo + n > row_base + batch_rows) return 0;
-    return n;
-}
-
 // inner_size[b] = rows of cloud b with inner == 1 (column 7 of the pool's rows)
 __global__ __launch_bounds__(256) void vote_inner_size_kernel(int P, long long T, const float* __restrict__ rows,
                                                               const long long* __restrict__ offsets, const int* __restrict__ block_ids,

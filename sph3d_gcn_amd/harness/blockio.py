@@ -232,6 +232,20 @@ def parse_block(record):
     return np.concatenate((xyz, rgb, seg, inner), axis=1)
 
 
+def parse_block_index(record):
+    """-> (index int32 [n], scene_idx int): the rows' positions in their scene's voxel cloud (`index_label`) and the scene's
+    number, from the Example parse_block reads (the reference's *_block2scene_index.py dumps the same two)"""
+    ex = decode_example(record)
+    index = np.frombuffer(ex["index_label"], dtype="<i4").astype(np.int32)
+    for name, width in (("xyz_raw", 12), ("rgb_raw", 12), ("seg_label", 4), ("inner_label", 4)):
+        if len(ex[name]) != width * len(index):
+            raise ValueError("block record with inconsistent array lengths")
+    scene = np.asarray(ex["scene_idx"]).reshape(-1)
+    if scene.shape[0] != 1:
+        raise ValueError("block record without a scalar scene_idx")
+    return index, int(scene[0])
+
+
 def sample_points(block, num_point, rng):
     """NUM_POINT rows of one block: without replacement when it has enough points, else with (train_s3dis.py:343-347)
     -> input [num_point, 6], label [num_point] i32, inner [num_point] i32"""

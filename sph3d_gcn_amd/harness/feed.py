@@ -267,11 +267,40 @@ def assemble(rows, offsets, block_ids, num_point, seed, step, augment=True, out=
     return (points, label, inner, index) if want_index else (points, label, inner)
 
 
+def check_scene_index(blocks, index, scene_of_block):
+    """what a pool with a scene index must satisfy (host, no device) -> (index int32 [T], scene_of_block int64 [P]):
+    one index array per block, as long as the block, values >= 0; the blocks of a scene consecutive; and the index values of a
+    block's INNER rows distinct — the reference's `predictions(idx,:) = predictions(idx,:) + p` would silently keep the last of
+    duplicates; its record writer produces none, and they are refused here rather than reproduced"""
+    index = [np.ascontiguousarray(np.asarray(i).reshape(-1), dtype=np.int32) for i in index]
+    scene_of_block = np.ascontiguousarray(np.asarray(scene_of_block).reshape(-1), dtype=np.int64)
+    if len(index) != len(blocks) or scene_of_block.shape[0] != len(blocks):
+        raise ValueError("index and scene_of_block have one entry per block")
+    seen = set()
+    for k, (b, i) in enumerate(zip(blocks, index)):
+        if i.shape[0] != b.shape[0]:
+            raise ValueError("block %d: %d index values for %d rows" % (k, i.shape[0], b.shape[0]))
+        if i.size and i.min() < 0:
+            raise ValueError("block %d: negative index value" % k)
+        inner = i[b[:, 7] == 1]
+        if np.unique(inner).shape[0] != inner.shape[0]:
+            raise ValueError("block %d: two inner rows share an index value" % k)
+        s = int(scene_of_block[k])
+        if s < 0:
+            raise ValueError("block %d: negative scene number" % k)
+        if k and s != int(scene_of_block[k - 1]) and s in seen:
+            raise ValueError("the blocks of scene %d are not consecutive" % s)
+        seen.add(s)
+    return np.concatenate(index), scene_of_block
+
+
 class BlockPool:
     """The parsed blocks of a dataset, resident on the device: rows [T, 8] fp32 (blockio.parse_block's layout) back to back and
-    offsets [P+1] int64, uploaded once; `sizes` stays on the host."""
+    offsets [P+1] int64, uploaded once; `sizes` stays on the host.  With `index` (per block: int32 [n], the rows' positions in
+    their scene's voxel cloud) and `scene_of_block` [P] the pool also knows its scenes (harness/scenemerge.py): `index` [T]
+    int32 on the device, `scene_of_block` on the host, checked by check_scene_index.  Without them both are None."""
 
-    def __init__(self, blocks, device=None):
+    def __init__(self, blocks, device=None, index=None, scene_of_block=None):
         import torch
         blocks = [np.ascontiguousarray(b, dtype=np.float32) for b in blocks]
         if not blocks:
@@ -281,20 +310,37 @@ class BlockPool:
                 raise ValueError("a block is [n, 8]: xyz, rgb, label, inner")
             if b.shape[0] == 0:
                 raise ValueError("empty block")
+        if (index is None) != (scene_of_block is None):
+            raise ValueError("index and scene_of_block come together")
+        host_index = None
+        if index is not None:
+            host_index, scene_of_block = check_scene_index(blocks, index, scene_of_block)
         self.sizes = np.array([b.shape[0] for b in blocks], dtype=np.int64)
         self.host_offsets = np.concatenate(([0], np.cumsum(self.sizes))).astype(np.int64)
         self.device = torch.device(device if device is not None else "cuda:0")
         self.rows = torch.from_numpy(np.concatenate(blocks, axis=0)).to(self.device)
         self.offsets = torch.from_numpy(self.host_offsets).to(self.device)
+        self.scene_of_block = scene_of_block
+        self.index = torch.from_numpy(host_index).to(self.device) if host_index is not None else None
 
     @classmethod
     def from_blocks(cls, blocks, device=None):
         return cls(blocks, device)
 
     @classmethod
-    def from_records(cls, paths, device=None, verify=True):
+    def from_records(cls, paths, device=None, verify=True, with_index=False):
+        """with_index: also keep the records' index_label, and number the scenes by file — one record file is one scene, in
+        path order (the records' own scene_idx is not consulted)"""
         from . import blockio
-        return cls([blockio.parse_block(r) for p in paths for r in blockio.read_records(p, verify=verify)], device)
+        if not with_index:
+            return cls([blockio.parse_block(r) for p in paths for r in blockio.read_records(p, verify=verify)], device)
+        blocks, index, scene = [], [], []
+        for s, p in enumerate(paths):
+            for r in blockio.read_records(p, verify=verify):
+                blocks.append(blockio.parse_block(r))
+                index.append(blockio.parse_block_index(r)[0])
+                scene.append(s)
+        return cls(blocks, device, index, scene)
 
     def __len__(self):
         return int(self.sizes.shape[0])
