@@ -548,6 +548,57 @@ int sph3d_nn1(long long V, long long F, const float* ref_xyz, const float* query
 int sph3d_scene_lift(int C, long long V, long long F, const int* pred_voxel, const int* idx, const int* label_map,
                      const int* label_full, int* pred_full, long long* confusion, sph3d_stream_t stream);
 
+/* ---- scene preparation (MATLAB pcdownsample 'gridAverage', preprocesing/s3dis_prepare_data.m:35-37; the block writer,
+ * io/make_tfrecord_s3dis.py:113-242; csrc/prep.hip): a full-resolution cloud is averaged over the cells of a grid, the voxel cloud
+ * is recentred, and the blocks of a pool (rows [T,8], index [T], as sph3d_feed_assemble / sph3d_scene_merge read them) are cut
+ * from it.  harness/sceneprep.py states every entry in numpy, bit for bit, the fp32 means included.  Every buffer is the
+ * caller's; nothing is allocated, no floating-point atomic is used, every output is a pure function of the inputs.
+ *   prep_voxel_grid      xyz [F,3], attr [F,A] fp32 (A <= 13; null for A = 0).  A point is KEPT when its 3+A values are finite and
+ *                        at most 2^17 in magnitude.  lo / hi: extrema of the kept points; cell i_a = floor((v_a - lo_a) / h), both
+ *                        operations rounded to fp32 once; n_a = i_a(hi_a) + 1; key = (i_x n_y + i_y) n_z + i_z; the voxel rows are
+ *                        the occupied cells in ascending key.  -> voxel_of_point [F] int32 (-1: dropped) and header [16] int32 =
+ *                        { V, dropped, flag, n_x, n_y, n_z, lo[3], hi[3] (fp32 bits), cells, 0, 0, 0 }, the one thing the host
+ *                        reads before it allocates the [V, ...] arrays.  flag 1: the grid needs more than max_cells (<= 2^30) cells
+ *                        (or an axis does); flag 2: no point is kept; with a flag V = 0, voxel_of_point is all -1 and no cell is
+ *                        touched.  The workspace (sph3d_prep_voxel_grid_workspace(F, max_cells) bytes, 16-byte aligned) holds the
+ *                        dense table, 4 bytes per cell of max_cells.
+ *   prep_voxel_reduce    sums [V, 3+A] int64 and count [V] int32 (both zeroed here): sums[row, col] = sum over the row's points of
+ *                        rint(v * 2^20) (the double product is exact; ties to even; wraps modulo 2^64), count = the row's points.
+ *                        SPH3D_PREP_REDUCE_ATOMIC: 64-bit integer atomics, no workspace; SPH3D_PREP_REDUCE_SORTED: a counting
+ *                        sort of the points by row and a per-row sum, workspace sph3d_prep_voxel_reduce_workspace(F, V, mode).
+ *                        Integer sums: both give the same bits in any order.
+ *   prep_voxel_finalize  voxel_xyz [V,3], voxel_attr [V,A] = f32(f64(sum) / f64(count) * 2^-20); box: as prep_box of voxel_xyz.
+ *   prep_box             box [8] int32 = { lo[3], hi[3] of the finite points as ORDERED integers (an fp32 bit pattern u maps to
+ *                        ~u when its sign bit is set, else u | 2^31), their count, 0 }.
+ *   prep_normalise       make_tfrecord_s3dis.py:114-122 in fp32, each operation rounded once: c = (lo + hi) / 2 with c_z = lo_z
+ *                        from `box`, out_xyz = xyz - c, out_rgb = (2 rgb) / 255 - 1.
+ *   prep_rect_count      counts [R] int32 (zeroed here) = the points of xyz [V,3] with x_lo <= x <= x_hi and y_lo <= y <= y_hi for
+ *                        each of rects [R,4] fp32 = (x_lo, x_hi, y_lo, y_hi), 16-byte aligned: all candidates of a scene in one call.
+ *   prep_block_fill      rects [P,8]: per block the context-padded rectangle, then the plain one.  Block p receives the points
+ *                        inside its padded rectangle in ASCENDING point index at rows [offsets[p], offsets[p+1]) of rows [T,8]
+ *                        (xyz, rgb, (float)label, inner = inside the plain rectangle; 16-byte aligned) and index [T] (the point's
+ *                        number); offsets [P+1] int64 come from prep_rect_count's counts of the padded rectangles.  A block whose
+ *                        points are not as many as its range counts in *mismatch (accumulated) and nothing is written outside
+ *                        its range.  Workspace: sph3d_prep_block_fill_workspace(V, P) bytes, 16-byte aligned. */
+#define SPH3D_PREP_REDUCE_ATOMIC 0
+#define SPH3D_PREP_REDUCE_SORTED 1
+size_t sph3d_prep_voxel_grid_workspace(long long F, long long max_cells);
+int sph3d_prep_voxel_grid(long long F, int A, const float* xyz, const float* attr, float h, long long max_cells,
+                          int* voxel_of_point, int* header, void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+size_t sph3d_prep_voxel_reduce_workspace(long long F, long long V, int mode);
+int sph3d_prep_voxel_reduce(long long F, int A, long long V, const float* xyz, const float* attr, const int* voxel_of_point,
+                            int mode, long long* sums, int* count, void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+int sph3d_prep_voxel_finalize(long long V, int A, const long long* sums, const int* count, float* voxel_xyz, float* voxel_attr,
+                              int* box, sph3d_stream_t stream);
+int sph3d_prep_box(long long V, const float* xyz, int* box, sph3d_stream_t stream);
+int sph3d_prep_normalise(long long V, const float* voxel_xyz, const float* voxel_rgb, const int* box, float* out_xyz,
+                         float* out_rgb, sph3d_stream_t stream);
+int sph3d_prep_rect_count(long long V, int R, const float* xyz, const float* rects, int* counts, sph3d_stream_t stream);
+size_t sph3d_prep_block_fill_workspace(long long V, int P);
+int sph3d_prep_block_fill(long long V, int P, long long T, const float* xyz, const float* rgb, const int* label,
+                          const float* rects, const long long* offsets, float* rows, int* index, int* mismatch, void* workspace,
+                          size_t workspace_bytes, sph3d_stream_t stream);
+
 /* the segmentation nets' training loss (models/SPH3D_s3dis.py:116-133: per block the mean over the points with inner_label > 0
  * of the sparse softmax cross-entropy, summed over the batch by the caller) and its gradient in one launch:
  *   loss_part[b * S + s], S = sph3d_masked_softmax_xent_parts(N): the shares of S slices of block b's points in

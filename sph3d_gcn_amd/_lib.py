@@ -89,6 +89,16 @@ SIGNATURES = {
     "sph3d_nn1_workspace": (_S, [_L, _L]),
     "sph3d_nn1": (_I, [_L, _L, _P, _P, _I, _P, _P, _S, _P]),
     "sph3d_scene_lift": (_I, [_I, _L, _L] + [_P] * 6 + [_P]),
+    "sph3d_prep_voxel_grid_workspace": (_S, [_L, _L]),
+    "sph3d_prep_voxel_grid": (_I, [_L, _I, _P, _P, _F, _L, _P, _P, _P, _S, _P]),
+    "sph3d_prep_voxel_reduce_workspace": (_S, [_L, _L, _I]),
+    "sph3d_prep_voxel_reduce": (_I, [_L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _S, _P]),
+    "sph3d_prep_voxel_finalize": (_I, [_L, _I] + [_P] * 5 + [_P]),
+    "sph3d_prep_box": (_I, [_L, _P, _P, _P]),
+    "sph3d_prep_normalise": (_I, [_L] + [_P] * 5 + [_P]),
+    "sph3d_prep_rect_count": (_I, [_L, _I, _P, _P, _P, _P]),
+    "sph3d_prep_block_fill_workspace": (_S, [_L, _I]),
+    "sph3d_prep_block_fill": (_I, [_L, _I, _L] + [_P] * 8 + [_P, _S, _P]),
     "sph3d_pointwise_gemm_skinny_supported": (_I, [_I] * 4),
     "sph3d_pointwise_gemm_skinny": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_pointwise_gemm_skinny_tn_workspace": (_S, [_I] * 4),

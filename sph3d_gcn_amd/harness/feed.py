@@ -342,6 +342,35 @@ class BlockPool:
                 scene.append(s)
         return cls(blocks, device, index, scene)
 
+    @classmethod
+    def from_device(cls, rows, offsets, sizes, index, scene_of_block):
+        """a pool whose tensors are on the device already (harness/sceneprep.py: sph3d_prep_block_fill wrote them): rows [T, 8]
+        fp32, offsets [P+1] int64 and index [T] int32 device tensors, taken as they are — no host copy of the rows; sizes [P]
+        and scene_of_block [P] on the host.  check_scene_index is NOT run: what it checks holds by construction for the
+        block fill — a block's index values are the voxel rows inside a rectangle in ascending order, hence distinct and
+        non-negative — and the caller numbers the scenes consecutively; only the shapes and the scene order are checked here"""
+        import torch
+        sizes = np.ascontiguousarray(np.asarray(sizes).reshape(-1), dtype=np.int64)
+        scene_of_block = np.ascontiguousarray(np.asarray(scene_of_block).reshape(-1), dtype=np.int64)
+        for t in (rows, offsets, index):
+            if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.device == rows.device):
+                raise ValueError("from_device: rows, offsets and index are contiguous tensors on one device")
+        P, T = int(sizes.shape[0]), int(sizes.sum())
+        if P == 0 or (sizes <= 0).any():
+            raise ValueError("empty pool or empty block")
+        if rows.dtype != torch.float32 or tuple(rows.shape) != (T, 8) or index.dtype != torch.int32 or tuple(index.shape) != (T,):
+            raise ValueError("from_device: rows [T, 8] fp32 and index [T] int32 with T = sum of sizes expected")
+        if offsets.dtype != torch.int64 or tuple(offsets.shape) != (P + 1,):
+            raise ValueError("from_device: offsets [P+1] int64 expected")
+        if scene_of_block.shape[0] != P or scene_of_block.min() < 0 or (np.diff(scene_of_block) < 0).any():
+            raise ValueError("from_device: scene_of_block has one non-negative entry per block, ascending")
+        self = cls.__new__(cls)
+        self.sizes = sizes
+        self.host_offsets = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        self.device = rows.device
+        self.rows, self.offsets, self.index, self.scene_of_block = rows, offsets, index, scene_of_block
+        return self
+
     def __len__(self):
         return int(self.sizes.shape[0])
 

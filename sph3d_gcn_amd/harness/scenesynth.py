@@ -67,3 +67,15 @@ def split_scene(voxel_xyz, voxel_label, rgb=None, block=1.5, stride=0.75, contex
             blocks.append(rows)
             index.append(at)
     return blocks, index
+
+
+def coverage_cloud(seed, thresh=500):
+    """-> xyz [2602, 3] fp32 for the block writer's branches (harness/sceneprep.py: block_plan with thresh = 500): 2000 uniform
+    points in a 7.5 x 7.5 x 2 box (81 squares of 1.5 m every 0.75 m, about 80 points each: all sparse), 600 points in the
+    0.6 x 0.6 patch at (3.45, 3.45) (the squares over it are kept, the ones beside it merge into each of the eight neighbour
+    rectangles, some of them into the same one, the far ones are skipped), and the two corners of the box; shuffled"""
+    rng = np.random.RandomState(seed)
+    box = rng.rand(2000, 3) * np.array([7.5, 7.5, 2.0])
+    patch = np.array([3.45, 3.45, 0.0]) + rng.rand(600, 3) * np.array([0.6, 0.6, 2.0])
+    xyz = np.concatenate([box, patch, [[0.0, 0.0, 0.0], [7.5, 7.5, 2.0]]]).astype(np.float32)
+    return xyz[rng.permutation(len(xyz))]
