@@ -306,6 +306,19 @@ int sph3d_weighted_interpolate_grad(int B, int N, int M, int C, int K,
                                     float* grad_input,
                                     void* workspace /* sph3d_scatter_grad_workspace(B,M,N,K) */, size_t workspace_bytes,
                                     sph3d_stream_t stream);
+/* Interpolation of NARROW rows (C <= 16, 16 lanes per row): what the last un-pooling becomes when the layer behind it is a plain
+ * product with few outputs (interp(x) W = interp(x W): the logits layer).
+ *   output[b,n,:] = base[b,n,:] + sum_k w_k input[b, nn_index[b,n,k], :]     w_k = 1/nn_count[b,n] (weight == NULL) or weight[b,n,k]
+ * base [B,N,C] is optional (NULL: zero); a row without neighbours gets its base row unchanged.  The neighbours are summed in the
+ * order sph3d_mean_interpolate / sph3d_weighted_interpolate use for C <= 128.  The gradient with respect to `input` gathers over
+ * the transposed graph (F = 1), like sph3d_scatter_grad_t: no atomics, fixed order. */
+int sph3d_interpolate_narrow_supported(int C);
+int sph3d_interpolate_narrow(int B, int N, int M, int C, int K,
+                             const int* nn_index, const int* nn_count, const float* input,
+                             const float* weight, const float* base, float* output, sph3d_stream_t stream);
+int sph3d_interpolate_narrow_grad_t(int B, int Nin, int Mout, int C,
+                                    const int* offsets, const int* ent_key, const float* ent_scale,
+                                    const float* grad_output, float* grad_input, sph3d_stream_t stream);
 
 /* ---- sampling -----------------------------------------------------------
  * replaces farthestPointSampleLauncher (tf_ops/sampling/tf_sample_gpu.cu:77-80;

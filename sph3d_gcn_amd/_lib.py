@@ -65,6 +65,9 @@ SIGNATURES = {
     "sph3d_mean_interpolate_grad": (_I, [_I] * 5 + [_P] * 4 + [_P, _S, _P]),
     "sph3d_weighted_interpolate": (_I, [_I] * 5 + [_P] * 6),
     "sph3d_weighted_interpolate_grad": (_I, [_I] * 5 + [_P] * 5 + [_P, _S, _P]),
+    "sph3d_interpolate_narrow_supported": (_I, [_I]),
+    "sph3d_interpolate_narrow": (_I, [_I] * 5 + [_P] * 7),
+    "sph3d_interpolate_narrow_grad_t": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_farthest_point_sample_workspace": (_S, [_I] * 3),
     "sph3d_farthest_point_sample": (_I, [_I] * 3 + [_P, _P, _P, _S, _P]),
     "sph3d_pointwise_gemm": (_I, [_I] * 3 + [_P, _P, _P, _I, _I, _P, _P]),

@@ -401,6 +401,106 @@ __global__ __launch_bounds__(256) void gather_bwd_t_split(
     }
 }
 
+// ---- narrow rows (C <= 16): interpolation of PROJECTED features -----------------------------------------------------------------
+// The decoder's last un-pooling feeds only the logits layer, and both are linear: interp(x) W = interp(x W).  The projected rows
+// have num_cls (13) floats, and a wave per row would idle 3/4 of its lanes: here 16 lanes own a row, four rows per wave.  The 16
+// lanes of a row fetch 16 consecutive neighbour ids (weights / entries) with ONE coalesced load and hand them round by
+// shuffle, so an edge costs one gather instruction, not two.
+//   out[b, n, :] = base[b, n, :] + sum_k w_k z[b, idx[b, n, k], :]        w_k = 1 / cnt (mean) or weight[b, n, k]
+// The neighbours are summed as gather_fwd_half sums them (even slots, odd slots, then the two sums; mean: one multiplication by
+// 1 / cnt at the end), so that a projection that only selects channels gives that kernel's values bit for bit.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void narrow_interp_fwd(
+    long long rows, int Nf, int Mc, int C, int K,
+    const int* __restrict__ nnIndex, const int* __restrict__ nnCount, const float* __restrict__ z,
+    const float* __restrict__ weight, const float* __restrict__ base, float* __restrict__ out)
+{
+    const int l16 = (int)threadIdx.x & 15;
+    const bool act = l16 < C;
+    const int cc = act ? l16 : 0;
+    const long long stride = (long long)gridDim.x * 16;
+    for (long long r = (long long)blockIdx.x * 16 + ((int)threadIdx.x >> 4); r < rows; r += stride) {
+        const int b = (int)(r / Nf);
+        const float* __restrict__ zb = z + (size_t)b * Mc * C + cc;
+        int cnt = nnCount[r];
+        cnt = cnt < K ? cnt : K;
+        const int* __restrict__ irow = nnIndex + (size_t)r * K;
+        float acc0 = 0.f, acc1 = 0.f;
+        for (int k0 = 0; k0 < cnt; k0 += 16) {                     // (the 16 lanes of a row share cnt: they stay together)
+            const bool mine = k0 + l16 < cnt;
+            const int my_n = mine ? irow[k0 + l16] : 0;
+            float my_w = 1.f;
+            if (WEIGHTED) my_w = mine ? weight[(size_t)r * K + k0 + l16] : 0.f;
+            const int kn = (cnt - k0) < 16 ? (cnt - k0) : 16;
+#pragma unroll 4
+            for (int j = 0; j < kn; j += 2) {
+                const bool two = (j + 1) < kn;
+                const int n0 = __shfl(my_n, j, 16), n1 = __shfl(my_n, two ? j + 1 : j, 16);
+                float w0 = 1.f, w1 = two ? 1.f : 0.f;              // the odd tail: the same row again with weight 0, as gather_fwd_half
+                if (WEIGHTED) { w0 = __shfl(my_w, j, 16); w1 = two ? __shfl(my_w, j + 1, 16) : 0.f; }
+                const float x0 = zb[(size_t)n0 * C], x1 = zb[(size_t)n1 * C];
+                acc0 = fmaf(x0, w0, acc0);
+                acc1 = fmaf(x1, w1, acc1);
+            }
+        }
+        if (act) {
+            const float bv = base != nullptr ? base[(size_t)r * C + l16] : 0.f;
+            float o = bv;                                          // rows without neighbours: base, bit for bit
+            if (cnt > 0) {
+                float s = acc0 + acc1;
+                if (!WEIGHTED) s = s * (1.0f / (float)cnt);
+                o = base != nullptr ? bv + s : s;
+            }
+            out[(size_t)r * C + l16] = o;
+        }
+    }
+}
+
+// its gradient with respect to z, a gather over the transposed graph like gather_bwd_t: one WAVE per source point; each of its four
+// 16-lane groups takes 16 consecutive in-edges of every 64 (one coalesced load of the entries per 64 edges), two chains per
+// group, and the four groups' sums meet by shuffle in a fixed order: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void narrow_interp_bwd_t(
+    long long sources, int Nin, int Mout, int C,
+    const int* __restrict__ offsets, const int* __restrict__ entKey, const float* __restrict__ entScale,
+    const float* __restrict__ gradOutput, float* __restrict__ gradInput)
+{
+    const int lane = lane_id();
+    const int l16 = lane & 15, grp = lane >> 4;
+    const bool act = l16 < C;
+    const int cc = act ? l16 : 0;
+    const bool pk = entScale == nullptr;
+    const long long stride = (long long)gridDim.x * 4;
+    for (long long src = (long long)blockIdx.x * 4 + uniform((int)threadIdx.x >> 6); src < sources; src += stride) {
+        const int b = (int)(src / Nin);
+        const int n = (int)(src - (long long)b * Nin);
+        const float* __restrict__ gob = gradOutput + (size_t)b * Mout * C + cc;
+        const int* __restrict__ offb = offsets + (size_t)b * (Nin + 1);
+        const int e0 = offb[n], e1 = offb[n + 1];                  // (entries of cloud b start at b * Mout * K: see graph.hip)
+        float acc0 = 0.f, acc1 = 0.f;
+        for (int ec = e0; ec < e1; ec += 64) {                     // wave-uniform trips
+            const int e = ec + lane;
+            const bool mine = e < e1;
+            const int wk = mine ? entKey[e] : 0;
+            const int my_m = tg_key(wk, pk);
+            float my_s = 0.f;
+            if (mine) my_s = pk ? tg_packed_scale(wk) : entScale[e];
+            const int left = e1 - (ec + 16 * grp);                 // edges of this group in this trip
+#pragma unroll
+            for (int j = 0; j < 16; j += 2) {
+                const int m0 = __shfl(my_m, j, 16), m1 = __shfl(my_m, j + 1, 16);
+                const float s0 = __shfl(my_s, j, 16), s1 = __shfl(my_s, j + 1, 16);
+                // (entries past the list have key 0 — a valid row — and scale 0, and are skipped)
+                if (j < left) acc0 = fmaf(gob[(size_t)m0 * C], s0, acc0);
+                if (j + 1 < left) acc1 = fmaf(gob[(size_t)m1 * C], s1, acc1);
+            }
+        }
+        float s = acc0 + acc1;
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        if (act && grp == 0) gradInput[(size_t)src * C + l16] = s;
+    }
+}
+
 template <Mode MODE>
 static int launch_fwd(const char* who, int B, int Nin, int Mout, int C, int K,
                       const int* nn_index, const int* nn_count, const float* input, const float* weight,
@@ -573,6 +673,50 @@ extern "C" int sph3d_weighted_interpolate(int B, int N, int M, int C, int K, con
 {
     return launch_fwd<Mode::Weighted>("sph3d_weighted_interpolate", B, M, N, C, K, nn_index, nn_count, input, weight,
                                       output, nullptr, as_stream(stream));
+}
+
+// ---- interpolation of narrow (projected) rows, C <= 16 ----
+extern "C" int sph3d_interpolate_narrow_supported(int C) { return (C >= 1 && C <= 16) ? 1 : 0; }
+
+extern "C" int sph3d_interpolate_narrow(int B, int N, int M, int C, int K, const int* nn_index, const int* nn_count,
+                                        const float* input, const float* weight, const float* base, float* output,
+                                        sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B >= 0 && N >= 0 && M > 0 && C > 0 && K > 0, "interpolate_narrow: bad dims B=%d N=%d M=%d C=%d K=%d", B, N, M, C, K);
+    if (C > 16) {
+        set_error("interpolate_narrow: rows of at most 16 channels (got C=%d)", C);
+        return SPH3D_EUNSUPPORTED;
+    }
+    const long long rows = (long long)B * N;
+    if (rows == 0) return SPH3D_OK;
+    long long wgs = (rows + 15) / 16;
+    if (wgs > 65536) wgs = 65536;
+    hipStream_t st = as_stream(stream);
+    if (weight != nullptr)
+        hipLaunchKernelGGL(narrow_interp_fwd<true>, dim3((unsigned)wgs), dim3(256), 0, st, rows, N, M, C, K, nn_index, nn_count, input,
+                           weight, base, output);
+    else
+        hipLaunchKernelGGL(narrow_interp_fwd<false>, dim3((unsigned)wgs), dim3(256), 0, st, rows, N, M, C, K, nn_index, nn_count, input,
+                           weight, base, output);
+    return check_launch("sph3d_interpolate_narrow");
+}
+
+extern "C" int sph3d_interpolate_narrow_grad_t(int B, int Nin, int Mout, int C, const int* offsets, const int* ent_key,
+                                               const float* ent_scale, const float* grad_output, float* grad_input,
+                                               sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B >= 0 && Nin > 0 && Mout >= 0 && C > 0, "interpolate_narrow_grad_t: bad dims B=%d N=%d M=%d C=%d", B, Nin, Mout, C);
+    if (C > 16) {
+        set_error("interpolate_narrow_grad_t: rows of at most 16 channels (got C=%d)", C);
+        return SPH3D_EUNSUPPORTED;
+    }
+    if (B == 0) return SPH3D_OK;
+    const long long sources = (long long)B * Nin;
+    long long wgs = (sources + 3) / 4;
+    if (wgs > 65536) wgs = 65536;
+    hipLaunchKernelGGL(narrow_interp_bwd_t, dim3((unsigned)wgs), dim3(256), 0, as_stream(stream), sources, Nin, Mout, C, offsets,
+                       ent_key, ent_scale, grad_output, grad_input);
+    return check_launch("sph3d_interpolate_narrow_grad_t");
 }
 
 extern "C" int sph3d_weighted_interpolate_grad(int B, int N, int M, int C, int K, const int* nn_index,

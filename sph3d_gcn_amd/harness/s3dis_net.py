@@ -453,18 +453,22 @@ def get_model(points, is_training, config=None, graphs=None, points_ready=None):
                                       g["filt_idx"], 'deconv' + str(l + 1), multiplier[l], reuse=reuse,
                                       weight_decay=config.weight_decay, with_bn=config.with_bn,
                                       with_bias=config.with_bias, is_training=is_training)
-        net = s3g_util.unpool3d(net, g["inter_idx"], g["inter_cnt"], g["inter_dst"], method=config.unpool_method,
-                                scope='unpool' + str(l + 1))
         if l + 1 < len(channels):
+            net = s3g_util.unpool3d(net, g["inter_idx"], g["inter_cnt"], g["inter_dst"], method=config.unpool_method,
+                                    scope='unpool' + str(l + 1))
             # tf.concat((net, encoder[l]), axis=2) (models/SPH3D_s3dis.py:100-104) feeds the next level's separable convolution,
             # which takes the pair as it is (s3g_util.separable_conv3d: the depthwise kernels read both tensors in place)
             net = (net, encoder[l])
-    # the last concatenation (models/SPH3D_s3dis.py:104) feeds only the logits layer: that layer reads its two halves in place
-    # (s3g_util.pointwise_conv3d_concat); end_points['feats'] materialises the concatenation when somebody asks for it
+    # the last un-pooling and concatenation (models/SPH3D_s3dis.py:99-104) feed only the logits layer, a plain product: the
+    # product runs before the interpolation, on the coarse points (s3g_util.unpool_logits), and the skip half is read in place;
+    # end_points['feats'] interpolates and concatenates when somebody asks for it
+    coarse, skip = net, encoder[len(channels) - 1]
+    unpool_kw = dict(method=config.unpool_method, scope='unpool' + str(len(channels)))
     end_points = _EndPoints(end_points)
-    end_points.feats_parts = (net, encoder[len(channels) - 1])
-    net = s3g_util.pointwise_conv3d_concat(net, encoder[len(channels) - 1], config.num_cls, scope='logits', with_bn=False,
-                                           with_bias=config.with_bias, activation_fn=None, is_training=is_training)
+    end_points.feats_parts = (lambda: s3g_util.unpool3d(coarse, g["inter_idx"], g["inter_cnt"], g["inter_dst"], **unpool_kw), skip)
+    net = s3g_util.unpool_logits(coarse, g["inter_idx"], g["inter_cnt"], g["inter_dst"], skip, config.num_cls, scope='logits',
+                                 method=config.unpool_method, with_bn=False, with_bias=config.with_bias, activation_fn=None,
+                                 is_training=is_training)
     return net, end_points
 
 
@@ -474,7 +478,7 @@ class _EndPoints(dict):
 
     def __missing__(self, key):
         if key == 'feats' and self.feats_parts is not None:
-            self['feats'] = torch.cat(self.feats_parts, dim=2)
+            self['feats'] = torch.cat([p() if callable(p) else p for p in self.feats_parts], dim=2)
             return self['feats']
         raise KeyError(key)
 

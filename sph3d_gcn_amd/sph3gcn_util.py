@@ -483,21 +483,52 @@ def pool3d_with_skip(inputs, nn_index, nn_count, scope, method):
     return pool3d(inputs, nn_index, nn_count, scope, method), inputs
 
 
+def _unpool_weights(nn_dist):
+    """the 'weighted' un-pooling's factors (utils/sph3gcn_util.py:313-317)"""
+    sum_nn_dist = torch.sum(nn_dist, dim=-1, keepdim=True)
+    epsilon = 1e-7
+    return (nn_dist + epsilon) / (sum_nn_dist + epsilon)
+
+
 def unpool3d(inputs, nn_index, nn_count, nn_dist, scope, method):
     """Feature interpolation back onto the finer point set, method 'mean' or 'weighted' (same signature as
     utils/sph3gcn_util.py:300-325)."""
     if method == 'mean':
         outputs = tf_unpool3d.mean_interpolate(inputs, nn_index, nn_count)
     elif method == 'weighted':
-        sum_nn_dist = torch.sum(nn_dist, dim=-1, keepdim=True)
-        epsilon = 1e-7
-        weight = (nn_dist + epsilon) / (sum_nn_dist + epsilon)
-        outputs = tf_unpool3d.weighted_interpolate(inputs, weight, nn_index, nn_count)
+        outputs = tf_unpool3d.weighted_interpolate(inputs, _unpool_weights(nn_dist), nn_index, nn_count)
     else:
         raise ValueError("Unknow unpooling method %s." % method)
     return outputs
 
 
+def unpool_logits(inputs, nn_index, nn_count, nn_dist, skip, num_out_channels, scope, method, use_xavier=True, stddev=1e-3,
+                  weight_decay=None, activation_fn=None, with_bn=False, with_bias=False, reuse=None, is_training=None):
+    """pointwise_conv3d_concat(unpool3d(inputs, ...), skip, num_out_channels, scope, ...) — same variables, created in the same
+    order — for a layer that is a plain product with few outputs (the logits layer of models/SPH3D_s3dis.py:99-108).
+    Interpolation and product are both linear, so the product runs on the COARSE points and the interpolation moves rows of
+    num_out_channels floats (tf_unpool3d.interpolate_linear); `skip` may be None.  Anything else takes the two calls."""
+    fn = getattr(tf_unpool3d, "interpolate_linear", None)          # (the oracle-backed CPU stand-ins of the tests have none)
+    if (FUSE_UNPOOL_LOGITS and fn is not None and inputs.is_cuda and not with_bn and activation_fn is None
+            and (skip is None or FUSE_LOGITS_CONCAT) and method in ('mean', 'weighted')
+            and tf_unpool3d.linear_supported(num_out_channels)):
+        cs = 0 if skip is None else skip.shape[-1]
+        kernel = _variable_with_weight_decay(scope + '/weights', shape=[inputs.shape[-1] + cs, num_out_channels],
+                                             use_xavier=use_xavier, stddev=stddev, with_decay=weight_decay)
+        biases = get_variable_store().get_variable(scope + '/biases', [num_out_channels], _constant(0.0)) if with_bias else None
+        weight = _unpool_weights(nn_dist) if method == 'weighted' else None
+        return fn(inputs, skip, kernel, biases, nn_index, nn_count, weight=weight)
+    net = unpool3d(inputs, nn_index, nn_count, nn_dist, scope, method)
+    if skip is None:
+        return pointwise_conv3d(net, num_out_channels, scope, use_xavier=use_xavier, stddev=stddev, weight_decay=weight_decay,
+                                activation_fn=activation_fn, with_bn=with_bn, with_bias=with_bias, reuse=reuse,
+                                is_training=is_training)
+    return pointwise_conv3d_concat(net, skip, num_out_channels, scope, use_xavier=use_xavier, stddev=stddev,
+                                   weight_decay=weight_decay, activation_fn=activation_fn, with_bn=with_bn, with_bias=with_bias,
+                                   reuse=reuse, is_training=is_training)
+
+
+FUSE_UNPOOL_LOGITS = True         # unpool_logits: the last un-pooling behind the logits product, on num_cls-wide rows
 FUSE_GEMM_BN = True    # the statistics of that tail from the GEMM's epilogue where the shape allows (tf_norm.gemm_elu_batch_norm)
 FUSE_POOL_SKIP = True             # pool3d_with_skip: the skip connection's gradient is added inside the max-pool gradient kernel
 FUSE_CONV_CONCAT = True           # separable_conv3d((a, b), ...): depthwise kernels over two inputs in place (tf_conv3d.depthwise_conv3d_concat)
