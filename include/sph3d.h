@@ -523,6 +523,39 @@ int sph3d_vote_finalize(int B, int C, int num_blocks, long long total_rows, cons
                         const int* block_ids, long long row_base, long long batch_rows, const float* votes, int* pred,
                         long long* confusion, long long* nonfinite, sph3d_stream_t stream);
 
+/* ---- the input side of the object datasets (shapenet_seg/train_shapenet.py:121-152, modelnet40_cls/train_modelnet.py:95-115,
+ * shapenet_seg/evaluate_shapenet.py:86-94) on the device: one launch assembles a batch from a resident pool of shapes.  The pool
+ * is sph3d_feed_assemble's (rows [T,8]: xyz in columns 0:3, the label in column 6; offsets [P+1]; shape_ids [B] int32, device),
+ * and so are the sample draws: index is the same pure function of (seed, step, b, n, num_point) and does not depend on recipe.
+ * recipe [B] int32 (device): per cloud a bit mask, applied in the reference's order (utils/data_util.py) —
+ *   1 TURN   xyz . Rz(2 pi u);   2 TILT   . Rz Ry Rx of three normal angles (sigma 0.06, clipped at 0.18);
+ *   4 SCALE  * (0.8 + 0.45 u);   8 SHIFT  + (-0.1 + 0.2 u) per axis;   16 JITTER  + normal noise per point (sigma 0.01, clip 0.02);
+ * bits above 16 are ignored.  A mask of 0 copies xyz bit for bit.  Every draw is a pure function of (seed, step, b, slot, purpose)
+ * (csrc/feed_draws.hpp, csrc/objfeed.hip; harness/objfeed.py states them in numpy).
+ * -> points [B,num_point,3] fp32, label [B,num_point] int32, index [B,num_point] int32 (nullable): the row of its shape each
+ * point came from.  A shape id outside [0, P) or an offset pair outside [0, T] reads nothing: zeros and index -1.  B <= 65535. */
+int sph3d_objfeed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                           const int* shape_ids, unsigned long long seed, unsigned long long step, const int* recipe,
+                           float* points, int* label, int* index, sph3d_stream_t stream);
+
+/* ---- the per-shape part IoU counts of the ShapeNet evaluation (shapenet_seg/evaluate_shapenet.py:262-289,
+ * evaluate_shapenet_onehot.py:283-314; csrc/shapeeval.hip): the finalize of a batch of sph3d_vote_* whose blocks are shapes (same
+ * rows / offsets / shape_ids / row_base / batch_rows, votes [batch_rows, C] as the accumulates left them, the part label in
+ * column 6 of the rows).  part_lo, part_n [B] int32 (device): the part range of each shape inside the C sums
+ * (0 < part_n, part_lo + part_n <= C <= 64; a per-category model has part_lo = 0, part_n = C).
+ *   pred[row] = part_lo[b] + first maximum of votes[row, part_lo[b] : part_lo[b] + part_n[b]] (a NaN counts as a maximum, as
+ *   np.argmax); per shape b and part l of its range: inter[b*C + l] = rows with pred == l and label == l, pred_cnt[b*C + l] = rows
+ *   with pred == l, gt_cnt[b*C + l] = rows with label == l; correct[b] = rows with pred == label.  A label outside the shape's
+ *   range matches no part.  inter / pred_cnt / gt_cnt [B,C] and correct [B] int32 are zeroed here; *nonfinite (int64) += rows of
+ *   the batch's shapes whose C sums are not all finite (accumulated, not zeroed).
+ * A shape id outside [0, P), a shape that is not inside the batch's row range, or one whose part range is not inside [0, C)
+ * takes no part: it counts nothing and none of its predictions is written.  Every buffer is the caller's; nothing is allocated,
+ * no floating-point atomic is used; harness/shapeeval.py:shape_vote_reference states it in numpy. */
+int sph3d_shape_iou(int B, int C, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                    const int* shape_ids, long long row_base, long long batch_rows, const float* votes, const int* part_lo,
+                    const int* part_n, int* pred, int* inter, int* pred_cnt, int* gt_cnt, int* correct, long long* nonfinite,
+                    sph3d_stream_t stream);
+
 /* ---- scene-level evaluation (post-merging/s3dis_merge.m:42-82, scannet_merge.m:28-55; csrc/scene.hip): the blocks' vote sums are
  * normalised per row, merged into a per-scene array through the records' index_label, and the arg-max is lifted to the
  * full-resolution cloud through a nearest-neighbour search.  harness/scenemerge.py states every entry in numpy, bit for bit, the

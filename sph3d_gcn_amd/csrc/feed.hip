@@ -13,48 +13,9 @@
 //               [third, 2 third) get clipped normal noise per coordinate.  Uniforms are (bits >> 8) * 2^-24, normals Box-Muller
 //               in fp32 with u1 = ((hi >> 8) + 1) * 2^-24 (never 0) and u2 from the low word of the same draw.
 // Traffic: two 16-byte loads of a random 32-byte row and 36 bytes of stores per point — bound by the launch and the row reads.
-#include "common.hpp"
+#include "feed_draws.hpp"
 
 namespace sph3d {
-
-constexpr unsigned long long kFeedGold = 0x9e3779b97f4a7c15ull;
-constexpr int kFeedRounds = 6;
-enum : unsigned long long { kFeedPerm = 1, kFeedRepl = 2, kFeedTurn = 3, kFeedTilt = 4, kFeedJitter = 5 };
-
-__host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long long z)
-{
-    z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ull;
-    z ^= z >> 27; z *= 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ __forceinline__ unsigned long long feed_cloud_key(unsigned long long seed, unsigned long long step, unsigned b)
-{
-    return feed_mix(feed_mix(feed_mix(seed + kFeedGold) + step + kFeedGold) + b + kFeedGold);
-}
-__device__ __forceinline__ unsigned long long feed_draw(unsigned long long ck, unsigned long long purpose, unsigned counter)
-{
-    return feed_mix(ck ^ (purpose << 56 | counter));
-}
-__device__ __forceinline__ unsigned feed_fmix32(unsigned x)
-{
-    x ^= x >> 16; x *= 0x85ebca6bu;
-    x ^= x >> 13; x *= 0xc2b2ae35u;
-    return x ^ (x >> 16);
-}
-__device__ __forceinline__ float feed_uniform(unsigned bits) { return (float)(bits >> 8) * 0x1p-24f; }
-
-// two independent N(0,1) from one 64-bit draw
-__device__ __forceinline__ void feed_normal_pair(unsigned long long w, float& z0, float& z1)
-{
-    const float u1 = (float)(((unsigned)(w >> 32) >> 8) + 1u) * 0x1p-24f;
-    const float u2 = feed_uniform((unsigned)w);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincosf(6.283185307179586f * u2, &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
-__device__ __forceinline__ float feed_clip(float v, float lim) { return fminf(fmaxf(v, -lim), lim); }
 
 __global__ __launch_bounds__(256) void feed_assemble_kernel(int B, int N, int P, long long T, const float* __restrict__ rows,
                                                             const long long* __restrict__ offsets, const int* __restrict__ block_ids,
