@@ -140,6 +140,19 @@ static inline TgLayout tg_layout(void* workspace, int B, int N, int M, int K, in
 constexpr unsigned kTgKeyMask = 0x00ffffffu;
 static inline bool tg_packable(int M, int K, const void* weight) { return weight == nullptr && M <= (1 << 24) && K <= 255; }
 
+// ---- the vote entry points (vote.hip, shapeeval.hip): what they all require of a batch and its row range; `what` heads the message
+constexpr int kVoteMaxClasses = 64;
+static inline int vote_check_args(const char* what, int B, int C, int num_blocks, long long total_rows, long long row_base,
+                                  long long batch_rows)
+{
+    SPH3D_REQUIRE(B > 0 && B <= 65535, "%s: batch 0<B<=65535 required, got %d", what, B);
+    SPH3D_REQUIRE(C > 0 && C <= kVoteMaxClasses, "%s: 0<C<=%d classes required, got %d", what, kVoteMaxClasses, C);
+    SPH3D_REQUIRE(num_blocks > 0 && total_rows > 0, "%s: empty pool (num_blocks=%d total_rows=%lld)", what, num_blocks, total_rows);
+    SPH3D_REQUIRE(row_base >= 0 && batch_rows > 0 && batch_rows <= 0x7fffffffll && row_base + batch_rows <= total_rows,
+                  "%s: rows [%lld, %lld + %lld) are not a range of the pool's %lld", what, row_base, row_base, batch_rows, total_rows);
+    return SPH3D_OK;
+}
+
 // ---- device helpers -----------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
@@ -159,7 +172,7 @@ __device__ __forceinline__ float uniformf(float v)
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
-// vote.hip, scene.hip — the rows of cloud b of a batch inside the pool and inside the batch's row range: -> n (0: the cloud takes no part), lo = its first pool row
+// vote.hip, scene.hip, shapeeval.hip — the rows of cloud b of a batch inside the pool and inside the batch's row range: -> n (0: the cloud takes no part), lo = its first pool row
 __device__ __forceinline__ long long vote_cloud(int b, int P, long long T, const long long* __restrict__ offsets,
                                                 const int* __restrict__ block_ids, long long row_base, long long batch_rows,
                                                 long long& lo)
@@ -172,6 +185,37 @@ __device__ __forceinline__ long long vote_cloud(int b, int P, long long T, const
     if (n <= 0 || n > 0x7fffffffll || lo < 0 || lo + n > T) return 0;
     if (lo < row_base || lo + n > row_base + batch_rows) return 0;
     return n;
+}
+
+// the first maximum of v[lo, lo + n) as np.argmax takes it (a NaN is a maximum); finite: all C entries of v are finite
+__device__ __forceinline__ int vote_argmax(const float* __restrict__ v, int lo, int n, int C, bool& finite)
+{
+    finite = true;
+    for (int c = 0; c < lo; ++c) finite = finite && isfinite(v[c]);
+    float best = v[lo];
+    int arg = lo;
+    finite = finite && isfinite(best);
+    for (int c = lo + 1; c < lo + n; ++c) {
+        const float x = v[c];
+        finite = finite && isfinite(x);
+        if (!isnan(best) && (x > best || isnan(x))) {
+            best = x;
+            arg = c;
+        }
+    }
+    for (int c = lo + n; c < C; ++c) finite = finite && isfinite(v[c]);
+    return arg;
+}
+
+// scene.hip, prep.hip — a float as an unsigned whose integer order is the float order (for atomicMin / atomicMax), and back
+__device__ __forceinline__ unsigned f2ord(float f)
+{
+    const unsigned u = (unsigned)__float_as_int(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(unsigned o)
+{
+    return __int_as_float((int)((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o));
 }
 
 // XCD-affine work decode.  Workgroup `bid` runs on XCD (bid % 8) (observed placement, used for

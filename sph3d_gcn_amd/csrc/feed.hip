@@ -30,75 +30,36 @@ __global__ __launch_bounds__(256) void feed_assemble_kernel(int B, int N, int P,
     float2* out = reinterpret_cast<float2*>(points + i * 6);
 
     // the cloud's rows; a block id or an offset pair that does not describe rows of the pool reads nothing (index -1, zeros)
-    const int id = block_ids[b];
-    long long lo = 0, n64 = 0;
-    if (id >= 0 && id < P) {
-        lo = offsets[id];
-        n64 = offsets[id + 1] - lo;
-    }
-    if (n64 <= 0 || n64 > 0x7fffffffll || lo < 0 || lo + n64 > T) {
+    long long lo;
+    const unsigned n = feed_pool_rows(block_ids[b], P, T, offsets, lo);
+    if (n == 0u) {
         out[0] = out[1] = out[2] = make_float2(0.f, 0.f);
         label[i] = 0;
         inner[i] = 0;
         if (index != nullptr) index[i] = -1;
         return;
     }
-    const unsigned n = (unsigned)n64;
     const unsigned long long ck = feed_cloud_key(seed, step, (unsigned)b);
-
-    unsigned r;
-    if (n >= (unsigned)N) {
-        const int k = n > 1 ? 32 - __builtin_clz(n - 1) : 0;        // 2^k >= n > 2^(k-1)
-        const int half = (k + 1) >> 1;
-        const unsigned mask = (1u << half) - 1u;                       // (half <= 16)
-        unsigned rk[kFeedRounds];
-#pragma unroll
-        for (int t = 0; t < kFeedRounds; ++t) rk[t] = (unsigned)(feed_draw(ck, kFeedPerm, (unsigned)t) >> 32);
-        r = slot;
-        do {
-            unsigned L = r >> half, R = r & mask;
-#pragma unroll
-            for (int t = 0; t < kFeedRounds; ++t) {
-                const unsigned f = feed_fmix32(R ^ rk[t]) & mask;
-                const unsigned nl = R;
-                R = L ^ f;
-                L = nl;
-            }
-            r = (L << half) | R;
-        } while (r >= n);
-    } else {
-        r = __umulhi((unsigned)(feed_draw(ck, kFeedRepl, slot) >> 32), n);
-    }
+    const unsigned r = feed_sample_row(ck, n, (unsigned)N, slot);
 
     const float4* src = reinterpret_cast<const float4*>(rows + (lo + (long long)r) * 8);
     const float4 a = src[0], c = src[1];            // x y z r | g b label inner
     float x = a.x, y = a.y, z = a.z;
     const int third = B / 3;
     if (augment && b < third) {
-        // xyz . Rz(theta) . (Rz(az) Ry(ay) Rx(ax)), row vector times matrix (utils/data_util.py:47-61,140-163); the nine
+        // xyz . Rz(theta) . (Rz(az) Ry(ay) Rx(ax)), row vector times matrix (utils/data_util.py:47-61,140-163); the eleven
         // numbers are the same for every point of the cloud: each thread recomputes them (4 sincos)
-        const float th = 6.283185307179586f * feed_uniform((unsigned)(feed_draw(ck, kFeedTurn, 0u) >> 32));
-        float ax, ay, az, unused;
-        feed_normal_pair(feed_draw(ck, kFeedTilt, 0u), ax, ay);
-        feed_normal_pair(feed_draw(ck, kFeedTilt, 1u), az, unused);
-        ax = feed_clip(0.06f * ax, 0.18f); ay = feed_clip(0.06f * ay, 0.18f); az = feed_clip(0.06f * az, 0.18f);
-        float st, ct, sx, cx, sy, cy, sz, cz;
-        sincosf(th, &st, &ct); sincosf(ax, &sx, &cx); sincosf(ay, &sy, &cy); sincosf(az, &sz, &cz);
-        const float x1 = x * ct + y * st, y1 = y * ct - x * st;        // . Rz(theta) = [[c,-s,0],[s,c,0],[0,0,1]]
-        // M = Rz Ry Rx
-        const float m00 = cz * cy, m01 = cz * sy * sx - sz * cx, m02 = cz * sy * cx + sz * sx;
-        const float m10 = sz * cy, m11 = sz * sy * sx + cz * cx, m12 = sz * sy * cx - cz * sx;
-        const float m20 = -sy, m21 = cy * sx, m22 = cy * cx;
-        x = x1 * m00 + y1 * m10 + a.z * m20;
-        y = x1 * m01 + y1 * m11 + a.z * m21;
-        z = x1 * m02 + y1 * m12 + a.z * m22;
+        float st, ct, m[9];
+        feed_turn(ck, st, ct);
+        feed_tilt(ck, m);
+        const float x1 = x * ct + y * st, y1 = y * ct - x * st;
+        x = x1 * m[0] + y1 * m[3] + a.z * m[6];
+        y = x1 * m[1] + y1 * m[4] + a.z * m[7];
+        z = x1 * m[2] + y1 * m[5] + a.z * m[8];
     } else if (augment && b < 2 * third) {
-        float j0, j1, j2, unused;
-        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot), j0, j1);
-        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot + 1u), j2, unused);
-        x += feed_clip(0.01f * j0, 0.02f);
-        y += feed_clip(0.01f * j1, 0.02f);
-        z += feed_clip(0.01f * j2, 0.02f);
+        float j0, j1, j2;
+        feed_jitter(ck, slot, j0, j1, j2);
+        x += j0; y += j1; z += j2;
     }
     out[0] = make_float2(x, y);
     out[1] = make_float2(z, a.w);

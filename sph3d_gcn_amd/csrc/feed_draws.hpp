@@ -75,4 +75,48 @@ __device__ __forceinline__ unsigned feed_sample_row(unsigned long long ck, unsig
     return r;
 }
 
+// the rows of pool block `id`: -> n (0 for an id or an offset pair that does not describe rows of the pool), lo = its first row
+__device__ __forceinline__ unsigned feed_pool_rows(int id, int P, long long T, const long long* __restrict__ offsets, long long& lo)
+{
+    long long n64 = 0;
+    lo = 0;
+    if (id >= 0 && id < P) {
+        lo = offsets[id];
+        n64 = offsets[id + 1] - lo;
+    }
+    return (n64 <= 0 || n64 > 0x7fffffffll || lo < 0 || lo + n64 > T) ? 0u : (unsigned)n64;
+}
+
+// The cloud-level numbers below are computed per lane: feed.hip's flat mapping lets one wave span two clouds, so only a caller
+// whose workgroup serves one cloud (objfeed.hip) may pin what they return with uniformf().
+
+// sin / cos of the turn: xyz . Rz(theta) = [[c,-s,0],[s,c,0],[0,0,1]] is  x' = x c + y s,  y' = y c - x s
+__device__ __forceinline__ void feed_turn(unsigned long long ck, float& st, float& ct)
+{
+    sincosf(6.283185307179586f * feed_uniform((unsigned)(feed_draw(ck, kFeedTurn, 0u) >> 32)), &st, &ct);
+}
+
+// m = Rz(az) Ry(ay) Rx(ax), row-major, of three clipped normal angles (utils/data_util.py:140-163); xyz . m is the tilt
+__device__ __forceinline__ void feed_tilt(unsigned long long ck, float (&m)[9])
+{
+    float ax, ay, az, unused;
+    feed_normal_pair(feed_draw(ck, kFeedTilt, 0u), ax, ay);
+    feed_normal_pair(feed_draw(ck, kFeedTilt, 1u), az, unused);
+    ax = feed_clip(0.06f * ax, 0.18f); ay = feed_clip(0.06f * ay, 0.18f); az = feed_clip(0.06f * az, 0.18f);
+    float sx, cx, sy, cy, sz, cz;
+    sincosf(ax, &sx, &cx); sincosf(ay, &sy, &cy); sincosf(az, &sz, &cz);
+    m[0] = cz * cy; m[1] = cz * sy * sx - sz * cx; m[2] = cz * sy * cx + sz * sx;
+    m[3] = sz * cy; m[4] = sz * sy * sx + cz * cx; m[5] = sz * sy * cx - cz * sx;
+    m[6] = -sy;     m[7] = cy * sx;                m[8] = cy * cx;
+}
+
+// the clipped normal noise of slot `slot`, one number per coordinate
+__device__ __forceinline__ void feed_jitter(unsigned long long ck, unsigned slot, float& j0, float& j1, float& j2)
+{
+    float unused;
+    feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot), j0, j1);
+    feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot + 1u), j2, unused);
+    j0 = feed_clip(0.01f * j0, 0.02f); j1 = feed_clip(0.01f * j1, 0.02f); j2 = feed_clip(0.01f * j2, 0.02f);
+}
+
 }  // namespace sph3d

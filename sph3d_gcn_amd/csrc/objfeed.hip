@@ -35,19 +35,14 @@ __global__ __launch_bounds__(256) void objfeed_assemble_kernel(int N, int P, lon
     float* out = points + i * 3;
 
     // the cloud's rows; a shape id or an offset pair that does not describe rows of the pool reads nothing (index -1, zeros)
-    const int id = shape_ids[b];
-    long long lo = 0, n64 = 0;
-    if (id >= 0 && id < P) {
-        lo = offsets[id];
-        n64 = offsets[id + 1] - lo;
-    }
-    if (n64 <= 0 || n64 > 0x7fffffffll || lo < 0 || lo + n64 > T) {
+    long long lo;
+    const unsigned n = feed_pool_rows(shape_ids[b], P, T, offsets, lo);
+    if (n == 0u) {
         out[0] = out[1] = out[2] = 0.f;
         label[i] = 0;
         if (index != nullptr) index[i] = -1;
         return;
     }
-    const unsigned n = (unsigned)n64;
     const unsigned long long ck = feed_cloud_key(seed, step, (unsigned)b);
     const int mask = uniform(recipe[b]) & kObjAll;
 
@@ -59,27 +54,20 @@ __global__ __launch_bounds__(256) void objfeed_assemble_kernel(int N, int P, lon
 
     // row vector times matrix, as utils/data_util.py writes it; the cloud's numbers are the same in every lane
     if (mask & kObjTurn) {
-        const float th = 6.283185307179586f * feed_uniform((unsigned)(feed_draw(ck, kFeedTurn, 0u) >> 32));
         float st, ct;
-        sincosf(th, &st, &ct);
+        feed_turn(ck, st, ct);
         st = uniformf(st); ct = uniformf(ct);
-        const float x1 = x * ct + y * st, y1 = y * ct - x * st;        // . Rz(theta) = [[c,-s,0],[s,c,0],[0,0,1]]
+        const float x1 = x * ct + y * st, y1 = y * ct - x * st;
         x = x1; y = y1;
     }
     if (mask & kObjTilt) {
-        float ax, ay, az, unused;
-        feed_normal_pair(feed_draw(ck, kFeedTilt, 0u), ax, ay);
-        feed_normal_pair(feed_draw(ck, kFeedTilt, 1u), az, unused);
-        ax = feed_clip(0.06f * ax, 0.18f); ay = feed_clip(0.06f * ay, 0.18f); az = feed_clip(0.06f * az, 0.18f);
-        float sx, cx, sy, cy, sz, cz;
-        sincosf(ax, &sx, &cx); sincosf(ay, &sy, &cy); sincosf(az, &sz, &cz);
-        // M = Rz Ry Rx
-        const float m00 = uniformf(cz * cy), m01 = uniformf(cz * sy * sx - sz * cx), m02 = uniformf(cz * sy * cx + sz * sx);
-        const float m10 = uniformf(sz * cy), m11 = uniformf(sz * sy * sx + cz * cx), m12 = uniformf(sz * sy * cx - cz * sx);
-        const float m20 = uniformf(-sy), m21 = uniformf(cy * sx), m22 = uniformf(cy * cx);
-        const float x1 = x * m00 + y * m10 + z * m20;
-        const float y1 = x * m01 + y * m11 + z * m21;
-        const float z1 = x * m02 + y * m12 + z * m22;
+        float m[9];
+        feed_tilt(ck, m);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) m[k] = uniformf(m[k]);
+        const float x1 = x * m[0] + y * m[3] + z * m[6];
+        const float y1 = x * m[1] + y * m[4] + z * m[7];
+        const float z1 = x * m[2] + y * m[5] + z * m[8];
         x = x1; y = y1; z = z1;
     }
     if (mask & kObjScale) {
@@ -92,12 +80,9 @@ __global__ __launch_bounds__(256) void objfeed_assemble_kernel(int N, int P, lon
         z += uniformf(-0.1f + 0.2f * feed_uniform((unsigned)(feed_draw(ck, kFeedShift, 2u) >> 32)));
     }
     if (mask & kObjJitter) {
-        float j0, j1, j2, unused;
-        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot), j0, j1);
-        feed_normal_pair(feed_draw(ck, kFeedJitter, 2u * slot + 1u), j2, unused);
-        x += feed_clip(0.01f * j0, 0.02f);
-        y += feed_clip(0.01f * j1, 0.02f);
-        z += feed_clip(0.01f * j2, 0.02f);
+        float j0, j1, j2;
+        feed_jitter(ck, slot, j0, j1, j2);
+        x += j0; y += j1; z += j2;
     }
     out[0] = x; out[1] = y; out[2] = z;
     label[i] = (int)lab;

@@ -41,15 +41,6 @@ struct PrepBox {
     int kept, pad;
 };
 
-__device__ __forceinline__ unsigned prep_f2ord(float f)
-{
-    const unsigned u = (unsigned)__float_as_int(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float prep_ord2f(unsigned o)
-{
-    return __int_as_float((int)((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o));
-}
 __device__ __forceinline__ bool prep_ok(float v) { return fabsf(v) <= kPrepMaxValue; }      // false for NaN and infinities
 
 __device__ __forceinline__ bool prep_kept(long long i, int A, const float* __restrict__ xyz, const float* __restrict__ attr)
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(256) void prep_bbox_kernel(long long F, int A, cons
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < F; i += (long long)gridDim.x * 256) {
         const float x = xyz[i * 3], y = xyz[i * 3 + 1], z = xyz[i * 3 + 2];
         if (A >= 0 ? !prep_kept(i, A, xyz, attr) : !(fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY)) continue;
-        const unsigned o[3] = {prep_f2ord(x), prep_f2ord(y), prep_f2ord(z)};
+        const unsigned o[3] = {f2ord(x), f2ord(y), f2ord(z)};
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], o[a]); hi[a] = max(hi[a], o[a]); }
         ++cnt;
@@ -151,7 +142,7 @@ __global__ void prep_grid_setup_kernel(long long F, float h, long long max_cells
     if (kept <= 0) { header[2] = 2; return; }
     int n[3];
     for (int a = 0; a < 3; ++a) {
-        const float lo = prep_ord2f(box->lo[a]), hi = prep_ord2f(box->hi[a]);
+        const float lo = ord2f(box->lo[a]), hi = ord2f(box->hi[a]);
         header[6 + a] = __float_as_int(lo);
         header[9 + a] = __float_as_int(hi);
         const float t = floorf((hi - lo) / h);
@@ -373,7 +364,7 @@ __global__ __launch_bounds__(256) void prep_normalise_kernel(long long V, const 
 {
     float c[3];
     for (int a = 0; a < 3; ++a) {
-        const float lo = prep_ord2f(box->lo[a]), hi = prep_ord2f(box->hi[a]);
+        const float lo = ord2f(box->lo[a]), hi = ord2f(box->hi[a]);
         c[a] = a == 2 ? lo : (lo + hi) / 2.0f;
     }
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long long)gridDim.x * 256) {

@@ -38,7 +38,7 @@
 
 namespace sph3d {
 
-constexpr int kSceneMaxClasses = 64;
+constexpr int kSceneMaxClasses = kVoteMaxClasses;
 constexpr int kSceneParts = 64;             // workgroups of a merge launch (row-strided)
 constexpr int kNn1MinGrid = 64;             // fewer finite reference points: brute force
 constexpr int kNn1MinCells = 64;
@@ -60,15 +60,6 @@ static inline long long nn1_cell_cap(long long V)
     return c < kNn1MinCells ? kNn1MinCells : (c > kNn1MaxCells ? kNn1MaxCells : c);
 }
 
-__device__ __forceinline__ unsigned f2ord(float f)
-{
-    const unsigned u = (unsigned)__float_as_int(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned o)
-{
-    return __int_as_float((int)((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o));
-}
 __device__ __forceinline__ bool finite3(float x, float y, float z)
 {
     return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
@@ -138,19 +129,9 @@ __global__ __launch_bounds__(256) void scene_finalize_kernel(int C, long long V,
     long long mine = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long long)gridDim.x * 256) {
         int arg = 0;
-        if (hits[i] > 0) {
-            const float* v = merged + i * C;
-            float best = v[0];
-            for (int c = 1; c < C; ++c) {
-                const float x = v[c];
-                if (!isnan(best) && (x > best || isnan(x))) {
-                    best = x;
-                    arg = c;
-                }
-            }
-        } else {
-            ++mine;
-        }
+        bool finite;
+        if (hits[i] > 0) arg = vote_argmax(merged + i * C, 0, C, C, finite);
+        else ++mine;
         pred[i] = arg;
         if (voxel_label != nullptr) {
             const int lab = voxel_label[i];
@@ -431,11 +412,7 @@ extern "C" int sph3d_scene_merge(int B, int C, int num_blocks, long long total_r
                                  const float* votes, long long V, float* merged, int* hits, long long* counters,
                                  sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B > 0 && B <= 65535, "scene_merge: batch 0<B<=65535 required, got %d", B);
-    SPH3D_REQUIRE(C > 0 && C <= kSceneMaxClasses, "scene_merge: 0<C<=%d classes required, got %d", kSceneMaxClasses, C);
-    SPH3D_REQUIRE(num_blocks > 0 && total_rows > 0, "scene_merge: empty pool (num_blocks=%d total_rows=%lld)", num_blocks, total_rows);
-    SPH3D_REQUIRE(row_base >= 0 && batch_rows > 0 && batch_rows <= 0x7fffffffll && row_base + batch_rows <= total_rows,
-                  "scene_merge: rows [%lld, %lld + %lld) are not a range of the pool's %lld", row_base, row_base, batch_rows, total_rows);
+    if (int rc = vote_check_args("scene_merge", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
     SPH3D_REQUIRE(V > 0 && V <= 0x7fffffffll, "scene_merge: 0<V<2^31 scene rows required, got %lld", V);
     SPH3D_REQUIRE(rows != nullptr && offsets != nullptr && index != nullptr && block_ids != nullptr && votes != nullptr,
                   "scene_merge: null input pointer");

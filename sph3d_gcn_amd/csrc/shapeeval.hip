@@ -17,7 +17,6 @@
 
 namespace sph3d {
 
-constexpr int kShapeMaxClasses = 64;
 constexpr int kShapeParts = 8;                  // workgroups per shape (a ShapeNet shape has 2 000 - 3 000 rows)
 
 __global__ __launch_bounds__(256) void shape_iou_kernel(int C, int P, long long T, const float* __restrict__ rows,
@@ -28,8 +27,8 @@ __global__ __launch_bounds__(256) void shape_iou_kernel(int C, int P, long long 
                                                         int* __restrict__ gt_cnt, int* __restrict__ correct,
                                                         unsigned long long* __restrict__ nonfinite)
 {
-    __shared__ unsigned hist[3 * kShapeMaxClasses + 2];          // inter | pred_cnt | gt_cnt | correct, non-finite rows
-    for (int k = threadIdx.x; k < 3 * kShapeMaxClasses + 2; k += 256) hist[k] = 0u;
+    __shared__ unsigned hist[3 * kVoteMaxClasses + 2];          // inter | pred_cnt | gt_cnt | correct, non-finite rows
+    for (int k = threadIdx.x; k < 3 * kVoteMaxClasses + 2; k += 256) hist[k] = 0u;
     __syncthreads();
     const int b = blockIdx.y;
     long long lo;
@@ -39,40 +38,28 @@ __global__ __launch_bounds__(256) void shape_iou_kernel(int C, int P, long long 
     for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < n; r += (long long)gridDim.x * 256) {
         const long long row = lo - row_base + r;
         const float* v = votes + row * C;
-        bool finite = true;
-        for (int c = 0; c < plo; ++c) finite = finite && isfinite(v[c]);
-        float best = v[plo];
-        int arg = plo;
-        finite = finite && isfinite(best);
-        for (int c = plo + 1; c < plo + pn; ++c) {
-            const float x = v[c];
-            finite = finite && isfinite(x);
-            if (!isnan(best) && (x > best || isnan(x))) {
-                best = x;
-                arg = c;
-            }
-        }
-        for (int c = plo + pn; c < C; ++c) finite = finite && isfinite(v[c]);
+        bool finite;
+        const int arg = vote_argmax(v, plo, pn, C, finite);
         pred[row] = arg;
-        if (!finite) atomicAdd(&hist[3 * kShapeMaxClasses + 1], 1u);
+        if (!finite) atomicAdd(&hist[3 * kVoteMaxClasses + 1], 1u);
         const float lab = rows[(lo + r) * 8 + 6];
-        atomicAdd(&hist[kShapeMaxClasses + arg], 1u);
+        atomicAdd(&hist[kVoteMaxClasses + arg], 1u);
         if (lab >= (float)plo && lab < (float)(plo + pn) && lab == (float)(int)lab)
-            atomicAdd(&hist[2 * kShapeMaxClasses + (int)lab], 1u);
+            atomicAdd(&hist[2 * kVoteMaxClasses + (int)lab], 1u);
         if (lab == (float)arg) {
             atomicAdd(&hist[arg], 1u);
-            atomicAdd(&hist[3 * kShapeMaxClasses], 1u);
+            atomicAdd(&hist[3 * kVoteMaxClasses], 1u);
         }
     }
     __syncthreads();
     for (int k = threadIdx.x; k < 3 * C; k += 256) {
         const int which = k / C, l = k - which * C;
-        const unsigned h = hist[which * kShapeMaxClasses + l];
+        const unsigned h = hist[which * kVoteMaxClasses + l];
         if (h != 0u) atomicAdd((which == 0 ? inter : which == 1 ? pred_cnt : gt_cnt) + (long long)b * C + l, (int)h);
     }
     if (threadIdx.x == 0) {
-        if (hist[3 * kShapeMaxClasses] != 0u) atomicAdd(&correct[b], (int)hist[3 * kShapeMaxClasses]);
-        if (hist[3 * kShapeMaxClasses + 1] != 0u) atomicAdd(nonfinite, (unsigned long long)hist[3 * kShapeMaxClasses + 1]);
+        if (hist[3 * kVoteMaxClasses] != 0u) atomicAdd(&correct[b], (int)hist[3 * kVoteMaxClasses]);
+        if (hist[3 * kVoteMaxClasses + 1] != 0u) atomicAdd(nonfinite, (unsigned long long)hist[3 * kVoteMaxClasses + 1]);
     }
 }
 
@@ -85,11 +72,7 @@ extern "C" int sph3d_shape_iou(int B, int C, int num_blocks, long long total_row
                                const int* part_lo, const int* part_n, int* pred, int* inter, int* pred_cnt, int* gt_cnt,
                                int* correct, long long* nonfinite, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B > 0 && B <= 65535, "shape_iou: batch 0<B<=65535 required, got %d", B);
-    SPH3D_REQUIRE(C > 0 && C <= kShapeMaxClasses, "shape_iou: 0<C<=%d classes required, got %d", kShapeMaxClasses, C);
-    SPH3D_REQUIRE(num_blocks > 0 && total_rows > 0, "shape_iou: empty pool (num_blocks=%d total_rows=%lld)", num_blocks, total_rows);
-    SPH3D_REQUIRE(row_base >= 0 && batch_rows > 0 && batch_rows <= 0x7fffffffll && row_base + batch_rows <= total_rows,
-                  "shape_iou: rows [%lld, %lld + %lld) are not a range of the pool's %lld", row_base, row_base, batch_rows, total_rows);
+    if (int rc = vote_check_args("shape_iou", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
     SPH3D_REQUIRE(rows != nullptr && offsets != nullptr && shape_ids != nullptr && votes != nullptr && part_lo != nullptr &&
                       part_n != nullptr,
                   "shape_iou: null input pointer");

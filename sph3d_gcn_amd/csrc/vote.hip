@@ -22,7 +22,6 @@
 
 namespace sph3d {
 
-constexpr int kVoteMaxClasses = 64;
 constexpr int kVoteFinalizeParts = 64;          // workgroups per cloud in the row-strided kernels
 
 // inner_size[b] = rows of cloud b with inner == 1 (column 7 of the pool's rows)
@@ -114,17 +113,8 @@ __global__ __launch_bounds__(256) void vote_finalize_kernel(int C, int P, long l
     for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < n; r += (long long)gridDim.x * 256) {
         const long long row = lo - row_base + r;
         const float* v = votes + row * C;
-        float best = v[0];
-        int arg = 0;
-        bool finite = isfinite(best);
-        for (int c = 1; c < C; ++c) {
-            const float x = v[c];
-            finite = finite && isfinite(x);
-            if (!isnan(best) && (x > best || isnan(x))) {
-                best = x;
-                arg = c;
-            }
-        }
+        bool finite;
+        const int arg = vote_argmax(v, 0, C, C, finite);
         pred[row] = arg;
         if (!finite) atomicAdd(&bad, 1u);
         const float* src = rows + (lo + r) * 8;
@@ -135,16 +125,6 @@ __global__ __launch_bounds__(256) void vote_finalize_kernel(int C, int P, long l
     for (int k = threadIdx.x; k < C * C; k += 256)
         if (hist[k] != 0u) atomicAdd(&confusion[k], (unsigned long long)hist[k]);
     if (threadIdx.x == 0 && bad != 0u) atomicAdd(nonfinite, (unsigned long long)bad);
-}
-
-static int vote_common(const char* what, int B, int C, int num_blocks, long long total_rows, long long row_base, long long batch_rows)
-{
-    SPH3D_REQUIRE(B > 0 && B <= 65535, "%s: batch 0<B<=65535 required, got %d", what, B);
-    SPH3D_REQUIRE(C > 0 && C <= kVoteMaxClasses, "%s: 0<C<=%d classes required, got %d", what, kVoteMaxClasses, C);
-    SPH3D_REQUIRE(num_blocks > 0 && total_rows > 0, "%s: empty pool (num_blocks=%d total_rows=%lld)", what, num_blocks, total_rows);
-    SPH3D_REQUIRE(row_base >= 0 && batch_rows > 0 && batch_rows <= 0x7fffffffll && row_base + batch_rows <= total_rows,
-                  "%s: rows [%lld, %lld + %lld) are not a range of the pool's %lld", what, row_base, row_base, batch_rows, total_rows);
-    return SPH3D_OK;
 }
 
 }  // namespace sph3d
@@ -161,7 +141,7 @@ extern "C" int sph3d_vote_begin(int B, int C, int num_blocks, long long total_ro
                                 int* covered, int* inner_size, int* remaining, void* workspace, size_t workspace_bytes,
                                 sph3d_stream_t stream)
 {
-    if (int rc = vote_common("vote_begin", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
+    if (int rc = vote_check_args("vote_begin", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
     SPH3D_REQUIRE(rows != nullptr && offsets != nullptr && block_ids != nullptr, "vote_begin: null input pointer");
     SPH3D_REQUIRE(votes != nullptr && count != nullptr && covered != nullptr && inner_size != nullptr && remaining != nullptr,
                   "vote_begin: null output pointer");
@@ -187,7 +167,7 @@ extern "C" int sph3d_vote_accumulate(int B, int num_point, int C, int num_blocks
                                      int* covered, const int* inner_size, int* remaining, void* workspace, size_t workspace_bytes,
                                      sph3d_stream_t stream)
 {
-    if (int rc = vote_common("vote_accumulate", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
+    if (int rc = vote_check_args("vote_accumulate", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
     SPH3D_REQUIRE(num_point > 0, "vote_accumulate: num_point>0 required, got %d", num_point);
     SPH3D_REQUIRE(min_votes >= 1, "vote_accumulate: min_votes>=1 required, got %d", min_votes);
     SPH3D_REQUIRE(pass >= 0 && pass < (1 << 20), "vote_accumulate: pass in [0, 2^20) required, got %d", pass);
@@ -217,7 +197,7 @@ extern "C" int sph3d_vote_finalize(int B, int C, int num_blocks, long long total
                                    const int* block_ids, long long row_base, long long batch_rows, const float* votes, int* pred,
                                    long long* confusion, long long* nonfinite, sph3d_stream_t stream)
 {
-    if (int rc = vote_common("vote_finalize", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
+    if (int rc = vote_check_args("vote_finalize", B, C, num_blocks, total_rows, row_base, batch_rows)) return rc;
     SPH3D_REQUIRE(rows != nullptr && offsets != nullptr && block_ids != nullptr && votes != nullptr, "vote_finalize: null input pointer");
     SPH3D_REQUIRE(pred != nullptr && confusion != nullptr && nonfinite != nullptr, "vote_finalize: null output pointer");
     SPH3D_REQUIRE((reinterpret_cast<size_t>(confusion) & 7) == 0 && (reinterpret_cast<size_t>(nonfinite) & 7) == 0,

@@ -87,6 +87,29 @@ def _check_loop_args(num_point, num_cls, min_votes, max_passes):
         raise ValueError("0<max_passes<2^%d required" % PASS_BITS)
 
 
+def check_share(batch_size, rank, world, what):
+    """the arguments that say which share of an evaluation a rank takes"""
+    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+        raise ValueError("%s: bad batch_size / rank / world" % what)
+
+
+def merge_order(results, keys="batches", what="batch", kept="votes"):
+    """What the `merge` of the ranks' results has in common.  `keys` names the attribute that lists what a result evaluated
+    (batch or scene numbers), `kept` the dict it may have kept per key.  -> (results as a list,
+    pick: name -> that per-key attribute of all results in ascending key order — position (key, rank, position) —,
+    the `kept` dicts joined, None unless every result has one).  A key that occurs twice is refused."""
+    results = list(results)
+    if not results:
+        raise ValueError("merge: no results")
+    rows = sorted((k, r, i) for r, res in enumerate(results) for i, k in enumerate(getattr(res, keys)))
+    if len(set(k for k, _, _ in rows)) != len(rows):
+        raise ValueError("merge: a %s occurs in two results" % what)
+    joined = None
+    if all(getattr(res, kept) is not None for res in results):
+        joined = {k: v for res in results for k, v in getattr(res, kept).items()}
+    return results, (lambda name: [getattr(results[r], name)[i] for _, r, i in rows]), joined
+
+
 BatchVotes = collections.namedtuple("BatchVotes", "votes count pred passes covered inner_size confusion complete nonfinite_rows")
 
 
@@ -174,18 +197,9 @@ class EvalResult:
     @classmethod
     def merge(cls, results):
         """the result of the ranks' shares together: equal to the world = 1 result"""
-        results = list(results)
-        if not results:
-            raise ValueError("merge: no results")
-        rows = sorted((b, r, i) for r, res in enumerate(results) for i, b in enumerate(res.batches))
-        if len(set(b for b, _, _ in rows)) != len(rows):
-            raise ValueError("merge: a batch occurs in two results")
-        votes = None
-        if all(res.votes is not None for res in results):
-            votes = {b: v for res in results for b, v in res.votes.items()}
-        return cls(sum(res.confusion for res in results), [b for b, _, _ in rows],
-                   [results[r].passes[i] for _, r, i in rows], [results[r].covered[i] for _, r, i in rows],
-                   [results[r].inner_size[i] for _, r, i in rows], sum(res.nonfinite_rows for res in results), votes)
+        results, pick, votes = merge_order(results)
+        return cls(sum(res.confusion for res in results), pick("batches"), pick("passes"), pick("covered"), pick("inner_size"),
+                   sum(res.nonfinite_rows for res in results), votes)
 
 
 def batch_blocks(num_blocks, batch_size, batch_index):
@@ -197,8 +211,7 @@ def evaluate_reference(logits_fn, sizes, rows_label, rows_inner, batch_size, num
                        max_passes=MAX_PASSES, rank=0, world=1, keep_votes=False):
     """`evaluate` stated in numpy: vote_reference over the batches of rank `rank`;
     logits_fn(batch_index, pass, index [b, N]) -> [b, N, C] float32"""
-    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
-        raise ValueError("evaluate_reference: bad batch_size / rank / world")
+    check_share(batch_size, rank, world, "evaluate_reference")
     P, C = len(sizes), int(num_cls)
     mine = list(range(rank, feed.batches_per_epoch(P, batch_size), world))
     done = [vote_reference(sizes, rows_label, rows_inner, batch_blocks(P, batch_size, i), num_point, seed, i,
@@ -214,14 +227,19 @@ def evaluate_reference(logits_fn, sizes, rows_label, rows_inner, batch_size, num
 class Voter:
     """The device buffers of one evaluation — vote sums [capacity_rows, C] fp32, counts, predictions, stamps, the feed's output
     set, the confusion matrix — allocated once and reused by every batch, and the pass loop of one batch.  A batch's blocks
-    must lie inside `capacity_rows` consecutive rows of the pool (evaluate sizes it to its largest batch)."""
+    must lie inside `capacity_rows` consecutive rows of the pool (evaluate sizes it to its largest batch).
+
+    The loop is stated here once; shapeeval.ShapeVoter runs the same one.  What a subclass may replace: `_alloc` (the output set
+    and what the closing kernel writes), `_open` (per batch, before anything is launched), `_pass` (what one pass draws and
+    feeds to model_fn), `_close` and `_empty` (how a finished batch, or one without rows, becomes a result)."""
+    what = "blocks"
 
     def __init__(self, pool, batch_size, num_point, num_cls, capacity_rows, min_votes=1):
         import torch
         from .. import _lib
         _check_loop_args(num_point, num_cls, min_votes, 1)
         if batch_size <= 0 or capacity_rows <= 0:
-            raise ValueError("Voter: batch_size>0 and capacity_rows>0 required")
+            raise ValueError("%s: batch_size>0 and capacity_rows>0 required" % type(self).__name__)
         self.pool, self.B, self.N, self.C = pool, int(batch_size), int(num_point), int(num_cls)
         self.cap, self.min_votes = int(capacity_rows), int(min_votes)
         dev = pool.device
@@ -232,87 +250,115 @@ class Voter:
         self.ws = torch.empty((self.ws_bytes,), dtype=torch.uint8, device=dev)
         self.state = torch.zeros((2 * self.B + 1,), dtype=torch.int32, device=dev)        # covered | inner_size | remaining
         self.covered, self.inner_size, self.remaining = self.state[:self.B], self.state[self.B:2 * self.B], self.state[2 * self.B:]
-        self.confusion = torch.zeros((self.C * self.C,), dtype=torch.int64, device=dev)
         self.nonfinite = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self._alloc(dev)
+
+    def _alloc(self, dev):
+        import torch
+        self.confusion = torch.zeros((self.C * self.C,), dtype=torch.int64, device=dev)
         self.out = (torch.empty((self.B, self.N, 6), dtype=torch.float32, device=dev),
                     torch.empty((self.B, self.N), dtype=torch.int32, device=dev),
                     torch.empty((self.B, self.N), dtype=torch.int32, device=dev))
 
-    def _range(self, block_ids):
+    def row_range(self, block_ids):
         """-> (row_base, batch_rows) of the batch's blocks in the pool's rows, None if none of them is in the pool"""
         ids = [int(i) for i in block_ids if 0 <= int(i) < len(self.pool)]
         if len(set(ids)) != len(ids):
-            raise ValueError("the blocks of a batch are distinct")
+            raise ValueError("the %s of a batch are distinct" % self.what)
         if not ids:
             return None
         lo = min(int(self.pool.host_offsets[i]) for i in ids)
         hi = max(int(self.pool.host_offsets[i + 1]) for i in ids)
         if hi - lo > self.cap:
-            raise ValueError("the batch's blocks span %d rows of the pool, the buffers hold %d" % (hi - lo, self.cap))
+            raise ValueError("the batch's %s span %d rows of the pool, the buffers hold %d" % (self.what, hi - lo, self.cap))
         return lo, hi - lo
 
+    def _open(self, block_ids):
+        """per batch, before anything is launched"""
+
+    def _pass(self, model_fn, ids_dev, out, seed, batch_index, p, vote):
+        """pass p of a batch: one sample without augmentation, voted as pass p"""
+        points, label, inner, index = feed.assemble(self.pool.rows, self.pool.offsets, ids_dev, self.N, seed, pass_step(batch_index, p),
+                                                    augment=False, out=out, want_index=True)
+        vote(p, index, lambda: model_fn(points, label, inner))
+
+    def _empty(self, b):
+        return BatchVotes(None, None, None, 0, np.zeros((b,), np.int32), np.zeros((b,), np.int32), None, True, 0)
+
+    def _close(self, block_ids, common, passes, keep_votes):
+        """the batch's predictions and confusion counts (added to self.confusion / self.nonfinite) -> BatchVotes; confusion is
+        None (the matrix is accumulated on the device)"""
+        from .. import _lib
+        before = int(self.nonfinite.item()) if keep_votes else 0
+        _lib.check(_lib.lib().sph3d_vote_finalize(len(block_ids), self.C, *common, _lib.ptr(self.votes), _lib.ptr(self.pred),
+                                                  _lib.ptr(self.confusion), _lib.ptr(self.nonfinite), _lib.stream_ptr()))
+        covered, inner_size = self._coverage(len(block_ids))
+        votes, count, pred = self._kept(block_ids, common, keep_votes)
+        nonfinite = int(self.nonfinite.item()) - before if keep_votes else 0
+        return BatchVotes(votes, count, pred, passes, covered, inner_size, None, bool((covered >= inner_size).all()), nonfinite)
+
+    def _coverage(self, b):
+        """-> covered, inner_size [b] of the batch (host)"""
+        state = self.state.cpu().numpy()
+        return state[:b].copy(), state[self.B:self.B + b].copy()
+
+    def _kept(self, block_ids, common, keep_votes):
+        """-> the batch's sums, counts and predictions as per-block host arrays with keep_votes, else None three times"""
+        if not keep_votes:
+            return None, None, None
+        P, base, nrows, offsets = common[0], common[5], common[6], self.pool.host_offsets
+        hv, hc, hp = self.votes[:nrows].cpu().numpy(), self.count[:nrows].cpu().numpy(), self.pred[:nrows].cpu().numpy()
+        votes, count, pred = [], [], []
+        for i in block_ids:
+            lo, hi = (int(offsets[i]) - base, int(offsets[i + 1]) - base) if 0 <= i < P else (0, 0)
+            votes.append(hv[lo:hi].copy())
+            count.append(hc[lo:hi].copy())
+            pred.append(hp[lo:hi].copy())
+        return votes, count, pred
+
     def run_batch(self, model_fn, block_ids, seed, batch_index, max_passes=MAX_PASSES, keep_votes=False, on_pass=None):
-        """all passes of one batch, then its predictions and confusion counts (added to self.confusion / self.nonfinite).
-        -> BatchVotes; votes / count / pred are per-block host arrays with keep_votes, else None, and confusion is None (the
-        matrix is accumulated on the device)"""
+        """all passes of one batch, then what `_close` makes of it; votes / count / pred of the result are per-block host arrays
+        with keep_votes, else None"""
         import torch
         from .. import _lib
         _check_loop_args(self.N, self.C, self.min_votes, max_passes)
         block_ids = np.ascontiguousarray(np.asarray(block_ids).reshape(-1), dtype=np.int32)
         b = int(block_ids.shape[0])
         if not 0 < b <= self.B:
-            raise ValueError("a batch has 1..%d blocks, got %d" % (self.B, b))
+            raise ValueError("a batch has 1..%d %s, got %d" % (self.B, self.what, b))
         if batch_index < 0 or batch_index >= 1 << (63 - PASS_BITS):
             raise ValueError("batch_index out of range")
-        rng = self._range(block_ids)
-        empty = BatchVotes(None, None, None, 0, np.zeros((b,), np.int32), np.zeros((b,), np.int32), None, True, 0)
+        self._open(block_ids)
+        rng = self.row_range(block_ids)
         if rng is None:
-            return empty
-        base, nrows = rng
+            return self._empty(b)
         p, l = self.pool, _lib.lib()
-        P, T = len(p), int(p.rows.shape[0])
         ids_dev = torch.from_numpy(block_ids).to(p.device)
-        stream = _lib.stream_ptr()
-        common = (P, T, _lib.ptr(p.rows), _lib.ptr(p.offsets), _lib.ptr(ids_dev), base, nrows)
-        _lib.check(l.sph3d_vote_begin(b, self.C, *common, _lib.ptr(self.votes), _lib.ptr(self.count), _lib.ptr(self.covered),
-                                      _lib.ptr(self.inner_size), _lib.ptr(self.remaining), _lib.ptr(self.ws), self.ws_bytes, stream))
-        out = tuple(t[:b] for t in self.out)
-        passes = 0
-        remaining = int(self.remaining.item())
-        while remaining > 0 and passes < max_passes:
-            points, label, inner, index = feed.assemble(p.rows, p.offsets, ids_dev, self.N, seed, pass_step(batch_index, passes),
-                                                        augment=False, out=out, want_index=True)
+        common = (len(p), int(p.rows.shape[0]), _lib.ptr(p.rows), _lib.ptr(p.offsets), _lib.ptr(ids_dev)) + rng
+        bufs = (_lib.ptr(self.votes), _lib.ptr(self.count), _lib.ptr(self.covered), _lib.ptr(self.inner_size),
+                _lib.ptr(self.remaining), _lib.ptr(self.ws), self.ws_bytes)
+        _lib.check(l.sph3d_vote_begin(b, self.C, *common, *bufs, _lib.stream_ptr()))
+
+        def vote(q, index, call):
             with torch.no_grad():
-                logits = model_fn(points, label, inner)
+                logits = call()
             _lib.require_device(logits)
             if tuple(logits.shape) != (b, self.N, self.C):
                 raise ValueError("model_fn: logits [%d, %d, %d] expected, got %s" % (b, self.N, self.C, tuple(logits.shape)))
             logits = _lib.f32(logits.detach())
             if on_pass is not None:
-                on_pass(batch_index, passes, index, logits)
-            _lib.check(l.sph3d_vote_accumulate(b, self.N, self.C, *common, passes, _lib.ptr(index), _lib.ptr(logits), self.min_votes,
-                                               _lib.ptr(self.votes), _lib.ptr(self.count), _lib.ptr(self.covered),
-                                               _lib.ptr(self.inner_size), _lib.ptr(self.remaining), _lib.ptr(self.ws), self.ws_bytes,
-                                               _lib.stream_ptr()))
+                on_pass(batch_index, q, index, logits)
+            _lib.check(l.sph3d_vote_accumulate(b, self.N, self.C, *common, q, _lib.ptr(index), _lib.ptr(logits), self.min_votes,
+                                               *bufs, _lib.stream_ptr()))
+
+        out = tuple(t[:b] for t in self.out)
+        passes = 0
+        remaining = int(self.remaining.item())
+        while remaining > 0 and passes < max_passes:
+            self._pass(model_fn, ids_dev, out, seed, batch_index, passes, vote)
             remaining = int(self.remaining.item())               # the loop's one word per pass: a host synchronisation
             passes += 1
-        before = int(self.nonfinite.item()) if keep_votes else 0
-        _lib.check(l.sph3d_vote_finalize(b, self.C, *common, _lib.ptr(self.votes), _lib.ptr(self.pred), _lib.ptr(self.confusion),
-                                         _lib.ptr(self.nonfinite), _lib.stream_ptr()))
-        state = self.state.cpu().numpy()
-        covered, inner_size = state[:b].copy(), state[self.B:self.B + b].copy()
-        votes = count = pred = None
-        nonfinite = 0
-        if keep_votes:
-            hv, hc, hp = self.votes[:nrows].cpu().numpy(), self.count[:nrows].cpu().numpy(), self.pred[:nrows].cpu().numpy()
-            nonfinite = int(self.nonfinite.item()) - before
-            votes, count, pred = [], [], []
-            for i in block_ids:
-                lo, hi = (int(p.host_offsets[i]) - base, int(p.host_offsets[i + 1]) - base) if 0 <= i < P else (0, 0)
-                votes.append(hv[lo:hi].copy())
-                count.append(hc[lo:hi].copy())
-                pred.append(hp[lo:hi].copy())
-        return BatchVotes(votes, count, pred, passes, covered, inner_size, None, bool((covered >= inner_size).all()), nonfinite)
+        return self._close(block_ids, common, passes, keep_votes)
 
     def totals(self):
         """-> confusion [C, C] int64 and the non-finite rows counted so far (host)"""
@@ -335,8 +381,7 @@ def evaluate(model_fn, pool, batch_size, num_point, seed, num_cls=13, min_votes=
     on_pass(batch_index, pass, index, logits): a hook that sees each pass's device tensors before they are voted.
     keep_votes: the finished batches' sums, counts and predictions are copied to the host (result.votes)."""
     _check_loop_args(num_point, num_cls, min_votes, max_passes)
-    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
-        raise ValueError("evaluate: bad batch_size / rank / world")
+    check_share(batch_size, rank, world, "evaluate")
     mine = list(range(rank, feed.batches_per_epoch(len(pool), batch_size), world))
     C = int(num_cls)
     if not mine:

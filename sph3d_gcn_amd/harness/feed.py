@@ -239,32 +239,44 @@ def epoch_plan(num_blocks, batch_size, seed, epoch, rank=0, world=1):
 # ---------------------------------------------------------------------------------------------------------------
 # the device side
 # ---------------------------------------------------------------------------------------------------------------
+def assemble_args(_lib, rows, offsets, ids, ids_name, num_point, out, channels, want_index):
+    """what feed.assemble and objfeed.assemble do before they launch: the checks of the pool's tensors and the ids, and the
+    outputs.  channels: per output its shape after [B, N]; the first output is fp32, the others int32.  `out` is checked
+    against that, or allocated where it is None; index is a new int32 [B, N] with want_index, else None.
+    -> B, N, out, index.  (`_lib` is the caller's: importing it here again would cost every call 0.8 us on the host, as much
+    as all the checks together.)"""
+    import torch
+    _lib.require_device(rows, offsets, ids)
+    if rows.dtype != torch.float32 or offsets.dtype != torch.int64 or ids.dtype != torch.int32:
+        raise TypeError("assemble: rows fp32, offsets int64, %s int32" % ids_name)
+    if rows.dim() != 2 or rows.shape[1] != 8 or not (rows.is_contiguous() and offsets.is_contiguous() and ids.is_contiguous()):
+        raise ValueError("assemble: rows must be a contiguous [T, 8], offsets and %s contiguous" % ids_name)
+    B, N, dev = int(ids.shape[0]), int(num_point), rows.device
+    if out is None:
+        out = tuple(torch.empty((B, N) + c, dtype=torch.int32 if k else torch.float32, device=dev) for k, c in enumerate(channels))
+    bn, dt = (B, N), torch.float32
+    for t, c in zip(out, channels):                   # (an `out` of another length fails where the caller unpacks it)
+        if t.shape != bn + c or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError("assemble: output of the wrong shape, type, layout or device")
+        dt = torch.int32
+    return B, N, out, torch.empty((B, N), dtype=torch.int32, device=dev) if want_index else None
+
+
 def assemble(rows, offsets, block_ids, num_point, seed, step, augment=True, out=None, want_index=False):
     """sph3d_feed_assemble on torch's current stream.  rows [T, 8] fp32, offsets [P+1] int64, block_ids [B] int32, all on the
     device.  out: (points [B, N, 6] fp32, label [B, N] i32, inner [B, N] i32) to write into, else new tensors.
     -> points, label, inner (and index [B, N] i32 with want_index)"""
-    import torch
     from .. import _lib
-    _lib.require_device(rows, offsets, block_ids)
-    if rows.dtype != torch.float32 or offsets.dtype != torch.int64 or block_ids.dtype != torch.int32:
-        raise TypeError("assemble: rows fp32, offsets int64, block_ids int32")
-    if rows.dim() != 2 or rows.shape[1] != 8 or not (rows.is_contiguous() and offsets.is_contiguous() and block_ids.is_contiguous()):
-        raise ValueError("assemble: rows must be a contiguous [T, 8], offsets and block_ids contiguous")
-    B, N = int(block_ids.shape[0]), int(num_point)
-    if out is None:
-        out = (torch.empty((B, N, 6), dtype=torch.float32, device=rows.device),
-               torch.empty((B, N), dtype=torch.int32, device=rows.device),
-               torch.empty((B, N), dtype=torch.int32, device=rows.device))
-    points, label, inner = out
-    for t, shape, dt in ((points, (B, N, 6), torch.float32), (label, (B, N), torch.int32), (inner, (B, N), torch.int32)):
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != rows.device:
-            raise ValueError("assemble: output of the wrong shape, type, layout or device")
-    index = torch.empty((B, N), dtype=torch.int32, device=rows.device) if want_index else None
+    B, N, (points, label, inner), index = assemble_args(_lib, rows, offsets, block_ids, "block_ids", num_point, out, _FEED_OUT,
+                                                        want_index)
     _lib.check(_lib.lib().sph3d_feed_assemble(B, N, int(offsets.shape[0]) - 1, int(rows.shape[0]), _lib.ptr(rows), _lib.ptr(offsets),
                                               _lib.ptr(block_ids), seed & 0xffffffffffffffff, step & 0xffffffffffffffff,
                                               1 if augment else 0, _lib.ptr(points), _lib.ptr(label), _lib.ptr(inner),
                                               _lib.ptr(index), _lib.stream_ptr()))
     return (points, label, inner, index) if want_index else (points, label, inner)
+
+
+_FEED_OUT = ((6,), (), ())          # the shapes after [B, N] of points (fp32), label and inner (int32)
 
 
 def check_scene_index(blocks, index, scene_of_block):
@@ -375,21 +387,16 @@ class BlockPool:
         return int(self.sizes.shape[0])
 
 
-class DeviceFeed:
-    """One epoch of training batches per iteration, assembled on the device.
+class TwoSetFeed:
+    """The protocol DeviceFeed and harness/objfeed.py's ObjectFeed share: one epoch of batches per iteration, assembled on the
+    feed's own stream into two alternating output sets.  A subclass says how a set is allocated (`_new_set`), what is launched
+    for one batch (`_launch`) and, if anything, what an epoch uploads besides its table (`_begin_epoch`).
 
-        feed = DeviceFeed(pool, 16, 8192, seed=1)
-        for points, label, inner, ready in feed:                 # epoch 0; the next `for` is epoch 1
-            pred, _ = model(points, is_training=True, points_ready=ready)
-            loss = model.loss(pred, label, inner)
-            feed.done(ready)                                     # the batch's last reader is issued (see below)
-            ...                                                  # backward, optimiser
-
-    The epoch's block order is one host permutation from (seed, epoch), identical on every rank; rank r takes batches
-    r, r + world, ...; the last batch may be smaller.  The kernel runs on the feed's own stream (`stream`, else one the feed
-    creates); `ready` is recorded behind it: hand it to the model as `points_ready`, or `wait_event` it on the consuming stream
-    (label and inner are consumed by the loss on the main stream: it must wait too — the model's plan does that for the
-    streams it uses when it gets `points_ready`, see s3dis_net.GraphPlan).
+    The epoch's order is one host permutation from (seed, epoch), identical on every rank; rank r takes batches r, r + world,
+    ...; the last batch may be smaller.  The kernel runs on the feed's own stream (`stream`, else one the feed creates);
+    `ready`, the last element of an item, is recorded behind it: hand it to the model as `points_ready`, or `wait_event` it on
+    the consuming stream (the labels are consumed by the loss on the main stream: it must wait too — the model's plan does
+    that for the streams it uses when it gets `points_ready`, see s3dis_net.GraphPlan).
 
     OWNERSHIP.  The tensors of an item are views of one of TWO preallocated output sets used alternately (no per-step
     allocation crosses streams), so item i is overwritten by item i+2: the consumer must have ISSUED all its work on item i
@@ -399,25 +406,29 @@ class DeviceFeed:
     second form is safe and slow: item i+2 is then assembled behind ALL of step i+1, so the plan of step i+2 no longer overlaps
     the step before it (+20 % per step); hand the event back, as early as the last reader of the batch."""
 
-    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None):
+    def __init__(self, pool, batch_size, num_point, seed, rank=0, world=1, stream=None):
         import torch
         if batch_size <= 0 or num_point <= 0:
-            raise ValueError("DeviceFeed: batch_size>0 and num_point>0 required")
+            raise ValueError("%s: batch_size>0 and num_point>0 required" % type(self).__name__)
         if world <= 0 or not 0 <= rank < world:
-            raise ValueError("DeviceFeed: bad rank / world")
+            raise ValueError("%s: bad rank / world" % type(self).__name__)
         self.pool, self.batch_size, self.num_point, self.seed = pool, int(batch_size), int(num_point), int(seed)
-        self.augment, self.rank, self.world = bool(augment), int(rank), int(world)
-        self.epoch = 0
-        dev = pool.device
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
-        self._sets = []
-        for _ in range(2):
-            self._sets.append({
-                "out": (torch.empty((self.batch_size, self.num_point, 6), dtype=torch.float32, device=dev),
-                        torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev),
-                        torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev)),
-                "ready": torch.cuda.Event(), "released": None, "used": False})
+        self.rank, self.world, self.epoch = int(rank), int(world), 0
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=pool.device)
+        self._sets = [{"out": self._new_set(pool.device), "ready": torch.cuda.Event(), "released": None, "used": False}
+                      for _ in range(2)]
         self._turn = 0
+
+    def _new_set(self, dev):
+        """-> the tensors of one output set, each with batch_size leading rows"""
+        raise NotImplementedError
+
+    def _launch(self, step, ids_dev, out):
+        """fill `out` (a set cut to the batch's size) with the batch of ids_dev; torch's current stream is the feed's"""
+        raise NotImplementedError
+
+    def _begin_epoch(self, plan):
+        """what an epoch uploads besides its table; torch's current stream is the feed's"""
 
     def __len__(self):
         """batches of this rank per epoch"""
@@ -448,7 +459,7 @@ class DeviceFeed:
         s["released"], s["used"] = None, True
         out = tuple(t[:b] for t in s["out"])
         with torch.cuda.stream(self.stream):
-            assemble(self.pool.rows, self.pool.offsets, ids_dev, self.num_point, self.seed, step, self.augment, out=out)
+            self._launch(step, ids_dev, out)
             s["ready"].record(self.stream)
         return out + (s["ready"],)
 
@@ -458,12 +469,39 @@ class DeviceFeed:
         self.epoch += 1
         if not plan:
             return
-        # the block ids of the whole epoch go up in one copy (a row per batch, the last one padded): no host copy per step
+        # the ids of the whole epoch go up in one copy (a row per batch, the last one padded): no host copy per step
         table = np.zeros((len(plan), self.batch_size), dtype=np.int32)
         for i, (_step, ids) in enumerate(plan):
             table[i, :len(ids)] = ids
         self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))      # (the pool's upload, a previous epoch's table)
         with torch.cuda.stream(self.stream):
             table_dev = torch.from_numpy(table).to(self.pool.device)
+            self._begin_epoch(plan)
         for i, (step, ids) in enumerate(plan):
             yield self._assemble(step, table_dev[i, :len(ids)], len(ids))
+
+
+class DeviceFeed(TwoSetFeed):
+    """One epoch of S3DIS training batches per iteration, assembled on the device (TwoSetFeed states the protocol and who owns
+    an item's tensors).
+
+        feed = DeviceFeed(pool, 16, 8192, seed=1)
+        for points, label, inner, ready in feed:                 # epoch 0; the next `for` is epoch 1
+            pred, _ = model(points, is_training=True, points_ready=ready)
+            loss = model.loss(pred, label, inner)
+            feed.done(ready)                                     # the batch's last reader is issued
+            ...                                                  # backward, optimiser
+    """
+
+    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None):
+        self.augment = bool(augment)
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
+
+    def _new_set(self, dev):
+        import torch
+        return (torch.empty((self.batch_size, self.num_point, 6), dtype=torch.float32, device=dev),
+                torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev),
+                torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev))
+
+    def _launch(self, step, ids_dev, out):
+        assemble(self.pool.rows, self.pool.offsets, ids_dev, self.num_point, self.seed, step, self.augment, out=out)

@@ -11,7 +11,7 @@ include/sph3d.h: sph3d_objfeed_assemble).
     draws the same sample twice, once plain and once augmented.  The kernel's integer outputs equal this statement bit for
     bit; what it computes in fp32 is held to the project's 1e-5 bound against the float64 evaluation of ``apply_reference``;
   * ``train_recipe`` / ``EVAL_AUGMENT``: the reference's recipes as per-cloud bit masks;
-  * ``assemble``: the C entry;  ``ObjectFeed``: one epoch of batches on the feed's own stream, ``DeviceFeed``'s protocol.
+  * ``assemble``: the C entry;  ``ObjectFeed``: one epoch of batches on the feed's own stream (``feed.TwoSetFeed``).
 
 A recipe is a bit mask per cloud, applied in the reference's order (utils/data_util.py:47-61,140-204):
 TURN (Rz of a uniform angle, purpose 3), TILT (Rz Ry Rx of three clipped normal angles, purpose 4), SCALE
@@ -229,26 +229,14 @@ def assemble(rows, offsets, shape_ids, num_point, seed, step, recipe, out=None, 
     -> points, label (and index [B, N] i32 with want_index)"""
     import torch
     from .. import _lib
-    _lib.require_device(rows, offsets, shape_ids)
-    if rows.dtype != torch.float32 or offsets.dtype != torch.int64 or shape_ids.dtype != torch.int32:
-        raise TypeError("assemble: rows fp32, offsets int64, shape_ids int32")
-    if rows.dim() != 2 or rows.shape[1] != 8 or not (rows.is_contiguous() and offsets.is_contiguous() and shape_ids.is_contiguous()):
-        raise ValueError("assemble: rows must be a contiguous [T, 8], offsets and shape_ids contiguous")
-    B, N = int(shape_ids.shape[0]), int(num_point)
+    B, N, (points, label), index = feed.assemble_args(_lib, rows, offsets, shape_ids, "shape_ids", num_point, out, _OBJ_OUT,
+                                                      want_index)
     if torch.is_tensor(recipe):
         _lib.require_device(recipe)
         if recipe.dtype != torch.int32 or tuple(recipe.shape) != (B,) or not recipe.is_contiguous():
             raise ValueError("assemble: a device recipe is a contiguous int32 [B]")
     else:
         recipe = torch.from_numpy(check_recipe(recipe, B)).to(rows.device)
-    if out is None:
-        out = (torch.empty((B, N, 3), dtype=torch.float32, device=rows.device),
-               torch.empty((B, N), dtype=torch.int32, device=rows.device))
-    points, label = out
-    for t, shape, dt in ((points, (B, N, 3), torch.float32), (label, (B, N), torch.int32)):
-        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != rows.device:
-            raise ValueError("assemble: output of the wrong shape, type, layout or device")
-    index = torch.empty((B, N), dtype=torch.int32, device=rows.device) if want_index else None
     _lib.check(_lib.lib().sph3d_objfeed_assemble(B, N, int(offsets.shape[0]) - 1, int(rows.shape[0]), _lib.ptr(rows),
                                                  _lib.ptr(offsets), _lib.ptr(shape_ids), seed & 0xffffffffffffffff,
                                                  step & 0xffffffffffffffff, _lib.ptr(recipe), _lib.ptr(points), _lib.ptr(label),
@@ -256,8 +244,12 @@ def assemble(rows, offsets, shape_ids, num_point, seed, step, recipe, out=None, 
     return (points, label, index) if want_index else (points, label)
 
 
-class ObjectFeed:
-    """One epoch of training batches per iteration, assembled on the device.
+_OBJ_OUT = ((3,), ())               # the shapes after [B, N] of points (fp32) and label (int32)
+
+
+class ObjectFeed(feed.TwoSetFeed):
+    """One epoch of training batches of an object dataset per iteration, assembled on the device (feed.TwoSetFeed states the
+    protocol and who owns an item's tensors).
 
         feed = ObjectFeed(pool, 32, 2048, seed=1, dataset="shapenet")
         for points, label, category, ready in feed:              # epoch 0; the next `for` is epoch 1
@@ -266,83 +258,30 @@ class ObjectFeed:
             feed.done(ready)
             ...
 
-    Built on feed.epoch_plan (one host permutation per epoch from (seed, epoch), rank r takes batches r, r + world, ...; the
-    last batch may be smaller and gets train_recipe of its own size) with DeviceFeed's protocol: the kernel runs on the feed's own
-    stream, `ready` is recorded behind it, and the tensors of an item are views of one of TWO preallocated output sets used
-    alternately — see feed.DeviceFeed's OWNERSHIP paragraph, which holds here word for word (`done(ready[, event])`).
-    label is [b, N] int32 (ModelNet: the class repeated on every point); category [b] int32 is gathered from the pool on the
-    same stream.  `recipe`: a mask for every cloud instead of the dataset's training recipe (0: no augmentation)."""
+    The last, smaller batch gets train_recipe of its own size.  label is [b, N] int32 (ModelNet: the class repeated on every
+    point); category [b] int32 is gathered from the pool on the same stream.  `recipe`: a mask for every cloud instead of the
+    dataset's training recipe (0: no augmentation)."""
 
     def __init__(self, pool, batch_size, num_point, seed, dataset="shapenet", recipe=None, rank=0, world=1, stream=None):
-        import torch
-        if batch_size <= 0 or num_point <= 0:
-            raise ValueError("ObjectFeed: batch_size>0 and num_point>0 required")
-        if world <= 0 or not 0 <= rank < world:
-            raise ValueError("ObjectFeed: bad rank / world")
-        self.pool, self.batch_size, self.num_point, self.seed = pool, int(batch_size), int(num_point), int(seed)
-        self.rank, self.world, self.epoch = int(rank), int(world), 0
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
         self._recipe = (lambda b: train_recipe(b, dataset)) if recipe is None else (lambda b: check_recipe(int(recipe), b))
         self._recipe(self.batch_size)                       # (a bad dataset name or mask fails here, not in the first epoch)
-        dev = pool.device
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
         self._recipes = {}
-        self._sets = []
-        for _ in range(2):
-            self._sets.append({
-                "out": (torch.empty((self.batch_size, self.num_point, 3), dtype=torch.float32, device=dev),
-                        torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev),
-                        torch.empty((self.batch_size,), dtype=torch.int32, device=dev)),
-                "ready": torch.cuda.Event(), "released": None, "used": False})
-        self._turn = 0
 
-    def __len__(self):
-        """batches of this rank per epoch"""
-        return len(range(self.rank, feed.batches_per_epoch(len(self.pool), self.batch_size), self.world))
-
-    def done(self, ready, event=None):
-        """the consumer is finished with the item whose event is `ready`: after `event` (default: one recorded now on the current
-        stream) its set may be overwritten"""
+    def _new_set(self, dev):
         import torch
-        for s in self._sets:
-            if s["ready"] is ready:
-                if event is None:
-                    event = torch.cuda.Event()
-                    event.record()
-                s["released"] = event
-                return
-        raise ValueError("done(): not the ready event of a live item")
+        return (torch.empty((self.batch_size, self.num_point, 3), dtype=torch.float32, device=dev),
+                torch.empty((self.batch_size, self.num_point), dtype=torch.int32, device=dev),
+                torch.empty((self.batch_size,), dtype=torch.int32, device=dev))
 
-    def _assemble(self, step, ids_dev, b):
+    def _begin_epoch(self, plan):
         import torch
-        s = self._sets[self._turn]
-        self._turn ^= 1
-        if s["used"]:
-            if s["released"] is not None:
-                self.stream.wait_event(s["released"])
-            else:
-                self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))
-        s["released"], s["used"] = None, True
-        points, label, category = (t[:b] for t in s["out"])
-        with torch.cuda.stream(self.stream):
-            assemble(self.pool.rows, self.pool.offsets, ids_dev, self.num_point, self.seed, step, self._recipes[b], out=(points, label))
-            torch.index_select(self.pool.category_dev, 0, ids_dev, out=category)
-            s["ready"].record(self.stream)
-        return points, label, category, s["ready"]
+        for b in set(len(ids) for _step, ids in plan) - set(self._recipes):
+            self._recipes[b] = torch.from_numpy(self._recipe(b)).to(self.pool.device)
 
-    def __iter__(self):
+    def _launch(self, step, ids_dev, out):
         import torch
-        plan = feed.epoch_plan(len(self.pool), self.batch_size, self.seed, self.epoch, self.rank, self.world)
-        self.epoch += 1
-        if not plan:
-            return
-        # the shape ids of the whole epoch go up in one copy (a row per batch, the last one padded): no host copy per step
-        table = np.zeros((len(plan), self.batch_size), dtype=np.int32)
-        for i, (_step, ids) in enumerate(plan):
-            table[i, :len(ids)] = ids
-        self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))      # (the pool's upload, a previous epoch's table)
-        with torch.cuda.stream(self.stream):
-            table_dev = torch.from_numpy(table).to(self.pool.device)
-            for b in set(len(ids) for _step, ids in plan) - set(self._recipes):
-                self._recipes[b] = torch.from_numpy(self._recipe(b)).to(self.pool.device)
-        for i, (step, ids) in enumerate(plan):
-            yield self._assemble(step, table_dev[i, :len(ids)], len(ids))
+        points, label, category = out
+        assemble(self.pool.rows, self.pool.offsets, ids_dev, self.num_point, self.seed, step, self._recipes[len(category)],
+                 out=(points, label))
+        torch.index_select(self.pool.category_dev, 0, ids_dev, out=category)

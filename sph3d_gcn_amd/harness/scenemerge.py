@@ -245,24 +245,14 @@ class SceneResult:
     @classmethod
     def merge(cls, results):
         """the result of the ranks' shares together: equal to the world = 1 result"""
-        results = list(results)
-        if not results:
-            raise ValueError("merge: no results")
-        rows = sorted((s, r, i) for r, res in enumerate(results) for i, s in enumerate(res.scenes))
-        if len(set(s for s, _, _ in rows)) != len(rows):
-            raise ValueError("merge: a scene occurs in two results")
-        pred = None
-        if all(res.pred is not None for res in results):
-            pred = {s: p for res in results for s, p in res.pred.items()}
-        pick = lambda name: [getattr(results[r], name)[i] for _, r, i in rows]
+        results, pick, pred = evalvote.merge_order(results, "scenes", "scene", "pred")
         return cls(sum(res.confusion_full for res in results), sum(res.confusion_voxel for res in results),
-                   evalvote.EvalResult.merge([res.block for res in results]), [s for s, _, _ in rows], pick("unseen_rows"),
+                   evalvote.EvalResult.merge([res.block for res in results]), pick("scenes"), pick("unseen_rows"),
                    pick("skipped_rows"), pick("out_of_scene"), pick("complete"), pred)
 
 
 def _check_scene_args(scenes, batch_size, rank, world):
-    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
-        raise ValueError("evaluate_scenes: bad batch_size / rank / world")
+    evalvote.check_share(batch_size, rank, world, "evaluate_scenes")
     if not scenes:
         raise ValueError("evaluate_scenes: no scenes")
 
@@ -389,7 +379,7 @@ def evaluate_scenes(model_fn, pool, scenes, batch_size, num_point, seed, num_cls
             done.append(d)
             numbers.append(i)
             ok = ok and d.complete
-            base, nrows = voter._range(ids)
+            base, nrows = voter.row_range(ids)
             ids_dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
             _lib.check(l.sph3d_scene_merge(len(ids), C, P, T, _lib.ptr(pool.rows), _lib.ptr(pool.offsets), _lib.ptr(pool.index),
                                            _lib.ptr(ids_dev), base, nrows, _lib.ptr(voter.votes), V, _lib.ptr(merged), _lib.ptr(hits),

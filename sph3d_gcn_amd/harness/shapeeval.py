@@ -192,24 +192,15 @@ class ShapeResult:
     @classmethod
     def merge(cls, results):
         """the result of the ranks' shares together: equal to the world = 1 result"""
-        results = list(results)
-        if not results:
-            raise ValueError("merge: no results")
-        order = sorted((b, r, i) for r, res in enumerate(results) for i, b in enumerate(res.batches))
-        if len(set(b for b, _, _ in order)) != len(order):
-            raise ValueError("merge: a batch occurs in two results")
+        results, order, votes = evalvote.merge_order(results)
         shapes = np.concatenate([res.shapes for res in results])
         if np.unique(shapes).shape[0] != shapes.shape[0]:
             raise ValueError("merge: a shape occurs in two results")
         by_shape = np.argsort(shapes, kind="stable")
         pick = lambda name: np.concatenate([getattr(res, name) for res in results])[by_shape]
-        votes = None
-        if all(res.votes is not None for res in results):
-            votes = {b: v for res in results for b, v in res.votes.items()}
         return cls(pick("shapes"), pick("category"), pick("shape_iou"), pick("correct"), pick("seen"),
-                   sum(res.class_correct for res in results), sum(res.class_seen for res in results), [b for b, _, _ in order],
-                   [results[r].passes[i] for _, r, i in order], [results[r].covered[i] for _, r, i in order],
-                   [results[r].size[i] for _, r, i in order], sum(res.nonfinite_rows for res in results),
+                   sum(res.class_correct for res in results), sum(res.class_seen for res in results), order("batches"),
+                   order("passes"), order("covered"), order("size"), sum(res.nonfinite_rows for res in results),
                    max(res.num_categories for res in results), votes)
 
 
@@ -230,8 +221,7 @@ def evaluate_reference(logits_fn, sizes, rows_label, category, batch_size, num_p
                        min_count=MIN_COUNT, max_passes=MAX_PASSES, rank=0, world=1, keep_votes=False):
     """`evaluate` stated in numpy: shape_vote_reference over the batches of rank `rank`; category [P]; part_lo / part_n: the
     one-hot model's table per category, None for a per-category model; logits_fn(batch_index, q, index [b, N]) -> [b, N, C]"""
-    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
-        raise ValueError("evaluate_reference: bad batch_size / rank / world")
+    evalvote.check_share(batch_size, rank, world, "evaluate_reference")
     P, C = len(sizes), int(num_cls)
     category = np.asarray(category, dtype=np.int32).reshape(-1)
     tlo, tn, ncat = _table(category, part_lo, part_n, C)
@@ -249,117 +239,70 @@ def evaluate_reference(logits_fn, sizes, rows_label, category, batch_size, num_p
 # ---------------------------------------------------------------------------------------------------------------
 # the device side
 # ---------------------------------------------------------------------------------------------------------------
-class ShapeVoter:
-    """The device buffers of one evaluation — vote sums [capacity_rows, C] fp32, counts, predictions, stamps, the feed's output
-    set, the part counts — allocated once and reused by every batch, and the loop of one batch.  `pool` is an
-    objfeed.ShapePool; a batch's shapes must lie inside `capacity_rows` consecutive rows of it."""
+class ShapeVoter(evalvote.Voter):
+    """evalvote.Voter's buffers and loop on an objfeed.ShapePool: a pass is one draw evaluated twice, on the plain and on the
+    augmented coordinates, and a finished batch is closed by sph3d_shape_iou into `parts` instead of a confusion matrix.  A
+    batch's shapes must lie inside `capacity_rows` consecutive rows of the pool."""
+    what = "shapes"
 
     def __init__(self, pool, batch_size, num_point, num_cls, capacity_rows, min_count=MIN_COUNT):
-        import torch
-        from .. import _lib
         _check_loop_args(num_point, num_cls, min_count, 1)
-        if batch_size <= 0 or capacity_rows <= 0:
-            raise ValueError("ShapeVoter: batch_size>0 and capacity_rows>0 required")
-        self.pool, self.B, self.N, self.C = pool, int(batch_size), int(num_point), int(num_cls)
-        self.cap, self.min_votes = int(capacity_rows), 2 * int(min_count)
-        dev, B, C = pool.device, self.B, self.C
-        self.votes = torch.empty((self.cap, C), dtype=torch.float32, device=dev)
-        self.count = torch.empty((self.cap,), dtype=torch.int32, device=dev)
-        self.pred = torch.empty((self.cap,), dtype=torch.int32, device=dev)
-        self.ws_bytes = int(_lib.lib().sph3d_vote_workspace(self.cap))
-        self.ws = torch.empty((self.ws_bytes,), dtype=torch.uint8, device=dev)
-        self.state = torch.zeros((2 * B + 1,), dtype=torch.int32, device=dev)             # covered | inner_size | remaining
-        self.covered, self.inner_size, self.remaining = self.state[:B], self.state[B:2 * B], self.state[2 * B:]
+        super().__init__(pool, batch_size, num_point, num_cls, capacity_rows, 2 * int(min_count))
+
+    def _alloc(self, dev):
+        import torch
+        B, C = self.B, self.C
         self.parts = torch.zeros((3 * B * C + B,), dtype=torch.int32, device=dev)         # inter | pred_cnt | gt_cnt | correct
-        self.nonfinite = torch.zeros((1,), dtype=torch.int64, device=dev)
         self.out = (torch.empty((B, self.N, 3), dtype=torch.float32, device=dev), torch.empty((B, self.N), dtype=torch.int32, device=dev))
         self.recipes = (torch.zeros((B,), dtype=torch.int32, device=dev),
                         torch.full((B,), objfeed.EVAL_AUGMENT, dtype=torch.int32, device=dev))
 
-    def _range(self, shape_ids):
-        ids = [int(i) for i in shape_ids if 0 <= int(i) < len(self.pool)]
-        if len(set(ids)) != len(ids):
-            raise ValueError("the shapes of a batch are distinct")
-        if not ids:
-            return None
-        lo = min(int(self.pool.host_offsets[i]) for i in ids)
-        hi = max(int(self.pool.host_offsets[i + 1]) for i in ids)
-        if hi - lo > self.cap:
-            raise ValueError("the batch's shapes span %d rows of the pool, the buffers hold %d" % (hi - lo, self.cap))
-        return lo, hi - lo
+    def _open(self, shape_ids):
+        """the shapes' part ranges and categories, on the host and on the device; the two recipes cut to the batch"""
+        import torch
+        p, P = self.pool, len(self.pool)
+        self._plo, self._pn = p.part_range(shape_ids, self.C)
+        self._range_dev = torch.from_numpy(np.concatenate([self._plo, self._pn])).to(p.device)
+        self._recipes = tuple(r[:len(shape_ids)] for r in self.recipes)
+        self._category = torch.from_numpy(np.where((shape_ids >= 0) & (shape_ids < P), p.category[np.clip(shape_ids, 0, P - 1)], 0)
+                                          .astype(np.int32)).to(p.device)
+
+    def _pass(self, model_fn, ids_dev, out, seed, batch_index, p, vote):
+        """draw p of a batch: the same sample plain, then with EVAL_AUGMENT, voted as passes 2 p and 2 p + 1"""
+        step = evalvote.pass_step(batch_index, p)
+        for a in range(2):
+            points, label, index = objfeed.assemble(self.pool.rows, self.pool.offsets, ids_dev, self.N, seed, step,
+                                                    self._recipes[a], out=out, want_index=True)
+            vote(2 * p + a, index, lambda: model_fn(points, label, self._category))
 
     def run_batch(self, model_fn, shape_ids, seed, batch_index, max_passes=MAX_PASSES, keep_votes=False, on_pass=None):
-        """all draws of one batch, then its predictions and part counts -> ShapeVotes (votes / count / pred are per-shape host
-        arrays with keep_votes, else None)"""
-        import torch
-        from .. import _lib
+        """all draws of one batch (at most max_passes of them), then its predictions and part counts -> ShapeVotes (votes /
+        count / pred are per-shape host arrays with keep_votes, else None)"""
         _check_loop_args(self.N, self.C, 1, max_passes)
-        shape_ids = np.ascontiguousarray(np.asarray(shape_ids).reshape(-1), dtype=np.int32)
-        b, B, C = int(shape_ids.shape[0]), self.B, self.C
-        if not 0 < b <= B:
-            raise ValueError("a batch has 1..%d shapes, got %d" % (B, b))
-        if batch_index < 0 or batch_index >= 1 << (63 - evalvote.PASS_BITS):
-            raise ValueError("batch_index out of range")
-        plo, pn = self.pool.part_range(shape_ids, C)
-        rng = self._range(shape_ids)
-        zb, zc = np.zeros((b,), np.int32), np.zeros((b, C), np.int32)
-        if rng is None:
-            return ShapeVotes(None, None, None, 0, zb, zb.copy(), zc, zc.copy(), zc.copy(), zb.copy(), np.full((b,), np.nan), True, 0)
-        base, nrows = rng
-        p, l = self.pool, _lib.lib()
-        P, T = len(p), int(p.rows.shape[0])
-        ids_dev = torch.from_numpy(shape_ids).to(p.device)
-        range_dev = torch.from_numpy(np.concatenate([plo, pn])).to(p.device)
-        category = torch.from_numpy(np.where((shape_ids >= 0) & (shape_ids < P), p.category[np.clip(shape_ids, 0, P - 1)], 0)
-                                    .astype(np.int32)).to(p.device)
-        common = (P, T, _lib.ptr(p.rows), _lib.ptr(p.offsets), _lib.ptr(ids_dev), base, nrows)
-        _lib.check(l.sph3d_vote_begin(b, C, *common, _lib.ptr(self.votes), _lib.ptr(self.count), _lib.ptr(self.covered),
-                                      _lib.ptr(self.inner_size), _lib.ptr(self.remaining), _lib.ptr(self.ws), self.ws_bytes,
-                                      _lib.stream_ptr()))
-        out = tuple(t[:b] for t in self.out)
-        passes = 0
-        remaining = int(self.remaining.item())
-        while remaining > 0 and passes < max_passes:
-            step = evalvote.pass_step(batch_index, passes)
-            for a in range(2):
-                points, label, index = objfeed.assemble(p.rows, p.offsets, ids_dev, self.N, seed, step, self.recipes[a][:b], out=out,
-                                                        want_index=True)
-                with torch.no_grad():
-                    logits = model_fn(points, label, category)
-                _lib.require_device(logits)
-                if tuple(logits.shape) != (b, self.N, C):
-                    raise ValueError("model_fn: logits [%d, %d, %d] expected, got %s" % (b, self.N, C, tuple(logits.shape)))
-                logits = _lib.f32(logits.detach())
-                if on_pass is not None:
-                    on_pass(batch_index, 2 * passes + a, index, logits)
-                _lib.check(l.sph3d_vote_accumulate(b, self.N, C, *common, 2 * passes + a, _lib.ptr(index), _lib.ptr(logits),
-                                                   self.min_votes, _lib.ptr(self.votes), _lib.ptr(self.count), _lib.ptr(self.covered),
-                                                   _lib.ptr(self.inner_size), _lib.ptr(self.remaining), _lib.ptr(self.ws),
-                                                   self.ws_bytes, _lib.stream_ptr()))
-            remaining = int(self.remaining.item())               # the loop's one word per draw: a host synchronisation
-            passes += 1
+        return super().run_batch(model_fn, shape_ids, seed, batch_index, max_passes, keep_votes, on_pass)
+
+    def _empty(self, b):
+        zb, zc = np.zeros((b,), np.int32), np.zeros((b, self.C), np.int32)
+        return ShapeVotes(None, None, None, 0, zb, zb.copy(), zc, zc.copy(), zc.copy(), zb.copy(), np.full((b,), np.nan), True, 0)
+
+    def _close(self, shape_ids, common, passes, keep_votes):
+        """the batch's predictions and part counts -> ShapeVotes"""
+        from .. import _lib
+        b, B, C, plo, pn = len(shape_ids), self.B, self.C, self._plo, self._pn
         before = int(self.nonfinite.item())
         inter, pred_cnt, gt_cnt = (self.parts[k * B * C:k * B * C + b * C] for k in range(3))
         correct = self.parts[3 * B * C:3 * B * C + b]
-        _lib.check(l.sph3d_shape_iou(b, C, *common, _lib.ptr(self.votes), _lib.ptr(range_dev), _lib.ptr(range_dev[b:]),
-                                     _lib.ptr(self.pred), _lib.ptr(inter), _lib.ptr(pred_cnt), _lib.ptr(gt_cnt), _lib.ptr(correct),
-                                     _lib.ptr(self.nonfinite), _lib.stream_ptr()))
-        state, parts = self.state.cpu().numpy(), self.parts.cpu().numpy()
+        _lib.check(_lib.lib().sph3d_shape_iou(b, C, *common, _lib.ptr(self.votes), _lib.ptr(self._range_dev),
+                                              _lib.ptr(self._range_dev[b:]), _lib.ptr(self.pred), _lib.ptr(inter), _lib.ptr(pred_cnt),
+                                              _lib.ptr(gt_cnt), _lib.ptr(correct), _lib.ptr(self.nonfinite), _lib.stream_ptr()))
+        covered, size = self._coverage(b)
+        parts = self.parts.cpu().numpy()
         nonfinite = int(self.nonfinite.item()) - before
-        covered, size = state[:b].copy(), state[B:B + b].copy()
         inter, pred_cnt, gt_cnt = (parts[k * B * C:k * B * C + b * C].reshape(b, C).copy() for k in range(3))
         correct = parts[3 * B * C:3 * B * C + b].copy()
         iou = np.array([shape_iou(inter[k], pred_cnt[k], gt_cnt[k], int(plo[k]), int(pn[k])) if size[k] else np.nan
                         for k in range(b)], dtype=np.float64)
-        votes = count = pred = None
-        if keep_votes:
-            hv, hc, hp = self.votes[:nrows].cpu().numpy(), self.count[:nrows].cpu().numpy(), self.pred[:nrows].cpu().numpy()
-            votes, count, pred = [], [], []
-            for i in shape_ids:
-                lo, hi = (int(p.host_offsets[i]) - base, int(p.host_offsets[i + 1]) - base) if 0 <= i < P else (0, 0)
-                votes.append(hv[lo:hi].copy())
-                count.append(hc[lo:hi].copy())
-                pred.append(hp[lo:hi].copy())
+        votes, count, pred = self._kept(shape_ids, common, keep_votes)
         return ShapeVotes(votes, count, pred, passes, covered, size, inter, pred_cnt, gt_cnt, correct, iou,
                           bool((covered >= size).all()), nonfinite)
 
@@ -381,8 +324,7 @@ def evaluate(model_fn, pool, batch_size, num_point, seed, num_cls, min_count=MIN
     reference's `count > 10`).  on_pass(batch_index, q, index, logits): a hook that sees the device tensors of evaluation
     q = 2 draw + (1 if augmented) before they are voted.  keep_votes: the sums, counts and predictions come to the host."""
     _check_loop_args(num_point, num_cls, min_count, max_passes)
-    if batch_size <= 0 or world <= 0 or not 0 <= rank < world:
-        raise ValueError("evaluate: bad batch_size / rank / world")
+    evalvote.check_share(batch_size, rank, world, "evaluate")
     C = int(num_cls)
     _lo, _n, ncat = _table(pool.category, pool.part_lo, pool.part_n, C)
     mine = list(range(rank, feed.batches_per_epoch(len(pool), batch_size), world))

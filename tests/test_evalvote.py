@@ -1,5 +1,6 @@
 """harness/evalvote.py without a GPU: the numpy statement of the overlap-voting evaluation (the duplicate rule against numpy's own
 fancy-index `+=`, the coverage loop, max_passes, metrics, merging ranks) and the C entries' host-side validation."""
+import collections
 import ctypes
 import os
 import re
@@ -259,3 +260,32 @@ def test_python_side_argument_checks():
         args.update(kw)
         with pytest.raises(ValueError):
             evalvote.evaluate(lambda p, l, i: None, None, **args)
+
+
+def test_merge_order_sorts_interleaved_ranks_and_refuses_a_repeated_key():
+    """the helper behind EvalResult / ShapeResult / SceneResult.merge: rank r of 3 evaluated batches r, r + 3, ...; the merged
+    order is ascending by key whatever order the results come in, the kept dicts are joined only when all have one"""
+    Res = collections.namedtuple("Res", "batches passes votes")
+    ranks = [Res([r, r + 3, r + 6][:3 - (r == 2)], ["p%d" % k for k in [r, r + 3, r + 6][:3 - (r == 2)]], {r: "v%d" % r}) for r in range(3)]
+    for order in ([0, 1, 2], [2, 0, 1]):
+        results, pick, votes = evalvote.merge_order([ranks[r] for r in order])
+        assert [res.batches for res in results] == [ranks[r].batches for r in order]
+        assert pick("batches") == list(range(8)) and pick("passes") == ["p%d" % k for k in range(8)]
+        assert votes == {0: "v0", 1: "v1", 2: "v2"}
+    _, _, votes = evalvote.merge_order([ranks[0], ranks[1]._replace(votes=None)])
+    assert votes is None
+    with pytest.raises(ValueError, match="a batch occurs in two results"):
+        evalvote.merge_order([ranks[0], ranks[1], Res([7, 3], ["x", "y"], None)])
+    Scenes = collections.namedtuple("Scenes", "scenes pred")
+    with pytest.raises(ValueError, match="a scene occurs in two results"):
+        evalvote.merge_order([Scenes([0, 2], None), Scenes([2], None)], "scenes", "scene", "pred")
+    with pytest.raises(ValueError, match="no results"):
+        evalvote.merge_order([])
+
+
+def test_check_share_refuses_what_is_no_share():
+    evalvote.check_share(1, 0, 1, "evaluate")
+    evalvote.check_share(16, 3, 4, "evaluate")
+    for batch_size, rank, world in ((16, 0, 0), (16, 4, 4), (0, 0, 1), (16, -1, 4)):
+        with pytest.raises(ValueError, match="evaluate_scenes: bad batch_size / rank / world"):
+            evalvote.check_share(batch_size, rank, world, "evaluate_scenes")

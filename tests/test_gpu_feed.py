@@ -110,6 +110,33 @@ def test_same_seed_and_step_give_identical_bytes(pool, dev):
     assert not torch.equal(a[3], c[3])
 
 
+def test_both_assemble_kernels_share_the_pool_lookup_and_the_sample(dev):
+    """feed.hip and objfeed.hip take a cloud's rows and a slot's row from the same helpers (csrc/feed_draws.hpp): on one pool,
+    without augmentation, index, label and xyz of the two are the same bytes.  Blocks of 1 and 40 rows are sampled with
+    replacement, 64 is n == N, and 64 / 65 / 257 / 1025 put the Feistel width on both sides of a power of two, odd and even;
+    an id of -1 reads nothing in both."""
+    import torch
+    from sph3d_gcn_amd.harness import objfeed
+    rng = np.random.RandomState(11)
+    blocks = [objfeed.shape_blocks(rng.rand(n, 3).astype(np.float32), rng.randint(0, 13, n)) for n in (1, 40, 64, 65, 257, 1025)]
+    p = feed.BlockPool.from_blocks(blocks, dev)
+    N, seed, step = 64, 0x1234567890abcdef, 77
+    for ids in ([0, 1, 2, 3, 4, 5], [5, -1, 3, 2, 1, 0]):
+        ids_dev = torch.tensor(ids, dtype=torch.int32, device=dev)
+        pts, label, inner, index = feed.assemble(p.rows, p.offsets, ids_dev, N, seed, step, augment=False, want_index=True)
+        opts, olabel, oindex = objfeed.assemble(p.rows, p.offsets, ids_dev, N, seed, step, 0, want_index=True)
+        assert torch.equal(index, oindex) and torch.equal(label, olabel)
+        assert torch.equal(pts[..., :3].contiguous().view(torch.int32), opts.view(torch.int32))
+        want = feed.assemble_reference(p.sizes, [i for i in ids if i >= 0], N, seed, step, False).index
+        for b, i in enumerate(ids):
+            if i < 0:
+                assert (index[b] == -1).all() and (oindex[b] == -1).all() and not pts[b].any() and not opts[b].any()
+            else:
+                assert (index[b] >= 0).all() and (index[b] < len(blocks[i])).all() and bool(inner[b].all())
+        if -1 not in ids:
+            assert np.array_equal(index.cpu().numpy(), want)
+
+
 def test_device_feed_epoch_matches_its_plan_and_alternates_two_sets(pool, dev):
     """every item equals assemble() of its planned (step, block ids); two consecutive items never share storage; item i+2 reuses
     item i's; the last batch is the short one; the second epoch has another order and continues the step numbers"""

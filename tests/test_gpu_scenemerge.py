@@ -65,7 +65,7 @@ def test_merge_and_finalize_equal_the_statement_bit_for_bit(dev, C, b):
     ids = np.arange(b, dtype=np.int32)
     got = voter.run_batch(_Toy(C, dev), ids, seed, 0)
     assert got.complete
-    base, nrows = voter._range(ids)
+    base, nrows = voter.row_range(ids)
     assert (base, nrows) == (0, sum(sizes))
     voter.votes[5:9] = 0.0
     voter.votes[2000, 3] = float("nan")
