@@ -207,6 +207,8 @@ int sph3d_graph_transpose(int B, int N, int M, int K, int F,
  * ent_key[e] = m | nn_count[m] << 24 and no scale array — allowed for un-weighted graphs (weight == NULL) with M <= 2^24 and K <= 255
  * (SPH3D_EINVAL otherwise); every consumer below that takes (ent_key, ent_scale) accepts ent_scale == NULL for such a graph and
  * derives 1 / nn_count[m] from the word (the same correctly rounded division); sph3d_max_pool3d_grad_t masks the row bits itself.
+ * Packed entries need nn_count <= K <= 255 in every row: the count takes the word's top eight bits (128..255 set bit 31; the
+ * word is formed and decoded in unsigned arithmetic).
  * The two phases of sph3d_graph_transpose on one workspace: segment counts (also produced by sph3d_build_sphere_graph), then
  * scan + fill. */
 int sph3d_graph_transpose_count(int B, int N, int M, int K, int F, const int* nn_index, const int* nn_count,
@@ -247,7 +249,10 @@ int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, int r,
                                   float* grad_input, float* grad_filter,
                                   void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
 /* (transposed graph built with F = 1)  grad_input[B,Nin,C] = sum over in-edges of grad_output[B,Mout,C] * ent_scale: the gradient of
- * avg_pool3d (Nin=N, Mout=M), mean_interpolate and weighted_interpolate (Nin=M coarse, Mout=N fine). */
+ * avg_pool3d (Nin=N, Mout=M), mean_interpolate and weighted_interpolate (Nin=M coarse, Mout=N fine).
+ * Non-finite values: an element with a non-finite term is non-finite, but not always of the reference's kind.  With C <= 128,
+ * C % 4 == 0, B * Nin <= 65536 and Mout >= 2 * Nin the in-edges are taken in pairs and an odd last edge is read twice, the
+ * second time with scale 0: +-inf in that row gives NaN (0 * inf) where the reference gives +-inf. */
 int sph3d_scatter_grad_t(int B, int Nin, int Mout, int C,
                          const int* offsets, const int* ent_key, const float* ent_scale,
                          const float* grad_output, float* grad_input, sph3d_stream_t stream);
@@ -273,6 +278,9 @@ int sph3d_max_pool3d_grad_t(int B, int N, int M, int C, const int* offsets, cons
                             const int* max_index, const float* grad_output,
                             const float* addend /* optional [B,N,C]: another gradient of the same input, added in (NULL: none) */,
                             float* grad_input, sph3d_stream_t stream);
+/* Non-finite values (C <= 128, C % 4 == 0): neighbours are taken in pairs and the last one of an odd count is read twice, the
+ * second time with weight 0, so +-inf in that neighbour's row gives NaN (0 * inf) where the reference gives +-inf.  Only an
+ * element that was non-finite anyway is affected. */
 int sph3d_avg_pool3d(int B, int N, int M, int C, int K,
                      const int* nn_index, const int* nn_count, const float* input,
                      float* output, sph3d_stream_t stream);
@@ -287,7 +295,9 @@ int sph3d_avg_pool3d_grad(int B, int N, int M, int C, int K,
  * weightedInterpolateLauncher / weightedInterpolateGradLauncher
  * (tf_ops/unpooling/tf_unpool3d_gpu.cu:87-113; kernels :5-84; ops
  * tf_unpool3d.cpp:64-242).  Here N = fine/output count, M = coarse/input
- * count (the reference's naming): input[B,M,C], nn_index[B,N,K] -> output[B,N,C]. */
+ * count (the reference's naming): input[B,M,C], nn_index[B,N,K] -> output[B,N,C].
+ * Non-finite values, both forward ops (C <= 128, C % 4 == 0): as sph3d_avg_pool3d, +-inf in the last neighbour of an odd count
+ * gives NaN where the reference gives +-inf; the element is non-finite either way. */
 int sph3d_mean_interpolate(int B, int N, int M, int C, int K,
                            const int* nn_index, const int* nn_count, const float* input,
                            float* output, sph3d_stream_t stream);
@@ -311,7 +321,8 @@ int sph3d_weighted_interpolate_grad(int B, int N, int M, int C, int K,
  *   output[b,n,:] = base[b,n,:] + sum_k w_k input[b, nn_index[b,n,k], :]     w_k = 1/nn_count[b,n] (weight == NULL) or weight[b,n,k]
  * base [B,N,C] is optional (NULL: zero); a row without neighbours gets its base row unchanged.  The neighbours are summed in the
  * order sph3d_mean_interpolate / sph3d_weighted_interpolate use for C <= 128.  The gradient with respect to `input` gathers over
- * the transposed graph (F = 1), like sph3d_scatter_grad_t: no atomics, fixed order. */
+ * the transposed graph (F = 1), like sph3d_scatter_grad_t: no atomics, fixed order.  Non-finite values in the forward op: as
+ * sph3d_avg_pool3d, +-inf in the last neighbour of an odd count (of each 16) gives NaN where the reference gives +-inf. */
 int sph3d_interpolate_narrow_supported(int C);
 int sph3d_interpolate_narrow(int B, int N, int M, int C, int K,
                              const int* nn_index, const int* nn_count, const float* input,

@@ -209,7 +209,8 @@ __device__ __forceinline__ void tg_fill_rows(int fb, int nfb, int B, int N, int 
             f = f < 0 ? 0 : (f >= F ? F - 1 : f);
             const int dst = ob[(size_t)n * F + f] + slotPos[e];
             if (entScale == nullptr) {
-                entKey[dst] = m | (cnt << 24);              // packed entry (common.hpp): one scattered store per edge
+                // packed entry (common.hpp): one scattered store per edge; unsigned, a count of 128..255 reaches bit 31
+                entKey[dst] = (int)((unsigned)m | ((unsigned)cnt << 24));
             } else {
                 entKey[dst] = m;
                 entScale[dst] = weight ? weight[e] : inv;
