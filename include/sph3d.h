@@ -195,6 +195,10 @@ int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, int r, int K,
  *   offsets[B*(N*F+1)]  edges of segment (b,n,f) are entries [offsets[s], offsets[s+1]), s = b*(N*F+1) + n*F + f
  *   ent_key[B*M*K]      m, the graph row (output point) the edge comes from
  *   ent_scale[B*M*K]    1/nn_count[b,m]   (weight[b,m,k] when weight is not NULL)
+ * Cloud b's entries fill [offsets[b, 0], offsets[b, N*F]) of its slab [b*M*K, (b+1)*M*K), offsets[b, 0] = b*M*K; the rest of
+ * the slab (the slots k >= nn_count of its rows) is not written, nor is active_bins behind its 1 + count words.  A bin id
+ * outside [0, F-1] counts for the nearest bin, 0 or F-1, in the offsets and in active_bins.  The order of the entries inside
+ * one segment is not defined.  tests/_tgraph_ref.py states all of this in numpy.
  * workspace: sph3d_graph_transpose_workspace() bytes of scratch (segment counters). */
 size_t sph3d_graph_transpose_workspace(int B, int N, int M, int K, int F);
 int sph3d_graph_transpose(int B, int N, int M, int K, int F,
