@@ -243,7 +243,14 @@ int sph3d_graph_balanced_order(int B, int N, int F, const int* offsets, int* ord
 /* conv gradients from a prebuilt transposed graph: both gradients in one pass, no float atomics
  * (grad_input gathered in registers; grad_filter accumulated in per-lane registers by persistent workgroups
  * that sweep the clouds of their XCD, one partial table per workgroup written to `workspace` =
- * sph3d_depthwise_conv3d_grad_t_workspace() bytes, then reduced). */
+ * sph3d_depthwise_conv3d_grad_t_workspace() bytes, then reduced).
+ * Non-finite values in grad_output: grad_input is non-finite exactly where the reference's sum has a non-finite term.  grad_filter
+ * is non-finite at least there.  With F <= 33, r in {1, 2}, C*r % 4 == 0 and C*r <= 128 the in-edges of a segment (source, bin) are
+ * taken in batches of 6 or 8 that run past the segment's end onto in-edges of the same source in other bins, multiplied by a
+ * scale of exactly 0: a non-finite grad_output[b, m, j] can then make grad_filter[f, j / r, j % r] NaN (0 * inf, 0 * NaN) in every
+ * bin f in which a source named by row m has an in-edge, also where the reference's element is finite.  No other element is
+ * affected; the other forms (C*r > 128, two channels per lane, the generic kernel) take exact remainders and deviate nowhere.
+ * tests/_conv_ref.py states the op in float64, tests/test_gpu_conv_forms.py holds every launch form to it. */
 size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r);
 int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, int r,
                                   const int* offsets, const int* ent_key, const float* ent_scale,

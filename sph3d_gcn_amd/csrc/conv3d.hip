@@ -592,9 +592,10 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
                         }
 #undef SPH3D_BWD_HALF_BATCH
                     } else {
-                    // scales of THIS segment's lanes, zero elsewhere: a batch may then run past the segment end (and, as
-                    // v_readlane takes the lane number modulo 64, wrap to lanes below e0) without clamps or selects:
-                    // the extra gathers hit valid rows (every lane holds a valid key) and are multiplied by exactly 0
+                    // scales of THIS segment's lanes, zero elsewhere.  The batches below read lanes e0 .. e1 - 1 only (four at a
+                    // time, then the exact remainder), so no row outside the segment is gathered and the mask changes nothing
+                    // here: unlike the half- and quarter-wave batches above, this branch never multiplies a foreign row by 0
+                    // (a non-finite grad_out row reaches the segments it belongs to and no other: include/sph3d.h)
                     const float svm = ((unsigned)(lane - e0) < (unsigned)(e1 - e0)) ? sv : 0.f;
                     // four edges at a time (their row gathers are independent and issued together), then the segment's last one
                     // to three edges with exactly that many gathers: a padded last batch made a third of all gathers padding
