@@ -478,6 +478,30 @@ size_t sph3d_pointwise_gemm_skinny_tn_workspace(int R, int K1, int K2, int N);
 int sph3d_pointwise_gemm_skinny_tn(int R, int K1, int K2, int N, const float* A1, const float* A2, const float* dY, float* dW,
                                    void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
 
+/* ---- the category-conditioned logits layer of the one-hot ShapeNet model ------------------------------------------------------
+ * models/SPH3D_shapenet_onehot.py:105-119: tf.concat((mlp2 output, mlp1 features), axis=2), tf.concat with a [B, P, T] tile of
+ * tf.one_hot(cls_label), then pointwise_conv3d to num_cls outputs — without the tile or either concatenation.  The one-hot block
+ * times its T rows of W is one row of W per cloud:
+ *   sph3d_pointwise_gemm_cond       Y[b*P + p, :] = A1[b*P + p, :] W[0:K1] + A2[b*P + p, :] W[K1:K1+K2] + W[K1+K2+cat[b], :] (+ bias)
+ *                                   A1 [B*P, K1], A2 [B*P, K2] (NULL with K2 = 0), W [K1+K2+T, N], bias [N] or NULL, cat [B] int32;
+ *                                   a category outside [0, T) selects no row (tf.one_hot gives zeros there)
+ *   sph3d_pointwise_gemm_cond_grad  dT[c, :] = sum over the clouds b with cat[b] == c and over p of dY[b*P + p, :]  ([T, N]: the
+ *                                   gradient of W[K1+K2:]; rows of categories no cloud has are exactly 0, categories outside
+ *                                   [0, T) are skipped) and, unless dbias == NULL, dbias[N] = the sum over all rows.  Two
+ *                                   launches in a fixed summation order, no floating-point atomics
+ *                                   (workspace: ..._cond_grad_workspace bytes).
+ * Shapes: K1 >= 16 and K2 >= 0 multiples of 16, K1 + K2 <= 128, N <= 64, T <= 4096, B*P + 15 fits an int (the gradient: B <= 65535),
+ * 16-byte aligned operands; ..._cond_supported() -> 1 | 0.  Dimensions that are not positive, B*P past an int, a NULL operand or
+ * a workspace that is too small give SPH3D_EINVAL, any other shape outside the above SPH3D_EUNSUPPORTED (concatenate and call
+ * sph3d_pointwise_gemm then); both before any launch.  The other gradients are existing entries: dA1 / dA2 =
+ * sph3d_pointwise_gemm(trans_w = 1) with the matching rows of W, dW[0:K1] and dW[K1:K1+K2] = sph3d_pointwise_gemm_tn per half. */
+int sph3d_pointwise_gemm_cond_supported(int B, int P, int K1, int K2, int N, int T);
+int sph3d_pointwise_gemm_cond(int B, int P, int K1, int K2, int N, int T, const float* A1, const float* A2, const float* W,
+                              const float* bias, const int* cat, float* Y, sph3d_stream_t stream);
+size_t sph3d_pointwise_gemm_cond_grad_workspace(int B, int P, int N, int T);
+int sph3d_pointwise_gemm_cond_grad(int B, int P, int N, int T, const float* dY, const int* cat, float* dT, float* dbias,
+                                   void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+
 /* ---- the depthwise convolution over a channel concatenation that is never materialised --------------------------------------
  * DepthwiseConv3d / DepthwiseConv3dGrad (tf_conv3d.cpp:34-107, :109-205) applied to tf.concat((input_a, input_b), axis=2)
  * (models/SPH3D_s3dis.py:100-104: a decoder level's un-pooled features and the encoder's skip features): input_a [B,N,Ca],

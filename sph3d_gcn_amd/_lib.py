@@ -108,6 +108,10 @@ SIGNATURES = {
     "sph3d_pointwise_gemm_skinny": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_pointwise_gemm_skinny_tn_workspace": (_S, [_I] * 4),
     "sph3d_pointwise_gemm_skinny_tn": (_I, [_I] * 4 + [_P] * 5 + [_S, _P]),
+    "sph3d_pointwise_gemm_cond_supported": (_I, [_I] * 6),
+    "sph3d_pointwise_gemm_cond": (_I, [_I] * 6 + [_P] * 7),
+    "sph3d_pointwise_gemm_cond_grad_workspace": (_S, [_I] * 4),
+    "sph3d_pointwise_gemm_cond_grad": (_I, [_I] * 4 + [_P] * 5 + [_S, _P]),
     "sph3d_separable_conv3d_fused_supported": (_I, [_I] * 6),
     "sph3d_separable_conv3d_fused": (_I, [_I] * 9 + [_P] * 11),
     "sph3d_separable_conv3d_train_supported": (_I, [_I] * 6),

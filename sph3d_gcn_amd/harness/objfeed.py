@@ -159,6 +159,27 @@ def shape_blocks(xyz, label):
     return out
 
 
+def read_class_info(path):
+    """The ShapeNet category table (class_info_all.txt of shapenet_seg/evaluate_shapenet_onehot.py:58-62; one line per category,
+    four tab-separated columns: name, folder, number of parts, first part among the one-hot model's outputs)
+    -> (names [list of str], part_lo int32 [T], part_n int32 [T]): the part table a ShapePool takes."""
+    names, lo, n = [], [], []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            cols = line.rstrip("\r\n").split("\t")
+            if len(cols) != 4:
+                raise ValueError("%s:%d: four tab-separated columns expected" % (path, number))
+            names.append(cols[0])
+            n.append(int(cols[2]))
+            lo.append(int(cols[3]))
+    part_lo, part_n = np.asarray(lo, dtype=np.int32), np.asarray(n, dtype=np.int32)
+    if not names or (part_n <= 0).any() or part_lo[0] != 0 or (part_lo[1:] != np.cumsum(part_n)[:-1]).any():
+        raise ValueError("%s: the parts of the categories should be consecutive ranges that start at 0" % path)
+    return names, part_lo, part_n
+
+
 class ShapePool:
     """The shapes of a dataset resident on the device: `pool`, a feed.BlockPool of shape_blocks rows; `category` [P] int32 on
     the host and `category_dev` on the device (the ModelNet class or the ShapeNet category); and, for a one-hot model, the

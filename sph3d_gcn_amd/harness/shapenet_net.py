@@ -2,7 +2,8 @@
 
 Part segmentation plan (shapenet_seg/shapenet_config.py): 2048-point objects, raw xyz as the only input feature, encoder
 2048 -> 1024 -> 768 -> 384 -> 128 with radii .08/.16/.32/.64, the S3DIS channel plan, a decoder that mirrors it, then
-mlp2 (-> 64), concatenation with the mlp1 features and a point-wise classifier.  The graph construction is the same
+mlp2 (-> 64), concatenation with the mlp1 features and a point-wise classifier: one model per category (get_model), or the
+one-hot model of models/SPH3D_shapenet_onehot.py for all 50 parts (get_model_onehot).  The graph construction is the same
 three-stream GraphPlan as the S3DIS harness (same ops and arguments as the reference's build_graph /
 build_graph_deconv / spherical_kernel calls, issued ahead of the feature path).
 """
@@ -13,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import sph3gcn_util as s3g_util
-from .s3dis_net import GraphPlan, _separable_conv3d_block
+from .s3dis_net import GraphPlan, _EndPoints, _separable_conv3d_block
 
 
 def shapenet_config(num_input=2048):
@@ -49,9 +50,9 @@ def small_config(num_input=512):
     return c
 
 
-def get_model(points, num_cls, is_training, config=None, graphs=None, points_ready=None):
-    """models/SPH3D_shapenet.py:33-113 (config lists are not reversed in place here)."""
-    end_points = {}
+def _features(points, is_training, config, graphs=None, points_ready=None):
+    """the body the two models share (models/SPH3D_shapenet.py:33-104 = models/SPH3D_shapenet_onehot.py:34-108; config lists are
+    not reversed in place here): mlp1, encoder, decoder, mlp2 -> (mlp2 output [B, N, mlp], mlp1 features [B, N, mlp])"""
     reuse = None
     net = s3g_util.pointwise_conv3d(points, config.mlp, 'mlp1', weight_decay=config.weight_decay,
                                     with_bn=config.with_bn, with_bias=config.with_bias, reuse=reuse,
@@ -89,10 +90,34 @@ def get_model(points, num_cls, is_training, config=None, graphs=None, points_rea
     net = s3g_util.pointwise_conv3d(net, config.mlp, 'mlp2', weight_decay=config.weight_decay,
                                     with_bn=config.with_bn, with_bias=config.with_bias, reuse=reuse,
                                     is_training=is_training)
-    net = torch.cat((net, encoder[-1]), dim=2)
+    return net, encoder[-1]
+
+
+def get_model(points, num_cls, is_training, config=None, graphs=None, points_ready=None):
+    """models/SPH3D_shapenet.py:33-113"""
+    end_points = {}
+    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready)
+    net = torch.cat((net, skip), dim=2)
     end_points['feats'] = net
     net = s3g_util.pointwise_conv3d(net, num_cls, scope='logits', with_bn=False, with_bias=config.with_bias,
                                     activation_fn=None, is_training=is_training)
+    return net, end_points
+
+
+NUM_CATEGORIES = 16                     # models/SPH3D_shapenet_onehot.py:13
+
+
+def get_model_onehot(points, cls_label, num_cls, is_training, config=None, graphs=None, points_ready=None,
+                     num_categories=NUM_CATEGORIES):
+    """models/SPH3D_shapenet_onehot.py:34-121: the same encoder and decoder; the classifier reads the mlp2 output, the mlp1
+    features and a one-hot tile of the shape's category (cls_label [B] integers) and gives the logits of all num_cls parts.
+    end_points['feats'] is the reference's [B, N, 2 mlp + num_categories] tensor, built on first access: the fused classifier
+    (s3g_util.pointwise_conv3d_onehot) never materialises it."""
+    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready)
+    end_points = _EndPoints()
+    end_points.feats_parts = (net, skip, lambda: s3g_util.one_hot_tile(cls_label, num_categories, net.shape[1]))
+    net = s3g_util.pointwise_conv3d_onehot(net, skip, cls_label, num_categories, num_cls, scope='logits', with_bn=False,
+                                           with_bias=config.with_bias, activation_fn=None, is_training=is_training)
     return net, end_points
 
 
@@ -112,6 +137,25 @@ class SPH3DShapeNet(torch.nn.Module):
     def forward(self, points, is_training=True, graphs=None, points_ready=None):
         with s3g_util.variable_store(self.store):
             return get_model(points, self.num_cls, is_training, self.config, graphs=graphs, points_ready=points_ready)
+
+    def loss(self, pred, label):
+        return get_loss(pred, label)
+
+
+class SPH3DShapeNetOneHot(torch.nn.Module):
+    """the one-hot model: ONE network for all categories, num_cls = 50 parts, conditioned on the shape's category"""
+
+    def __init__(self, num_cls=50, num_categories=NUM_CATEGORIES, config=None, device=None, seed=7):
+        super().__init__()
+        self.num_cls = num_cls
+        self.num_categories = num_categories
+        self.config = copy.deepcopy(config) if config is not None else shapenet_config()
+        self.store = s3g_util.VariableStore(device=device, seed=seed)
+
+    def forward(self, points, cls_label, is_training=True, graphs=None, points_ready=None):
+        with s3g_util.variable_store(self.store):
+            return get_model_onehot(points, cls_label, self.num_cls, is_training, self.config, graphs=graphs,
+                                    points_ready=points_ready, num_categories=self.num_categories)
 
     def loss(self, pred, label):
         return get_loss(pred, label)

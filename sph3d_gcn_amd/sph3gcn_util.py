@@ -443,6 +443,35 @@ def pointwise_conv3d_concat(inputs_a, inputs_b, num_out_channels, scope, use_xav
                             reuse=reuse, is_training=is_training)
 
 
+def one_hot_tile(cls_label, num_categories, num_point):
+    """tf.tile(tf.reshape(tf.one_hot(cls_label, num_categories), [B, 1, T]), [1, num_point, 1]) (models/SPH3D_shapenet_onehot.py:
+    111-113): fp32 [B, num_point, T]; a label outside [0, T) gives a zero row, as tf.one_hot does"""
+    cls_label = cls_label.reshape(-1).long()
+    hot = (cls_label.unsqueeze(1) == torch.arange(num_categories, device=cls_label.device).unsqueeze(0)).float()
+    return hot.unsqueeze(1).expand(-1, num_point, -1)
+
+
+def pointwise_conv3d_onehot(inputs_a, inputs_b, cls_label, num_categories, num_out_channels, scope, use_xavier=True, stddev=1e-3,
+                            weight_decay=None, activation_fn=elu, with_bn=False, with_bias=False, reuse=None, is_training=None):
+    """pointwise_conv3d(tf.concat((inputs_a, inputs_b, one_hot_tile(cls_label, num_categories, N)), axis=2), ...) — same variables
+    (scope/weights [ca + cb + num_categories, num_out_channels], scope/biases), same result — for the category-conditioned logits
+    layer of models/SPH3D_shapenet_onehot.py:105-119: where the layer is a plain product the one-hot block selects one row of the
+    weights per cloud (tf_gemm.linear_concat2_onehot) and neither concatenation nor the tile is materialised.  With batch norm or an
+    activation, on tensors that are not on the HIP device, or for shapes the kernel does not cover: the literal concatenation."""
+    ca, cb = inputs_a.shape[-1], inputs_b.shape[-1]
+    B, P = inputs_a.shape[0], inputs_a.shape[1]
+    if (FUSE_LOGITS_ONEHOT and inputs_a.is_cuda and not with_bn and activation_fn is None
+            and tf_gemm.cond_supported(B, P, ca, cb, num_out_channels, num_categories)):
+        kernel = _variable_with_weight_decay(scope + '/weights', shape=[ca + cb + num_categories, num_out_channels],
+                                             use_xavier=use_xavier, stddev=stddev, with_decay=weight_decay)
+        biases = get_variable_store().get_variable(scope + '/biases', [num_out_channels], _constant(0.0)) if with_bias else None
+        out = tf_gemm.linear_concat2_onehot(inputs_a.reshape(B * P, ca), inputs_b.reshape(B * P, cb), cls_label, kernel, biases, P)
+        return out.reshape(B, P, num_out_channels)
+    net = torch.cat((inputs_a, inputs_b, one_hot_tile(cls_label, num_categories, P)), dim=2)
+    return pointwise_conv3d(net, num_out_channels, scope, use_xavier=use_xavier, stddev=stddev, weight_decay=weight_decay,
+                            activation_fn=activation_fn, with_bn=with_bn, with_bias=with_bias, reuse=reuse, is_training=is_training)
+
+
 def fully_connected(inputs,
                     num_out_channels,
                     scope,
@@ -533,6 +562,10 @@ FUSE_GEMM_BN = True    # the statistics of that tail from the GEMM's epilogue wh
 FUSE_POOL_SKIP = True             # pool3d_with_skip: the skip connection's gradient is added inside the max-pool gradient kernel
 FUSE_CONV_CONCAT = True           # separable_conv3d((a, b), ...): depthwise kernels over two inputs in place (tf_conv3d.depthwise_conv3d_concat)
 FUSE_LOGITS_CONCAT = True         # pointwise_conv3d_concat: few-output layer over two operand halves (tf_gemm.linear_concat2)
+# pointwise_conv3d_onehot: two operand halves + one weight row per cloud (tf_gemm.linear_concat2_onehot).  Measured at 32 x 2048,
+# 64 + 64 + 16 -> 50 (tools/exp_onehot.py): forward 22 against 51 us for the literal concatenation, backward 87 against
+# 65 (two half-sized weight-gradient products), forward + backward 109 against 119: True.
+FUSE_LOGITS_ONEHOT = True
 # is_training=False under torch.no_grad(): separable_conv3d as ONE kernel (tf_conv3d.separable_conv3d_fused).
 #   "auto" (default): where the one-kernel layer is the faster one (measured, tools/exp_sepconv_layers.py: with the pointwise
 #                     weights resident in registers always; with W streamed per tile — wider layers — from 16 384 output points up:

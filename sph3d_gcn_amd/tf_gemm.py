@@ -214,3 +214,129 @@ class _SkinnyLinear2Fn(torch.autograd.Function):
 def linear_concat2(a1, a2, w, bias=None):
     """[a1 | a2] @ w + bias for few output columns (N <= 16), the concatenation never materialised; a2 may be None"""
     return _SkinnyLinear2Fn.apply(a1, a2, w, bias)
+
+
+# ---- the category-conditioned logits layer: two operand halves and one row of w per cloud (csrc/condlogits.hip) ----------------
+def cond_supported(B, P, K1, K2, N, T):
+    return bool(_lib.lib().sph3d_pointwise_gemm_cond_supported(int(B), int(P), int(K1), int(K2), int(N), int(T)))
+
+
+def _cond_dims(a1, a2, w, rows_per_cloud):
+    R, K1 = a1.shape
+    K2 = 0 if a2 is None else a2.shape[1]
+    P = int(rows_per_cloud)
+    if P <= 0 or R % P != 0 or R == 0:
+        raise ValueError("rows_per_cloud should divide the %d rows" % R)
+    T = w.shape[0] - K1 - K2
+    if T < 1:
+        raise ValueError("weights should be [K1 + K2 + T, N] with T >= 1 category rows")
+    return R // P, P, K1, K2, w.shape[1], T
+
+
+def _cond_impl(a1: torch.Tensor, a2: torch.Tensor, cat: torch.Tensor, w: torch.Tensor, bias: torch.Tensor,
+               rows_per_cloud: int) -> torch.Tensor:
+    """a1[R,K1] @ w[:K1] + a2[R,K2] @ w[K1:K1+K2] + w[K1+K2+cat[row // rows_per_cloud]] + bias -> [R,N]
+    (a2 / bias with zero elements: absent; a category outside the T rows adds nothing)"""
+    _lib.require_device(a1, w, cat)
+    a1, w, cat = _lib.f32(a1), _lib.f32(w), _lib.i32(cat)
+    a2 = None if a2 is None or a2.numel() == 0 else _lib.f32(a2)
+    bias = None if bias is None or bias.numel() == 0 else _lib.f32(bias)
+    B, P, K1, K2, N, T = _cond_dims(a1, a2, w, rows_per_cloud)
+    if cat.numel() != B:
+        raise ValueError("one category per cloud expected (%d clouds, %d categories)" % (B, cat.numel()))
+    y = torch.empty((B * P, N), dtype=torch.float32, device=a1.device)
+    _lib.check(_lib.lib().sph3d_pointwise_gemm_cond(B, P, K1, K2, N, T, _lib.ptr(a1), _lib.ptr(a2), _lib.ptr(w), _lib.ptr(bias),
+                                                    _lib.ptr(cat), _lib.ptr(y), _lib.stream_ptr()))
+    return y
+
+
+def _cond_grad_into(dy, cat, rows_per_cloud, dt, dbias):
+    """dt[T,N] (a contiguous row range of the weight gradient) = per-category column sums of dy; dbias[N] (or None) = all rows"""
+    B, (T, N) = cat.numel(), dt.shape
+    l = _lib.lib()
+    wsb = l.sph3d_pointwise_gemm_cond_grad_workspace(B, int(rows_per_cloud), N, T)
+    ws = _lib.scratch(wsb, dy.device)
+    _lib.check(l.sph3d_pointwise_gemm_cond_grad(B, int(rows_per_cloud), N, T, _lib.ptr(dy), _lib.ptr(cat), _lib.ptr(dt),
+                                                _lib.ptr(dbias), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+
+
+def _cond_grad_impl(dy: torch.Tensor, cat: torch.Tensor, num_categories: int, rows_per_cloud: int, with_bias: bool) -> torch.Tensor:
+    """-> [T + 1, N]: rows 0..T-1 the gradient of the category rows, row T the bias gradient (zeros without with_bias)"""
+    _lib.require_device(dy, cat)
+    dy, cat = _lib.f32(dy), _lib.i32(cat)
+    if dy.shape[0] != cat.numel() * int(rows_per_cloud):
+        raise ValueError("dy should have rows_per_cloud rows per category entry")
+    out = torch.empty((num_categories + 1, dy.shape[1]), dtype=torch.float32, device=dy.device)
+    if not with_bias:
+        out[num_categories].zero_()
+    _cond_grad_into(dy, cat, rows_per_cloud, out[:num_categories], out[num_categories] if with_bias else None)
+    return out
+
+
+def _pointwise_gemm_tn_into(x, dy, dw):
+    """dw (a contiguous [Cin, Cout] row range) = x[R,Cin]^T @ dy[R,Cout]"""
+    R, Cin = x.shape
+    Cout = dy.shape[1]
+    l = _lib.lib()
+    wsb = l.sph3d_pointwise_gemm_tn_workspace(R, Cin, Cout)
+    ws = _lib.scratch(wsb, x.device)
+    _lib.check(l.sph3d_pointwise_gemm_tn(R, Cin, Cout, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(ws), wsb,
+                                         _lib.stream_ptr()))
+
+
+_cond = torch.library.custom_op("sph3d::pointwise_gemm_cond", mutates_args=())(_cond_impl)
+
+
+@_cond.register_fake
+def _(a1, a2, cat, w, bias, rows_per_cloud):
+    return a1.new_empty((a1.shape[0], w.shape[1]))
+
+
+_cond_grad = torch.library.custom_op("sph3d::pointwise_gemm_cond_grad", mutates_args=())(_cond_grad_impl)
+
+
+@_cond_grad.register_fake
+def _(dy, cat, num_categories, rows_per_cloud, with_bias):
+    return dy.new_empty((num_categories + 1, dy.shape[1]))
+
+
+class _CondLinear2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a1, a2, cat, w, bias, rows_per_cloud):
+        cat = _lib.i32(cat)
+        ctx.save_for_backward(a1, a2, cat, w)
+        ctx.has_bias = bias is not None
+        ctx.rows_per_cloud = int(rows_per_cloud)
+        return _cond_impl(a1, a2, cat, w, bias, rows_per_cloud)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a1, a2, cat, w = ctx.saved_tensors
+        dy = _lib.f32(dy)
+        K1 = a1.shape[1]
+        K2 = 0 if a2 is None else a2.shape[1]
+        # the input gradients: the general product with the matching rows of w, one call per half (_SkinnyLinear2Fn)
+        da1 = _pointwise_gemm_impl(dy, w[:K1], True) if ctx.needs_input_grad[0] else None
+        da2 = _pointwise_gemm_impl(dy, w[K1:K1 + K2], True) if (a2 is not None and ctx.needs_input_grad[1]) else None
+        want_b = ctx.has_bias and ctx.needs_input_grad[4]
+        dw = None
+        db = torch.empty((w.shape[1],), dtype=torch.float32, device=dy.device) if want_b else None
+        if ctx.needs_input_grad[3]:
+            # ONE weight gradient, written in three contiguous row ranges: the two operand halves' products and the
+            # per-category column sums of dy (which also give the bias gradient)
+            dw = torch.empty_like(w, dtype=torch.float32, memory_format=torch.contiguous_format)
+            _pointwise_gemm_tn_into(_lib.f32(a1), dy, dw[:K1])
+            if a2 is not None:
+                _pointwise_gemm_tn_into(_lib.f32(a2), dy, dw[K1:K1 + K2])
+            _cond_grad_into(dy, cat, ctx.rows_per_cloud, dw[K1 + K2:], db)
+        elif want_b:
+            db = dy.sum(0)
+        return da1, da2, None, dw, db, None
+
+
+def linear_concat2_onehot(a1, a2, cat, w, bias, rows_per_cloud):
+    """[a1 | a2 | onehot(cat[row // rows_per_cloud])] @ w + bias with neither concatenation nor the one-hot tile materialised;
+    w is [K1 + K2 + T, N]; a2 (or a zero-width a2) and bias may be None.  Shapes: cond_supported(B, rows_per_cloud, K1, K2, N, T)"""
+    if a2 is not None and a2.shape[-1] == 0:
+        a2 = None
+    return _CondLinear2Fn.apply(a1, a2, cat, w, bias, rows_per_cloud)
