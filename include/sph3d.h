@@ -584,6 +584,22 @@ int sph3d_objfeed_assemble(int B, int num_point, int num_blocks, long long total
                            const int* shape_ids, unsigned long long seed, unsigned long long step, const int* recipe,
                            float* points, int* label, int* index, sph3d_stream_t stream);
 
+/* ---- the input side of the RueMonge2014 facade line (ruemonge2014_seg/train_ruemonge2014.py:98-138,159,
+ * ruemonge2014_seg/evaluate_ruemonge2014.py:180-305, utils/data_util.py:64-105; records: io/make_tfrecord_ruemonge2014.py:45-57) on
+ * the device: one launch assembles a batch of 9-channel clouds from a resident pool of facade splits.  The pool is
+ * sph3d_feed_assemble's (rows [T,8]: xyz, rgb, label, inner; offsets [P+1]; ids [B] int32, device) plus normals [T,4] fp32
+ * (nx, ny, nz and a padding column that is never written out; 16-byte aligned).  The sample draws are sph3d_feed_assemble's: index
+ * is the same pure function of (seed, step, b, n, num_point) and does not depend on recipe.  recipe [B] int32 (device): the bit
+ * masks, purposes and counters of sph3d_objfeed_assemble; TURN and TILT multiply xyz AND the normal by the same matrix entries,
+ * SCALE, SHIFT and JITTER touch xyz only, rgb and the label are always copied.  A mask of 0 copies all nine channels bit for bit;
+ * a mask without TURN and TILT copies the normal bit for bit (csrc/facadefeed.hip; harness/facadefeed.py states it in numpy).
+ * -> points [B,num_point,9] fp32 in the reference's channel order xyz, normal, rgb; label [B,num_point] int32; index
+ * [B,num_point] int32 (nullable).  An id outside [0, P) or an offset pair outside [0, T] reads nothing: zeros in all nine
+ * channels, label 0 and index -1.  B <= 65535, B * num_point <= 2^31 - 1. */
+int sph3d_facadefeed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows, const float* normals,
+                              const long long* offsets, const int* ids, unsigned long long seed, unsigned long long step,
+                              const int* recipe, float* points, int* label, int* index, sph3d_stream_t stream);
+
 /* ---- the per-shape part IoU counts of the ShapeNet evaluation (shapenet_seg/evaluate_shapenet.py:262-289,
  * evaluate_shapenet_onehot.py:283-314; csrc/shapeeval.hip): the finalize of a batch of sph3d_vote_* whose blocks are shapes (same
  * rows / offsets / shape_ids / row_base / batch_rows, votes [batch_rows, C] as the accumulates left them, the part label in

@@ -390,7 +390,8 @@ class BlockPool:
 class TwoSetFeed:
     """The protocol DeviceFeed and harness/objfeed.py's ObjectFeed share: one epoch of batches per iteration, assembled on the
     feed's own stream into two alternating output sets.  A subclass says how a set is allocated (`_new_set`), what is launched
-    for one batch (`_launch`) and, if anything, what an epoch uploads besides its table (`_begin_epoch`).
+    for one batch (`_launch`) and, if anything, what an epoch uploads besides its table (`_begin_epoch`); one whose epoch is not
+    one visit per block says how many ids an epoch permutes (`_epoch_ids`) and how they become pool ids (`_map_ids`).
 
     The epoch's order is one host permutation from (seed, epoch), identical on every rank; rank r takes batches r, r + world,
     ...; the last batch may be smaller.  The kernel runs on the feed's own stream (`stream`, else one the feed creates);
@@ -430,9 +431,17 @@ class TwoSetFeed:
     def _begin_epoch(self, plan):
         """what an epoch uploads besides its table; torch's current stream is the feed's"""
 
+    def _epoch_ids(self):
+        """how many ids an epoch permutes (default: one per block of the pool)"""
+        return len(self.pool)
+
+    def _map_ids(self, table):
+        """the epoch's id table [batches, batch_size] int32 -> the pool ids that go up (default: the ids themselves)"""
+        return table
+
     def __len__(self):
         """batches of this rank per epoch"""
-        return len(range(self.rank, batches_per_epoch(len(self.pool), self.batch_size), self.world))
+        return len(range(self.rank, batches_per_epoch(self._epoch_ids(), self.batch_size), self.world))
 
     def done(self, ready, event=None):
         """the consumer is finished with the item whose event is `ready`: after `event` (default: one recorded now on the current
@@ -465,7 +474,7 @@ class TwoSetFeed:
 
     def __iter__(self):
         import torch
-        plan = epoch_plan(len(self.pool), self.batch_size, self.seed, self.epoch, self.rank, self.world)
+        plan = epoch_plan(self._epoch_ids(), self.batch_size, self.seed, self.epoch, self.rank, self.world)
         self.epoch += 1
         if not plan:
             return
@@ -475,7 +484,7 @@ class TwoSetFeed:
             table[i, :len(ids)] = ids
         self.stream.wait_stream(torch.cuda.current_stream(self.pool.device))      # (the pool's upload, a previous epoch's table)
         with torch.cuda.stream(self.stream):
-            table_dev = torch.from_numpy(table).to(self.pool.device)
+            table_dev = torch.from_numpy(self._map_ids(table)).to(self.pool.device)
             self._begin_epoch(plan)
         for i, (step, ids) in enumerate(plan):
             yield self._assemble(step, table_dev[i, :len(ids)], len(ids))

@@ -107,12 +107,14 @@ class GraphPlan:
     On CPU tensors (oracle-backed tests) everything is built lazily on the spot."""
 
     def __init__(self, points, config, overlap=True, points_ready=None, decoder=True, global_kernel=None, global_radius=100.0,
-                 global_query=None, prepare_input=True, need_backward=None, xyz_transform=None):
+                 global_query=None, prepare_input=True, need_backward=None, xyz_transform=None, net_input=None):
         """decoder=False: an encoder-only plan (the classification net); global_kernel: also the global graph of
         models/SPH3D_modelnet.py:83-93 (query = centroid of the last level's points, every remaining point a neighbour) with
         the bins of that kernel (global_query: the query points [B, 1, 3], default the centroid of the last level);
         need_backward (default: torch.is_grad_enabled()): also build the transposed graphs the gradients gather over;
         prepare_input=False: `points` are coordinates only (no S3DIS input features to prepare).
+        net_input: the function (points, config) -> the network's input features that prepare_input runs (default: the S3DIS
+        one, centred coordinates + colours; harness/ruemonge_net.py brings its nine channels).
         xyz_transform: a function of the raw coordinates (the classification net's unit-sphere normalisation) applied ON THE
         SAMPLING STREAM before anything else: the plan is built on its result (xyz_layers[0]; `xyz0()` hands it to the feature
         path), so that with points_ready the whole plan depends on the input batch alone.  global_query="centroid": the
@@ -133,6 +135,7 @@ class GraphPlan:
         self._enc_ev, self._dec_ev, self._pool_ev = {}, {}, {}
         self._synced = set()
         self.net_input = None
+        self._input_fn = net_input if net_input is not None else _net_input
         self._in_key = None
         if self.use_side:
             self.main = torch.cuda.current_stream()
@@ -189,7 +192,7 @@ class GraphPlan:
                 # the network's input features (centred coordinates + colours, models/SPH3D_s3dis.py:11-19,38-41) depend on the
                 # batch only: prepared here, ahead of the feature path (one reduction + four small kernels, 60 us of main-stream time)
                 if prepare_input:
-                    self.net_input = _net_input(points, config)
+                    self.net_input = self._input_fn(points, config)
                     self._in_key = (points.data_ptr(), points._version, tuple(points.shape))
                     self._in_ev = torch.cuda.Event()
                     self._in_ev.record(s_fps)
@@ -380,7 +383,7 @@ class GraphPlan:
                 and self._in_key == (points.data_ptr(), points._version, tuple(points.shape))):
             self._sync(("input",), self._in_ev, [self.net_input])
             return self.net_input
-        return _net_input(points, self.config)
+        return self._input_fn(points, self.config)
 
     def enc(self, l):
         """encoder level l: intra graph + bins of xyz_l"""
@@ -420,11 +423,14 @@ def build_graphs(points, config, overlap=True):
     return plan
 
 
-def get_model(points, is_training, config=None, graphs=None, points_ready=None):
-    """models/SPH3D_s3dis.py:35-113 (config lists are not reversed in place here)."""
+def get_model(points, is_training, config=None, graphs=None, points_ready=None, net_input=None):
+    """models/SPH3D_s3dis.py:35-113 (config lists are not reversed in place here).  net_input: GraphPlan's (a plan handed in as
+    `graphs` must have been built with the same one)."""
     end_points = {}
     reuse = None
-    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready)
+    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready, net_input=net_input)
+    if net_input is not None and plan._input_fn is not net_input:
+        raise ValueError("get_model: `graphs` was built with another net_input")
     net = plan.input(points)
     net = s3g_util.pointwise_conv3d(net, config.mlp, 'mlp1', weight_decay=config.weight_decay,
                                     with_bn=config.with_bn, with_bias=config.with_bias, reuse=reuse,
