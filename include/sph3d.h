@@ -618,6 +618,38 @@ int sph3d_shape_iou(int B, int C, int num_blocks, long long total_rows, const fl
                     const int* part_n, int* pred, int* inter, int* pred_cnt, int* gt_cnt, int* correct, long long* nonfinite,
                     sph3d_stream_t stream);
 
+/* ---- the ModelNet40 classification evaluation on the device (modelnet40_cls/evaluate_modelnet.py:149-223; csrc/clseval.hip;
+ * harness/clseval.py states every entry in numpy).  Every buffer is the caller's; nothing is allocated, no floating-point atomic
+ * is used, and every id and label is checked against its range before an address is formed.
+ *   clsfeed_assemble     the whole-shape batch: sph3d_objfeed_assemble's pool, draws, purposes and counters (csrc/feed_draws.hpp),
+ *                        without the label output and with two more arguments.  order = 1: slot i reads row i of its shape — the
+ *                        stored order the reference evaluates in (evaluate_modelnet.py:170-177; farthest-point sampling starts from
+ *                        row 0) —, slots i >= n write zeros and index -1; order = 0: the feed's draw.  swap_yz = 1 exchanges
+ *                        columns 1 and 2 of the row before any transform: `batch_xyz[:, :, [0, 2, 1]]` of evaluate_modelnet.py:173
+ *                        and train_modelnet.py:278,337.  recipe [B] int32 (device): bits 1 TURN, 2 TILT, 4 SCALE, 8 SHIFT
+ *                        (evaluate_modelnet.py:71-78, train_modelnet.py:104-113; utils/data_util.py:47-61,140-204); the kernel reads
+ *                        no other bit, and the binding refuses a mask above 15 before it uploads it.  A mask of 0 copies bit for
+ *                        bit.  -> points [B,num_point,3] fp32, index [B,num_point] int32 (nullable).  A shape id outside [0, P) or
+ *                        an offset pair outside [0, T] reads nothing: zeros and index -1.  B <= 65535, B * num_point <= 2^31 - 1.
+ *   cls_vote_accumulate  `batch_pred_sum += pred_val` of evaluate_modelnet.py:180,196 in float64: sums[b,c] = 0.0 + (double)
+ *                        logits[b,c] for vote 0 (the sum starts from np.zeros, so a logit of -0.0 leaves +0.0), sums[b,c] +=
+ *                        (double)logits[b,c] for the votes after it — one float64 add per vote, in vote order.  With votes_out
+ *                        [P,num_votes,C] fp32 (nullable) the logits are also stored at [shape_ids[b], vote, :], the `pred_votes`
+ *                        of :194; a shape id outside [0, num_blocks) stores none.  0 <= vote < num_votes, C <= 64.
+ *   cls_vote_finalize    evaluate_modelnet.py:198-207: pred[shape_ids[b]] = first maximum of sums[b, :] (a NaN counts as a
+ *                        maximum, as np.argmax); with label = category[shape_ids[b]]: counters[0] (seen) += 1, class_seen[label]
+ *                        += 1, counters[2] (nonfinite) += 1 if one of the C sums is a NaN or an infinity, and counters[1]
+ *                        (correct) and class_correct[label] += 1 if pred == label.  A label outside [0, C) counts in counters[3]
+ *                        (bad_label) only; a shape id outside [0, num_blocks) counts nothing and writes no prediction.
+ *                        pred [P], counters [4], class_seen [C], class_correct [C] int32 are accumulated, not zeroed. */
+int sph3d_clsfeed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                           const int* shape_ids, unsigned long long seed, unsigned long long step, const int* recipe, int order,
+                           int swap_yz, float* points, int* index, sph3d_stream_t stream);
+int sph3d_cls_vote_accumulate(int B, int C, const float* logits, int vote, int num_votes, double* sums, const int* shape_ids,
+                              float* votes_out, int num_blocks, sph3d_stream_t stream);
+int sph3d_cls_vote_finalize(int B, int C, const double* sums, const int* shape_ids, const int* category, int num_blocks, int* pred,
+                            int* counters, int* class_seen, int* class_correct, sph3d_stream_t stream);
+
 /* ---- scene-level evaluation (post-merging/s3dis_merge.m:42-82, scannet_merge.m:28-55; csrc/scene.hip): the blocks' vote sums are
  * normalised per row, merged into a per-scene array through the records' index_label, and the arg-max is lifted to the
  * full-resolution cloud through a nearest-neighbour search.  harness/scenemerge.py states every entry in numpy, bit for bit, the

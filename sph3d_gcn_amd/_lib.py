@@ -85,6 +85,9 @@ SIGNATURES = {
     "sph3d_objfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
     "sph3d_facadefeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
     "sph3d_shape_iou": (_I, [_I, _I, _I, _L, _P, _P, _P, _L, _L, _P, _P, _P] + [_P] * 6 + [_P]),
+    "sph3d_clsfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, _I, _I, _P, _P, _P]),
+    "sph3d_cls_vote_accumulate": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _I, _P]),
+    "sph3d_cls_vote_finalize": (_I, [_I, _I, _P, _P, _P, _I] + [_P] * 4 + [_P]),
     "sph3d_vote_workspace": (_S, [ctypes.c_longlong]),
     "sph3d_vote_begin": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong] + [_P] * 5 + [_P, _S, _P]),
     "sph3d_vote_accumulate": (_I, [_I, _I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _I, _P, _P, _I]
