@@ -9,8 +9,8 @@ written"), the gradient's workspace — slabs and hub list — with 0xFF bytes (
 written this call shows), transposed graphs are built with sph3d_graph_transpose itself.  assert_conv prints the used fraction
 of each derived bound behind a [form] tag: DESIGN.md §2 quotes the maxima.
 
-Left out on purpose: the 32-bit-offset fall-backs (N C or M C r near 2^32, N above 2^24), neighbour ids outside [0, N), and
-the separable kernels (sepconv.hip, sepring.hip)."""
+Left out on purpose: the 32-bit-offset fall-backs (N C or M C r near 2^32, N above 2^24) and neighbour ids outside [0, N).  The
+separable kernels (sepconv.hip, sepring.hip) are held the same way in tests/test_gpu_sep_forms.py."""
 import os
 
 import numpy as np
