@@ -382,11 +382,31 @@ int sph3d_spatial_order(int B, int N, const float* xyz, int* order, sph3d_stream
 int sph3d_pointwise_gemm(int R, int Cin, int Cout,
                          const float* X, const float* W, const float* bias, int act,
                          int trans_w, float* Y, sph3d_stream_t stream);
-/* How the whole-tile products (all three, and the statistics variant) run — process-wide, returns the previous mode:
+/* How the products (all three, and the statistics variant) run — process-wide, returns the previous mode:
  *   1 (default): bf16 matrix pipe with every fp32 operand cut EXACTLY into three bf16 pieces and the six leading piece products
  *      accumulated in fp32 (csrc/gemm.hip: gemm_split_mfma) — fp32-sized error (<= 2^-23 per product), 2.7x the fp32 MFMA rate;
- *   0: v_mfma_f32_32x32x2_f32, a k-ordered fp32 fmaf chain (what ragged shapes always take);  other values: query only. */
+ *   0: v_mfma_f32_32x32x2_f32, a k-ordered fp32 fmaf chain;  other values: query only.
+ * Ragged shapes and misaligned operands take the same kernels with element-wise bounds, in either mode; only the very narrow ones
+ * (NN / NT: Cin < 16 or Cout < 32; TN: Cin < 32 or Cout < 32) take the fp32 kernels in mode 1 too. */
 int sph3d_pointwise_gemm_mode(int mode);
+/* The launch a product takes, answered on the host (no device is touched): csrc/gemm.hip states the choice once (gemm_plan) and
+ * every entry point below launches what it says.
+ *   product: SPH3D_GEMM_NN / _NT (sph3d_pointwise_gemm with trans_w = 0 / 1), _NN_STATS (sph3d_pointwise_gemm_bnstats), _TN
+ *            (sph3d_pointwise_gemm_tn); R, Cin, Cout as that entry point takes them
+ *   aligned: 1 if every operand pointer of the call is 16-byte aligned;  mode: 0 | 1, or -1 for the current process-wide mode;
+ *   exchange_ok: 1 if the stream can supply the exchange buffer (0: a stream under capture that has none yet)
+ *   out[SPH3D_GEMM_PLAN_FIELDS], in this order:
+ *     0 pipe (0 fp32 MFMA, 1 split bf16)   1 bm  2 bn  3 bk (tile extents)   4 guard (element-wise bounds)   5 stats (statistics epilogue)
+ *     6 xs (workgroups per tile of the in-kernel exchange, 1: none)   7 nsplit  8 kchunk (the weight gradient's slabs; kchunk: the k
+ *     extent of one workgroup, 0: all of k)   9 reduce (1: the slab-sum launch follows)   10 grid (workgroups of the main launch; 0: no
+ *     launch, the statistics product outside its shapes)   11 stats_blocks (sph3d_pointwise_gemm_bnstats_blocks; _NN_STATS only)
+ * -> SPH3D_OK, or SPH3D_EINVAL for an unknown product, dimensions that are not positive, a flag outside the above or out == NULL. */
+#define SPH3D_GEMM_NN 0
+#define SPH3D_GEMM_NT 1
+#define SPH3D_GEMM_NN_STATS 2
+#define SPH3D_GEMM_TN 3
+#define SPH3D_GEMM_PLAN_FIELDS 12
+int sph3d_pointwise_gemm_plan(int product, int R, int Cin, int Cout, int aligned, int mode, int exchange_ok, int* out);
 /* Products whose tile grid is too small to fill the chip run several workgroups per tile that exchange their partial accumulators inside
  * the launch (csrc/gemm.hip); the waiting workgroup's spin is bounded.  -> number of launches that ever gave up waiting
  * (never expected: 0; synchronises with the device; -1 if the counter cannot be read). */

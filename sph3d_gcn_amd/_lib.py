@@ -72,6 +72,7 @@ SIGNATURES = {
     "sph3d_farthest_point_sample": (_I, [_I] * 3 + [_P, _P, _P, _S, _P]),
     "sph3d_pointwise_gemm": (_I, [_I] * 3 + [_P, _P, _P, _I, _I, _P, _P]),
     "sph3d_pointwise_gemm_mode": (_I, [_I]),
+    "sph3d_pointwise_gemm_plan": (_I, [_I] * 7 + [_P]),
     "sph3d_pointwise_gemm_tn_workspace": (_S, [_I] * 3),
     "sph3d_pointwise_gemm_tn": (_I, [_I] * 3 + [_P, _P, _P, _P, _S, _P]),
     "sph3d_elu_bn_workspace": (_S, [_I] * 2),

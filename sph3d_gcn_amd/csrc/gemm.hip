@@ -18,7 +18,9 @@
 // Ragged edges (Cin = 3, Cout = 13, R not a multiple of 128) take guarded scalar loads / stores.
 // TN splits R over workgroups; every split writes its partial tile to a workspace slab and a second kernel adds the
 // slabs in a fixed order (deterministic, no float atomics).
+#include <string.h>
 #include <atomic>
+#include <type_traits>
 #include "common.hpp"
 
 namespace sph3d {
@@ -856,8 +858,8 @@ static unsigned gemm_grid(long long tiles_m, long long tiles_n, long long nsplit
 
 static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
-// whole-tile products on the bf16 pipe with split operands (gemm_split_mfma); sph3d_pointwise_gemm_mode(0) selects the exact
-// fp32-MFMA kernels instead.  Ragged shapes always take the fp32 kernels
+// products on the bf16 pipe with split operands (gemm_split_mfma); sph3d_pointwise_gemm_mode(0) selects the exact fp32-MFMA kernels
+// instead.  Ragged or misaligned products take the guarded variants of either; the very narrow ones always the fp32 ones (gemm_plan)
 static std::atomic<int> g_split_mode{1};
 static bool split_on() { return g_split_mode.load(std::memory_order_relaxed) != 0; }
 
@@ -867,9 +869,8 @@ constexpr long long kMinTiles = 512;
 
 // In-kernel split-K exchange (gemm_split_mfma<..., XS>): splits per tile for a whole-tile product that would run as T 64 x 64 tiles
 // (grid Tg after XCD padding), 1 = do not split.  Up to ~1024 workgroups (4 per CU: all resident), at least 256 of k per split.
-constexpr int kXsCap = 4;             // at most this many splits of a product (the weight gradient's short path: 8)
-constexpr int kXsMaxWgs = 1024;
-constexpr int kXsMaxTg = 384;
+constexpr int kXsCap = 4;             // at most this many splits of a product (the weight gradient's short path: kTnXsCap)
+constexpr int kXsMaxWgs = 1024, kXsMaxTg = 384;
 static int xs_splits(long long Tg, int Kd, int bk, int cap)
 {
     int ns = (int)(kXsMaxWgs / (Tg > 0 ? Tg : 1));
@@ -879,110 +880,17 @@ static int xs_splits(long long Tg, int Kd, int bk, int cap)
     return ns < 1 ? 1 : ns;
 }
 constexpr size_t kXsFlagBytes = 16384;      // 4096 arrival counters in front of the slabs
-// -> the exchange buffer of the stream (counters zero), or nullptr (capture in progress and nothing allocated yet / out of memory /
-// too many tiles): the caller then launches the ordinary kernel
-static char* xs_buffer(hipStream_t st, long long ntile, int nsplit, size_t tile_floats)
+// -> the exchange buffer of the stream (counters zero) for a plan with the exchange, or nullptr (no exchange planned / capture in
+// progress and nothing allocated yet / out of memory / too many tiles): the caller then plans again without the exchange
+static char* xs_buffer(hipStream_t st, int M, int N, int nsplit)
 {
-    if (ntile > (long long)(kXsFlagBytes / sizeof(int))) return nullptr;
-    return (char*)stream_scratch(st, kXsFlagBytes + sizeof(float) * (size_t)(nsplit - 1) * (size_t)ntile * tile_floats, 1);
-}
-
-template <bool AK, bool BKM, bool GUARD>
-static void launch_gemm_tiles(int M, int N, int Kd, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                              const float* bias, int act, hipStream_t st)
-{
-    // tile choice: see kMinTiles
-    auto ntiles = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    // (BK = 32 at two workgroups per CU for the big grids: measured slower than BK = 16 at four, before and after the
-    //  round-2 register fix: 0.101 vs 0.094 ms at (131072, 256 -> 128))
-    if constexpr (GUARD) {
-        // ragged shapes (the ModelNet plan's 35 / 67 / 131-channel layers, Cin = 3): the same kernels with element-wise bounds on the
-        // loads and stores; not for the very narrow ones (K < 16 or N < 32: mostly zero padding on the matrix pipe)
-        if (split_on() && Kd >= 16 && N >= 32) {
-            if (N > 64 && ntiles(128, 128) >= kMinTiles)
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 128, 128, 16, false, false, true>), dim3(gemm_grid((M + 127) / 128, (N + 127) / 128)),
-                                   dim3(256), 0, st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            else if (!BKM && N <= 64 && ntiles(128, 64) >= kMinTiles)
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 128, 64, 16, false, false, true>), dim3(gemm_grid((M + 127) / 128, (N + 63) / 64)),
-                                   dim3(256), 0, st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            else
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 64, 64, 16, false, false, true>), dim3(gemm_grid((M + 63) / 64, (N + 63) / 64)), dim3(256),
-                                   0, st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            return;
-        }
-    }
-    if constexpr (!GUARD) {
-        if (split_on()) {
-            // 64 x 64 tiles take two MFMA k-steps per barrier where K allows
-            if (N > 64 && ntiles(128, 128) >= kMinTiles)
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 128, 128, 16, false, false>), dim3(gemm_grid((M + 127) / 128, (N + 127) / 128)), dim3(256),
-                                   0, st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            else if (!BKM && N <= 64 && ntiles(128, 64) >= kMinTiles)
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 128, 64, 16, false, false>), dim3(gemm_grid((M + 127) / 128, (N + 63) / 64)), dim3(256), 0,
-                                   st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            else if (Kd % 32 == 0) {
-                const long long Tg = gemm_grid(M / 64, N / 64);
-                const int ns = xs_splits(Tg, Kd, 32, kXsCap);
-                char* xb = ns > 1 ? xs_buffer(st, (long long)(M / 64) * (N / 64), ns, 64 * 64) : nullptr;
-                if (xb != nullptr)
-                    hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 64, 64, 32, false, false, false, true>), dim3((unsigned)(Tg * ns)), dim3(256), 0, st,
-                                       M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, Kd / ns, nullptr, ns, (float*)(xb + kXsFlagBytes), (int*)xb);
-                else
-                    hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 64, 64, 32, false, false>), dim3(gemm_grid((M + 63) / 64, (N + 63) / 64)), dim3(256), 0,
-                                       st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            } else
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, 64, 64, 16, false, false>), dim3(gemm_grid((M + 63) / 64, (N + 63) / 64)), dim3(256), 0,
-                                   st, M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-            return;
-        }
-    }
-    if (BKM && !(N > 64 && ntiles(128, 128) >= kMinTiles)) {
-        // input-gradient product (W stored [n][k]) below 2 big tiles per CU: 64x64 tiles (0.071 vs 0.088 ms at
-        // (6144, 2048 -> 256) ... ) -- with >= kMinTiles big tiles the 128x128 kernel wins since its prefetch registers stopped
-        // going through scratch: 0.100 vs 0.106 ms at (131072, 256 -> 128), 0.089 vs 0.098 at (32768, 512 -> 256),
-        // 0.062 vs 0.071 at (6144, 256 -> 2048)
-        hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, 64, 64, BKS, false, GUARD>), dim3(gemm_grid((M + 63) / 64, (N + 63) / 64)), dim3(256), 0, st, M,
-                           N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-    } else if (N > 64 && ntiles(128, 128) >= kMinTiles) {
-        constexpr int BKX = BKS;
-        hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, 128, 128, BKX, false, GUARD>), dim3(gemm_grid((M + 127) / 128, (N + 127) / 128)), dim3(256), 0, st,
-                           M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-    } else if (N <= 64 && ntiles(128, 64) >= kMinTiles) {      // (wider outputs with fewer rows: 64x64, e.g. 0.092 vs 0.111 ms at (32768, 1024 -> 128))
-        hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, 128, 64, BKS, false, GUARD>), dim3(gemm_grid((M + 127) / 128, (N + 63) / 64)), dim3(256), 0, st,
-                           M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-    } else {
-        hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, 64, 64, BKS, false, GUARD>), dim3(gemm_grid((M + 63) / 64, (N + 63) / 64)), dim3(256), 0, st, M,
-                           N, Kd, A, lda, B, ldb, C, ldc, bias, act, 0);
-    }
-}
-
-template <bool AK, bool BKM>
-static int launch_gemm(int M, int N, int Kd, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                       const float* bias, int act, hipStream_t st)
-{
-    // unguarded kernels need whole tiles in every variant the tile chooser may pick (128 | M, 128 | N or 64 | N, 16 | K)
-    const bool whole = (M % 128 == 0) && (N % 64 == 0) && (N <= 64 || N % 128 == 0) && (Kd % BKS == 0) &&
-                       (lda % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && aligned16(A) && aligned16(B) && aligned16(C);
-    if (whole) launch_gemm_tiles<AK, BKM, false>(M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, st);
-    else launch_gemm_tiles<AK, BKM, true>(M, N, Kd, A, lda, B, ldb, C, ldc, bias, act, st);
-    return check_launch("sph3d_pointwise_gemm");
-}
-
-// forward product + BN partial statistics: unguarded NN tiles only.  -> row blocks of the statistics (2 per tile row), 0 if
-// the shape does not qualify (the caller then runs the plain product and the op's own statistics pass)
-static int nn_stats_tile(int M, int N, int Kd, int& bm, int& bn)
-{
-    const bool whole = (M % 128 == 0) && (N % 64 == 0) && (N <= 64 || N % 128 == 0) && (Kd % BKS == 0) && (Kd % 4 == 0) && (N % 4 == 0);
-    if (!whole) return 0;
-    auto ntiles = [&](int a, int b) { return (long long)((M + a - 1) / a) * ((N + b - 1) / b); };
-    if (N > 64 && ntiles(128, 128) >= kMinTiles) { bm = 128; bn = 128; }
-    else if (ntiles(128, 64) >= kMinTiles) { bm = 128; bn = 64; }      // (N > 64 too: 32768 x 1024 -> 128 measured 81 vs 90 us with 64 x 64)
-    else { bm = 64; bn = 64; }
-    return 2 * (M / bm);
+    const long long ntile = (long long)(M / 64) * (N / 64);
+    if (nsplit < 2 || ntile > (long long)(kXsFlagBytes / sizeof(int))) return nullptr;
+    return (char*)stream_scratch(st, kXsFlagBytes + sizeof(float) * (size_t)(nsplit - 1) * (size_t)ntile * 64 * 64, 1);
 }
 
 // split-K plan for the weight gradient: enough (tile, split) workgroups to fill 256 CUs, k chunks multiple of BK
-static void tn_plan(int R, int Cin, int Cout, int& bn, int& tiles, int& nsplit, int& kchunk)
+static void tn_slabs(int R, int Cin, int Cout, int& bn, int& tiles, int& nsplit, int& kchunk)
 {
     // the weight gradient always has thousands of (tile, split) workgroups: wide k-tile
     bn = Cout > 64 ? 128 : 64;
@@ -1004,6 +912,160 @@ static void tn_plan(int R, int Cin, int Cout, int& bn, int& tiles, int& nsplit, 
     nsplit = (R + kchunk - 1) / kchunk;
 }
 
+// ---- the plan: everything the host decides about a product's launch, stated once (sph3d_pointwise_gemm_plan reports it) ---------
+enum { kNN = SPH3D_GEMM_NN, kNT = SPH3D_GEMM_NT, kNNS = SPH3D_GEMM_NN_STATS, kTN = SPH3D_GEMM_TN };
+
+struct GemmPlan {
+    int bf16;                       // pipe: 1 gemm_split_mfma (bf16 MFMA, split operands), 0 gemm_f32_mfma
+    int bm, bn, bk, guard, stats;   // tile extents; element-wise bounds on loads and stores; the statistics epilogue
+    int xs;                         // workgroups per tile of the in-kernel exchange, 1: none
+    int nsplit, kchunk, reduce;     // the weight gradient's slabs (kchunk: k extent of one workgroup, 0: all of k); gemm_reduce_splits follows
+    int grid;                       // workgroups of the main launch; 0: no kernel (the statistics product outside its shapes)
+    int stats_blocks;               // row blocks of the statistics (2 per tile row), 0 if the shape does not qualify
+};
+
+// The plan of a product from its dimensions as the C ABI names them.  In the kernels' terms, C[M,N] = A[M,Kd] B[Kd,N]:
+//   NN, NNS, NT : M = R,   N = Cout, Kd = Cin;  lda = Cin, ldb = Cout (NT: Cin, W stored [Cout][Cin]), ldc = Cout
+//   TN          : M = Cin, N = Cout, Kd = R;    lda = Cin, ldb = ldc = Cout
+// aligned: every operand pointer of the call is 16-byte aligned.  split: the product mode.  exchange_ok: the stream can supply the
+// exchange buffer (xs_buffer); without one NN / NT / NNS keep tile and k-step and lose the exchange, TN takes its slab plan.
+static GemmPlan gemm_plan(int product, int R, int Cin, int Cout, bool aligned, bool split, bool exchange_ok)
+{
+    const bool tn = product == kTN, nt = product == kNT, nns = product == kNNS;
+    const int M = tn ? Cin : R, N = Cout, Kd = tn ? R : Cin;
+    GemmPlan p = {};
+    p.xs = p.nsplit = 1, p.stats = nns;
+    auto ntiles = [&](int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
+    // the unguarded kernels need whole tiles in every variant the tile ladder may pick: 128 | M, 64 | N and 128 | N above 64,
+    // kstep | Kd (BKS; the weight gradient: its slab's kchunk) — and float4 rows: 16-byte aligned pointers and leading dimensions
+    // that are multiples of 4.  The latter follow from the whole tiles: lda is Kd (a multiple of 16) or, for TN, M (of 128); ldb
+    // is Kd (NT) or N (of 64); ldc is N.  So the lda / ldb / ldc % 4 terms of a general-stride launcher have no say here
+    auto whole = [&](int kstep) { return M % 128 == 0 && N % 64 == 0 && (N <= 64 || N % 128 == 0) && Kd % kstep == 0; };
+    // 64 x 64 x 32 tiles, up to `cap` workgroups per tile that exchange their accumulators in the kernel -> taken or not.  (xs_buffer
+    // also refuses more tiles than its 4096 counters: with Tg <= kXsMaxTg = 384 that never binds, and the plan does not repeat it)
+    auto exchange = [&](int cap) {
+        const long long Tg = gemm_grid(M / 64, N / 64);
+        const int ns = xs_splits(Tg, Kd, 32, cap);
+        if (ns < 2 || !exchange_ok) return false;
+        p.bf16 = 1; p.bm = p.bn = 64; p.bk = 32; p.guard = 0;
+        p.xs = ns; p.kchunk = Kd / ns; p.grid = (int)(Tg * ns);
+        return true;
+    };
+    if (tn) {
+        // short products (few rows of k, many output tiles): 64 x 64 tiles with the in-kernel exchange — up to 8 splits whose slabs are
+        // 16 KB — instead of 128 x 128 tiles + slab-sum launch.  (The exchange with 128 x 128 tiles and 8-16 splits was measured and is
+        // SLOWER than the slab-sum kernel: 72 vs 38, 82 vs 50, 84 vs 62 us — split 0 reads 7-15 64-KB slabs past the cache, one dword per
+        // lane and instruction; profiles/r06_exp_gemm_xs.log.)  kTnXsRows: largest R that takes this path
+        constexpr int kTnXsRows = 2048, kTnXsCap = 8;
+        if (split && aligned && R <= kTnXsRows && Cin % 64 == 0 && Cout % 64 == 0 && R % 32 == 0 && exchange(kTnXsCap)) return p;
+        int tiles;
+        tn_slabs(R, Cin, Cout, p.bn, tiles, p.nsplit, p.kchunk);
+        p.bm = 128;
+        p.guard = !(whole(p.kchunk) && aligned);
+        // ragged shapes: the split kernel with element-wise bounds, not for the very narrow ones (mostly zero padding on the matrix pipe)
+        p.bf16 = split && (!p.guard || (Cin >= 32 && Cout >= 32));
+        // whole tiles: BK = 16 at four workgroups per CU (8 + 8 prefetch registers with the 2x4 transposing units): 0.786 vs
+        // 0.855 ms over the step's shapes against BK = 32 at two per CU; the guarded fp32 kernel (two per CU either way) keeps BK = 32
+        p.bk = (p.bf16 || !p.guard) ? BKS : BKL;
+        p.reduce = p.nsplit > 1;
+        p.grid = gemm_grid(tiles, 1, p.nsplit);
+        return p;
+    }
+    const bool w = whole(BKS);
+    if (nns && !w) return p;        // statistics: unguarded tiles only (the caller runs the plain product and the op's own statistics pass)
+    // the tile ladder (kMinTiles), the same on both pipes.  128 x 64: outputs of at most 64 columns (wider ones with fewer rows: 64 x 64,
+    // e.g. 0.092 vs 0.111 ms at (32768, 1024 -> 128)); the statistics product for N > 64 too (32768 x 1024 -> 128 measured 81 vs 90 us
+    // with 64 x 64); never the input-gradient product (W stored [n][k]), which below 2 big tiles per CU runs 64 x 64 (0.071 vs 0.088 ms
+    // at (6144, 2048 -> 256)) — with >= kMinTiles big tiles 128 x 128 wins since its prefetch registers stopped going through scratch:
+    // 0.100 vs 0.106 ms at (131072, 256 -> 128), 0.089 vs 0.098 at (32768, 512 -> 256), 0.062 vs 0.071 at (6144, 256 -> 2048).
+    // (BK = 32 at two workgroups per CU for the big grids: slower than BK = 16 at four: 0.101 vs 0.094 ms at (131072, 256 -> 128))
+    const bool big = N > 64 && ntiles(128, 128) >= kMinTiles;
+    const bool mid = !nt && (nns || N <= 64) && ntiles(128, 64) >= kMinTiles;
+    const int bm = big || mid ? 128 : 64, bn = big ? 128 : 64;
+    if (nns) {
+        p.stats_blocks = 2 * (M / bm);
+        if (!aligned) return p;
+    }
+    p.guard = !(w && aligned);
+    // ragged shapes (the ModelNet plan's 35 / 67 / 131-channel layers, Cin = 3): the same kernels with element-wise bounds on the
+    // loads and stores; on the bf16 pipe not for the very narrow ones (K < 16 or N < 32: mostly zero padding on the matrix pipe)
+    p.bf16 = split && (!p.guard || (Kd >= 16 && N >= 32));
+    // unguarded 64 x 64 tiles on the bf16 pipe take two MFMA k-steps per barrier where K allows, and the exchange where it pays
+    const bool bk32 = p.bf16 && !p.guard && bm == 64 && Kd % 32 == 0;
+    if (bk32 && exchange(kXsCap)) return p;
+    p.bm = bm; p.bn = bn; p.bk = bk32 ? 32 : BKS;
+    p.grid = gemm_grid((M + bm - 1) / bm, (N + bn - 1) / bn);
+    return p;
+}
+
+// ---- the launcher: the kernel a plan names.  Only the instantiations some plan reaches are compiled ------------------------------
+constexpr bool plan_reaches(int product, bool bf16, int bm, int bn, int bk, bool guard, bool xs)
+{
+    // 64 x 64 x 32 on the bf16 pipe: every product's exchange, and NN / NT / NNS without it
+    if (xs || (bf16 && bk == 32)) return bf16 && !guard && bm == 64 && bk == 32 && (xs || product != kTN);
+    if (product == kTN) return bm == 128 && bk == (!bf16 && guard ? BKL : BKS);        // the slab kernels
+    return bk == BKS && !(product == kNNS && guard) && !(product == kNT && bm == 128 && bn == 64);
+}
+
+struct GemmOperands {       // C[M,N] = A[M,Kd] B[Kd,N]
+    int M, N, Kd; const float* A; int lda; const float* B; int ldb; float* C; int ldc; const float* bias; int act; float* stats;
+};
+
+template <int PRODUCT>
+static int launch_plan(const GemmPlan& p, const GemmOperands& o, char* xb, hipStream_t st)
+{
+    constexpr bool AK = PRODUCT != kTN, BKM = PRODUCT == kNT, STATS = PRODUCT == kNNS;
+    const int ns = p.xs > 1 ? p.xs : p.nsplit;
+    auto go = [&](auto BF16, auto BMT, auto BN, auto BK, auto GUARD, auto XS) {
+        if constexpr (plan_reaches(PRODUCT, BF16(), BMT(), BN(), BK(), GUARD(), XS())) {
+            constexpr bool SPLITK = PRODUCT == kTN && !XS();
+            if constexpr (BF16())
+                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, BMT(), BN(), BK(), SPLITK, STATS, GUARD(), XS()>), dim3(p.grid), dim3(256), 0, st,
+                                   o.M, o.N, o.Kd, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.act, p.kchunk, o.stats, ns,
+                                   XS() ? (float*)(xb + kXsFlagBytes) : nullptr, XS() ? (int*)xb : nullptr);
+            else
+                hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, BMT(), BN(), BK(), SPLITK, GUARD(), STATS>), dim3(p.grid), dim3(256), 0, st, o.M,
+                                   o.N, o.Kd, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.act, p.kchunk, o.stats, ns);
+            return (int)SPH3D_OK;
+        }
+        set_error("pointwise_gemm: product %d has no kernel for pipe %d, tile %d x %d x %d, guard %d", PRODUCT, p.bf16, p.bm, p.bn, p.bk, p.guard);
+        return (int)SPH3D_EUNSUPPORTED;
+    };
+    using std::integral_constant;
+    const std::true_type T{};
+    const std::false_type F{};
+    auto with_guard = [&](auto BF16, auto BMT, auto BN, auto BK) {
+        if (p.xs > 1) return go(BF16, BMT, BN, BK, F, T);
+        return p.guard ? go(BF16, BMT, BN, BK, T, F) : go(BF16, BMT, BN, BK, F, F);
+    };
+    auto with_tile = [&](auto BF16, auto BK) {
+        if (p.bm == 128 && p.bn == 128) return with_guard(BF16, integral_constant<int, 128>{}, integral_constant<int, 128>{}, BK);
+        if (p.bm == 128) return with_guard(BF16, integral_constant<int, 128>{}, integral_constant<int, 64>{}, BK);
+        return with_guard(BF16, integral_constant<int, 64>{}, integral_constant<int, 64>{}, BK);
+    };
+    auto with_bk = [&](auto BF16) { return p.bk == 32 ? with_tile(BF16, integral_constant<int, 32>{}) : with_tile(BF16, integral_constant<int, 16>{}); };
+    return p.bf16 ? with_bk(T) : with_bk(F);
+}
+
+static bool plan_args_ok(int R, int Cin, int Cout) { return R > 0 && Cin > 0 && Cout > 0; }
+
+// NN, NT and NNS: plan, fetch the stream's exchange buffer if the plan wants one (none, e.g. under capture: plan again without), launch
+static int run_forward(int product, int R, int Cin, int Cout, const float* X, const float* W, const float* bias, int act, float* Y,
+                       float* partial, hipStream_t st, const char* what)
+{
+    const bool aligned = aligned16(X) && aligned16(W) && aligned16(Y), split = split_on();
+    GemmPlan p = gemm_plan(product, R, Cin, Cout, aligned, split, true);
+    if (p.grid == 0) {
+        set_error("%s: shape (%d, %d -> %d) needs whole tiles and 16-byte aligned operands", what, R, Cin, Cout);
+        return SPH3D_EUNSUPPORTED;
+    }
+    char* xb = xs_buffer(st, R, Cout, p.xs);
+    if (p.xs > 1 && xb == nullptr) p = gemm_plan(product, R, Cin, Cout, aligned, split, false);
+    const GemmOperands o = {R, Cout, Cin, X, Cin, W, product == kNT ? Cin : Cout, Y, Cout, bias, act, partial};
+    const int rc = product == kNT ? launch_plan<kNT>(p, o, xb, st) : product == kNNS ? launch_plan<kNNS>(p, o, xb, st) : launch_plan<kNN>(p, o, xb, st);
+    return rc != SPH3D_OK ? rc : check_launch(what);
+}
+
 }  // namespace sph3d
 
 using namespace sph3d;
@@ -1021,137 +1083,74 @@ extern "C" int sph3d_pointwise_gemm_mode(int mode)
     return g_split_mode.load();
 }
 
+extern "C" int sph3d_pointwise_gemm_plan(int product, int R, int Cin, int Cout, int aligned, int mode, int exchange_ok, int* out)
+{
+    SPH3D_REQUIRE(product >= kNN && product <= kTN && plan_args_ok(R, Cin, Cout), "pointwise_gemm_plan: bad product %d or dims R=%d Cin=%d Cout=%d",
+                  product, R, Cin, Cout);
+    SPH3D_REQUIRE((aligned | 1) == 1 && (exchange_ok | 1) == 1 && mode >= -1 && mode <= 1 && out != nullptr,
+                  "pointwise_gemm_plan: aligned and exchange_ok are 0 or 1, mode is -1, 0 or 1, out is not NULL");
+    const GemmPlan p = gemm_plan(product, R, Cin, Cout, aligned != 0, mode < 0 ? split_on() : mode != 0, exchange_ok != 0);
+    static_assert(sizeof(GemmPlan) == SPH3D_GEMM_PLAN_FIELDS * sizeof(int), "the plan is the documented fields, in their order");
+    memcpy(out, &p, sizeof(p));
+    return SPH3D_OK;
+}
+
 extern "C" int sph3d_pointwise_gemm(int R, int Cin, int Cout, const float* X, const float* W, const float* bias, int act,
                                     int trans_w, float* Y, sph3d_stream_t stream)
 {
     SPH3D_REQUIRE(R >= 0 && Cin > 0 && Cout > 0, "pointwise_gemm: bad dims R=%d Cin=%d Cout=%d", R, Cin, Cout);
     SPH3D_REQUIRE(act == 0 || act == 1, "pointwise_gemm: act must be 0 (none) or 1 (ELU), got %d", act);
     if (R == 0) return SPH3D_OK;
-    hipStream_t st = as_stream(stream);
     // Y[R,Cout] = X[R,Cin] * op(W);  trans_w: W is stored [Cout,Cin] (k contiguous), else [Cin,Cout] (n contiguous)
-    if (trans_w) return launch_gemm<true, true>(R, Cout, Cin, X, Cin, W, Cin, Y, Cout, bias, act, st);
-    return launch_gemm<true, false>(R, Cout, Cin, X, Cin, W, Cout, Y, Cout, bias, act, st);
+    return run_forward(trans_w ? kNT : kNN, R, Cin, Cout, X, W, bias, act, Y, nullptr, as_stream(stream), "sph3d_pointwise_gemm");
 }
 
 extern "C" int sph3d_pointwise_gemm_bnstats_blocks(int R, int Cin, int Cout)
 {
-    int bm = 0, bn = 0;
-    return (R > 0 && Cin > 0 && Cout > 0) ? nn_stats_tile(R, Cout, Cin, bm, bn) : 0;
+    return plan_args_ok(R, Cin, Cout) ? gemm_plan(kNNS, R, Cin, Cout, true, split_on(), false).stats_blocks : 0;
 }
 
+// forward product + BN partial statistics (partial: sph3d_pointwise_gemm_bnstats_blocks row blocks)
 extern "C" int sph3d_pointwise_gemm_bnstats(int R, int Cin, int Cout, const float* X, const float* W, const float* bias, float* Y,
                                             float* partial, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && Cin > 0 && Cout > 0, "pointwise_gemm_bnstats: bad dims R=%d Cin=%d Cout=%d", R, Cin, Cout);
-    int bm = 0, bn = 0;
-    const int nblk = nn_stats_tile(R, Cout, Cin, bm, bn);
-    if (nblk == 0 || !aligned16(X) || !aligned16(W) || !aligned16(Y)) {
-        set_error("pointwise_gemm_bnstats: shape (%d, %d -> %d) needs whole tiles and 16-byte aligned operands", R, Cin, Cout);
-        return SPH3D_EUNSUPPORTED;
-    }
-    hipStream_t st = as_stream(stream);
-    const unsigned tiles = gemm_grid(R / bm, Cout / bn);
-    if (split_on()) {
-        if (bm == 128 && bn == 128)
-            hipLaunchKernelGGL((gemm_split_mfma<true, false, 128, 128, 16, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X, Cin, W,
-                               Cout, Y, Cout, bias, 0, 0, partial);
-        else if (bm == 128)
-            hipLaunchKernelGGL((gemm_split_mfma<true, false, 128, 64, 16, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X, Cin, W,
-                               Cout, Y, Cout, bias, 0, 0, partial);
-        else if (Cin % 32 == 0) {
-            const int ns = xs_splits(tiles, Cin, 32, kXsCap);
-            char* xb = ns > 1 ? xs_buffer(st, (long long)(R / 64) * (Cout / 64), ns, 64 * 64) : nullptr;
-            if (xb != nullptr)
-                hipLaunchKernelGGL((gemm_split_mfma<true, false, 64, 64, 32, false, true, false, true>), dim3(tiles * ns), dim3(256), 0, st, R, Cout,
-                                   Cin, X, Cin, W, Cout, Y, Cout, bias, 0, Cin / ns, partial, ns, (float*)(xb + kXsFlagBytes), (int*)xb);
-            else
-                hipLaunchKernelGGL((gemm_split_mfma<true, false, 64, 64, 32, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X, Cin, W,
-                                   Cout, Y, Cout, bias, 0, 0, partial);
-        } else
-            hipLaunchKernelGGL((gemm_split_mfma<true, false, 64, 64, 16, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X, Cin, W,
-                               Cout, Y, Cout, bias, 0, 0, partial);
-        return check_launch("sph3d_pointwise_gemm_bnstats");
-    }
-    if (bm == 128 && bn == 128)
-        hipLaunchKernelGGL((gemm_f32_mfma<true, false, 128, 128, BKS, false, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X,
-                           Cin, W, Cout, Y, Cout, bias, 0, 0, partial);
-    else if (bm == 128)
-        hipLaunchKernelGGL((gemm_f32_mfma<true, false, 128, 64, BKS, false, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X,
-                           Cin, W, Cout, Y, Cout, bias, 0, 0, partial);
-    else
-        hipLaunchKernelGGL((gemm_f32_mfma<true, false, 64, 64, BKS, false, false, true>), dim3(tiles), dim3(256), 0, st, R, Cout, Cin, X,
-                           Cin, W, Cout, Y, Cout, bias, 0, 0, partial);
-    return check_launch("sph3d_pointwise_gemm_bnstats");
+    SPH3D_REQUIRE(plan_args_ok(R, Cin, Cout), "pointwise_gemm_bnstats: bad dims R=%d Cin=%d Cout=%d", R, Cin, Cout);
+    return run_forward(kNNS, R, Cin, Cout, X, W, bias, 0, Y, partial, as_stream(stream), "sph3d_pointwise_gemm_bnstats");
 }
 
 extern "C" size_t sph3d_pointwise_gemm_tn_workspace(int R, int Cin, int Cout)
 {
-    int bn, tiles, nsplit, kchunk;
-    tn_plan(R, Cin, Cout, bn, tiles, nsplit, kchunk);
-    return nsplit > 1 ? sizeof(float) * (size_t)nsplit * Cin * Cout : 0;
+    // the slab plan's, whether or not the exchange ends up taking the call (its buffer may be missing at launch)
+    if (!plan_args_ok(R, Cin, Cout)) return 0;
+    const GemmPlan p = gemm_plan(kTN, R, Cin, Cout, true, split_on(), false);
+    return p.reduce ? sizeof(float) * (size_t)p.nsplit * Cin * Cout : 0;
 }
 
 extern "C" int sph3d_pointwise_gemm_tn(int R, int Cin, int Cout, const float* X, const float* dY, float* dW,
                                        void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && Cin > 0 && Cout > 0, "pointwise_gemm_tn: bad dims R=%d Cin=%d Cout=%d", R, Cin, Cout);
+    SPH3D_REQUIRE(plan_args_ok(R, Cin, Cout), "pointwise_gemm_tn: bad dims R=%d Cin=%d Cout=%d", R, Cin, Cout);
     hipStream_t st = as_stream(stream);
-    int bn, tiles, nsplit, kchunk;
-    tn_plan(R, Cin, Cout, bn, tiles, nsplit, kchunk);
     const size_t need = sph3d_pointwise_gemm_tn_workspace(R, Cin, Cout);
     if (need > 0 && (workspace == nullptr || workspace_bytes < need)) {
         set_error("pointwise_gemm_tn: workspace %zu B < required %zu B", workspace_bytes, need);
         return SPH3D_EWORKSPACE;
     }
-    float* out = nsplit > 1 ? (float*)workspace : dW;
-    // dW[Cin,Cout] = X^T * dY : A(m=cin, k=r) = X[r*Cin + cin] (row contiguous), B(k=r, n=cout) = dY[r*Cout + cout]
-    const bool whole = (Cin % 128 == 0) && (Cout % bn == 0) && (R % kchunk == 0) && aligned16(X) && aligned16(dY) && aligned16(out);
-#define SPH3D_TN(BNN, G)                                                                                                   \
-    hipLaunchKernelGGL((gemm_f32_mfma<false, false, 128, BNN, BKL, true, G>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st, Cin, Cout, R, X, \
-                       Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit)
-#define SPH3D_TN16(BNN)                                                                                                    \
-    hipLaunchKernelGGL((gemm_f32_mfma<false, false, 128, BNN, BKS, true, false>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st, Cin, Cout, R, X, \
-                       Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit)
-    // whole tiles: BK = 16 at four workgroups per CU (8 + 8 prefetch registers with the 2x4 transposing units): 0.786 vs
-    // 0.855 ms over the step's shapes against BK = 32 at two per CU
-    // short products (few rows of k, many output tiles): 64 x 64 tiles with the in-kernel exchange — up to 8 splits whose slabs are
-    // 16 KB — instead of 128 x 128 tiles + slab-sum launch.  (The exchange with 128 x 128 tiles and 8-16 splits was measured and is
-    // SLOWER than the slab-sum kernel: 72 vs 38, 82 vs 50, 84 vs 62 us — split 0 reads 7-15 64-KB slabs past the cache, one dword per
-    // lane and instruction; profiles/r06_exp_gemm_xs.log.)  kTnXsRows: largest R that takes this path
-    constexpr int kTnXsRows = 2048;
-    if (split_on() && R <= kTnXsRows && Cin % 64 == 0 && Cout % 64 == 0 && R % 32 == 0 && aligned16(X) && aligned16(dY) && aligned16(dW)) {
-        const long long Tg = gemm_grid(Cin / 64, Cout / 64);
-        const int ns = xs_splits(Tg, R, 32, 8);
-        char* xb = ns > 1 ? xs_buffer(st, (long long)(Cin / 64) * (Cout / 64), ns, 64 * 64) : nullptr;
-        if (xb != nullptr) {
-            hipLaunchKernelGGL((gemm_split_mfma<false, false, 64, 64, 32, false, false, false, true>), dim3((unsigned)(Tg * ns)), dim3(256), 0, st, Cin,
-                               Cout, R, X, Cin, dY, Cout, dW, Cout, nullptr, 0, R / ns, nullptr, ns, (float*)(xb + kXsFlagBytes), (int*)xb);
-            return check_launch("sph3d_pointwise_gemm_tn");
-        }
+    // the exchange writes dW itself, the slab plan its slabs (if more than one) to the workspace: each with its pointers' alignment
+    const bool in16 = aligned16(X) && aligned16(dY), split = split_on();
+    float* out = dW;
+    GemmPlan p = gemm_plan(kTN, R, Cin, Cout, in16 && aligned16(dW), split, true);
+    char* xb = xs_buffer(st, Cin, Cout, p.xs);
+    if (xb == nullptr) {
+        if (need > 0) out = (float*)workspace;
+        p = gemm_plan(kTN, R, Cin, Cout, in16 && aligned16(out), split, false);
     }
-    if (whole && split_on()) {
-        if (bn == 128)
-            hipLaunchKernelGGL((gemm_split_mfma<false, false, 128, 128, 16, true, false>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st, Cin,
-                               Cout, R, X, Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit);
-        else
-            hipLaunchKernelGGL((gemm_split_mfma<false, false, 128, 64, 16, true, false>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st, Cin,
-                               Cout, R, X, Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit);
-    } else if (!whole && split_on() && Cin >= 32 && Cout >= 32) {
-        if (bn == 128)
-            hipLaunchKernelGGL((gemm_split_mfma<false, false, 128, 128, 16, true, false, true>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st,
-                               Cin, Cout, R, X, Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit);
-        else
-            hipLaunchKernelGGL((gemm_split_mfma<false, false, 128, 64, 16, true, false, true>), dim3(gemm_grid(tiles, 1, nsplit)), dim3(256), 0, st,
-                               Cin, Cout, R, X, Cin, dY, Cout, out, Cout, nullptr, 0, kchunk, nullptr, nsplit);
-    } else
-    if (whole) { if (bn == 128) SPH3D_TN16(128); else SPH3D_TN16(64); }
-    else if (bn == 128) SPH3D_TN(128, true);
-    else SPH3D_TN(64, true);
-#undef SPH3D_TN16
-#undef SPH3D_TN
-    if (nsplit > 1) {
+    // dW[Cin,Cout] = X^T * dY : A(m=cin, k=r) = X[r*Cin + cin] (row contiguous), B(k=r, n=cout) = dY[r*Cout + cout]
+    const int rc = launch_plan<kTN>(p, {Cin, Cout, R, X, Cin, dY, Cout, out, Cout, nullptr, 0, nullptr}, xb, st);
+    if (rc != SPH3D_OK) return rc;
+    if (p.reduce) {
         const int total = Cin * Cout;
-        hipLaunchKernelGGL(gemm_reduce_splits, dim3((total + 31) / 32), dim3(256), 0, st, nsplit, total, out, dW);
+        hipLaunchKernelGGL(gemm_reduce_splits, dim3((total + 31) / 32), dim3(256), 0, st, p.nsplit, total, out, dW);
     }
     return check_launch("sph3d_pointwise_gemm_tn");
 }

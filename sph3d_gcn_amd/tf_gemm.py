@@ -34,14 +34,8 @@ def _pointwise_gemm_tn_impl(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     """dw[Cin,Cout] = x[R,Cin]^T @ dy[R,Cout]"""
     _lib.require_device(x, dy)
     x, dy = _lib.f32(x), _lib.f32(dy)
-    R, Cin = x.shape
-    Cout = dy.shape[1]
-    dw = torch.empty((Cin, Cout), dtype=torch.float32, device=x.device)
-    l = _lib.lib()
-    wsb = l.sph3d_pointwise_gemm_tn_workspace(R, Cin, Cout)
-    ws = _lib.scratch(wsb, x.device)
-    _lib.check(l.sph3d_pointwise_gemm_tn(R, Cin, Cout, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(ws), wsb,
-                                         _lib.stream_ptr()))
+    dw = torch.empty((x.shape[1], dy.shape[1]), dtype=torch.float32, device=x.device)
+    _pointwise_gemm_tn_into(x, dy, dw)
     return dw
 
 
