@@ -453,7 +453,11 @@ int sph3d_elu_bn_forward_partials(int R, int C, int nblk, const float* partial, 
  * (tf_conv3d.cpp:34-107 / tf_conv3d_gpu.cu:7-29) -> matmul with pointwise_weights[C*r][Cout] -> + bias[Cout] (NULL: none)
  * -> act (0 none | 1 ELU) -> y*scale[Cout] + shift[Cout] (NULL: identity; batch norm with the moving statistics is
  * scale = gamma / sqrt(moving_var + eps), shift = beta - moving_mean*scale).  output [B, M, Cout]; the [B, M, C*r] depthwise
- * tensor is never written.  Shapes: r in {1, 2}, C <= 128 a multiple of 4, Cout <= 128 a multiple of 16, F <= 254;
+ * tensor is never written.  Shapes: r in {1, 2}; C a multiple of 4, at most 128 or a multiple of 128 up to 4096; Cout a multiple of
+ * 16 up to 512; F <= 254 and few enough bins that the filter table (a 128-channel slice of it) and one 16-point tile fit the CU's
+ * 160 KB of LDS (F <= 142 beside 256 depthwise channels); N <= 2^24 and N*C*4 < 2^32.  Three kernels share them: where C <= 128,
+ * C*r <= 256 and Cout is a power of two up to 256 the barrier-free ring kernel of the training entry below, else for Cout <= 128
+ * the small kernel (pointwise weights resident in registers), else the general one (weights streamed per 128-channel slice).
  * sph3d_separable_conv3d_fused_supported() -> 1 | 0, and the call returns SPH3D_EUNSUPPORTED outside them (run
  * sph3d_depthwise_conv3d_forward + sph3d_pointwise_gemm then). */
 int sph3d_separable_conv3d_fused_supported(int N, int F, int C, int r, int K, int Cout);
@@ -474,6 +478,18 @@ int sph3d_separable_conv3d_fused(int B, int N, int M, int F, int C, int r, int K
  * (sph3d_separable_conv3d_train_supported() -> 1 | 0; SPH3D_EUNSUPPORTED otherwise: run sph3d_depthwise_conv3d +
  * sph3d_pointwise_gemm_bnstats).  The same kernel without the two extra outputs serves sph3d_separable_conv3d_fused on
  * these shapes.  sph3d_separable_conv3d_ring_failures(): 1 if a launch ever gave up waiting (never expected; synchronises). */
+/* The launch either entry point takes, answered on the host (no device is touched): csrc/sepconv.hpp states the choice once
+ * (sep_plan) and both entry points launch what it says.  train: 1 sph3d_separable_conv3d_train, 0 sph3d_separable_conv3d_fused;
+ * the dimensions as that entry point takes them.
+ *   out[SPH3D_SEP_PLAN_FIELDS], in this order:
+ *     0 kernel (0 the shape is unsupported: every field is 0; 1 ring, 2 small, 3 general)   1 R (depth multiplier)   2 LPE (lanes per
+ *     edge of the gather: 16 for C <= 64, else 32)   3 KT (ring, small: k groups of 16 the kernel is instantiated for; general: 0)
+ *     4 RBK (general: 16-point row blocks per tile; else 0)   5 RBK by the point count alone, before many bins lower it (general; else 0)
+ *     6 NB (ring: slots)   7 G (ring: wave groups)   8 dynamic LDS bytes   9 grid (workgroups; 0: nothing is launched — inference with
+ *     B == 0 or M == 0; training still launches)   10 stats_blocks (training: sph3d_separable_conv3d_train_blocks; else 0)
+ * -> SPH3D_OK, or SPH3D_EINVAL for out == NULL, train outside {0, 1}, negative B or M, or N, F, C, K, Cout that are not positive. */
+#define SPH3D_SEP_PLAN_FIELDS 11
+int sph3d_separable_conv3d_plan(int train, int B, int N, int M, int F, int C, int r, int K, int Cout, int* out);
 int sph3d_separable_conv3d_train_supported(int N, int F, int C, int r, int K, int Cout);
 int sph3d_separable_conv3d_train_blocks(int Cout);
 int sph3d_separable_conv3d_train(int B, int N, int M, int F, int C, int r, int K, int Cout,

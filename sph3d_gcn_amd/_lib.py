@@ -119,6 +119,7 @@ SIGNATURES = {
     "sph3d_pointwise_gemm_cond_grad": (_I, [_I] * 4 + [_P] * 5 + [_S, _P]),
     "sph3d_separable_conv3d_fused_supported": (_I, [_I] * 6),
     "sph3d_separable_conv3d_fused": (_I, [_I] * 9 + [_P] * 11),
+    "sph3d_separable_conv3d_plan": (_I, [_I] * 9 + [_P]),
     "sph3d_separable_conv3d_train_supported": (_I, [_I] * 6),
     "sph3d_separable_conv3d_train_blocks": (_I, [_I]),
     "sph3d_separable_conv3d_train": (_I, [_I] * 8 + [_P] * 11),

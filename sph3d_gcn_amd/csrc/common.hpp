@@ -165,6 +165,11 @@ __device__ __forceinline__ int prefix_popc(unsigned long long mask)
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
+// ELU (alpha = 1) as every kernel with a fused tail takes it (norm.hip, gemm.hip, sepring.hip, sepconv.hip).  exp(y) - 1 through
+// v_exp_f32: absolute error ~1e-7 on (-inf, 0] (measured: tools/micro/elu_err.hip), far inside the 1e-5 activation bound; the software
+// expm1f made the HBM-streaming kernels of norm.hip VALU-bound (3.7 ms/step, no better than the unfused torch ops)
+__device__ __forceinline__ float elu1(float y) { return y > 0.f ? y : __expf(y) - 1.f; }
+
 // make a wave-uniform int visibly scalar to the compiler
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ float uniformf(float v)

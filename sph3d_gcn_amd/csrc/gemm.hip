@@ -252,7 +252,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], float* lds,
 #pragma unroll
                     for (int e = 0; e < 16; e++) {
                         const float y = acc[i][j][e] + bv;
-                        const float z = y > 0.f ? y : __expf(y) - 1.f;         // == norm.hip: elu1
+                        const float z = elu1(y);
                         sz += z;
                         sq = fmaf(z, z, sq);
                     }

@@ -17,10 +17,6 @@ namespace sph3d {
 
 constexpr int kNormMaxBlocks = 1024;
 
-// exp(y) - 1 through v_exp_f32: absolute error ~1e-7 on (-inf, 0], far inside the 1e-5 activation bound; the software expm1f
-// made these HBM-streaming kernels VALU-bound (3.7 ms/step, no better than the unfused torch ops)
-__device__ __forceinline__ float elu1(float y) { return y > 0.f ? y : __expf(y) - 1.f; }
-
 // partial[blk][0][C] = sum a, partial[blk][1][C] = sum b over the block's rows, where
 //   BWD = false: a = z,    b = z*z            (z = elu(y))
 //   BWD = true : a = dout, b = dout * zhat    (zhat = (z - mean) * rstd)

@@ -12,19 +12,12 @@
 // path is taken when no gradient is recorded.  Shapes outside C <= 128, C*r <= 256, Cout <= 128 — every deeper layer of the
 // S3DIS / ShapeNet plans — run sepconv_general_kernel below (accumulators resident, W streamed per k slice).
 //
-// k-order of the product: lane (i = lane % 16, kq = lane / 16) supplies A[i][16t + 4kq + u] and B[16t + 4kq + u][j] at step
-// (t, u): any pairing is legal as long as A and B use the same one, and this one makes a lane's four A values of a t ONE
-// ds_read_b128.  fp32 MFMA is exact fp32 FMA arithmetic; results differ from the separate kernels by summation order only.
-#include "common.hpp"
+// fp32 MFMA is exact fp32 FMA arithmetic; results differ from the separate kernels by summation order only (k-order of the product:
+// sepconv.hpp, sep_load_w).  The launch choice of this file's two kernels and of sepring.hip's is sepconv.hpp's sep_plan; the one
+// launcher and the host-only query are at the end of this file.
+#include "sepconv.hpp"
 
 namespace sph3d {
-
-typedef float sc_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kScWaves = 16;
-constexpr int kScTile = 32;                 // output points per tile (two per wave in the gather phase)
-
-__device__ __forceinline__ float sc_elu(float y) { return y > 0.f ? y : __expf(y) - 1.f; }      // == norm.hip: elu1
 
 // R = depth multiplier; LPE = lanes per edge in the gather phase (16: C <= 64, 32: C <= 128); KT = ceil(C*R / 16) k-groups
 template <int R, int LPE, int KT>
@@ -36,10 +29,7 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
     float* __restrict__ output)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int EPL = 64 / LPE;
-    constexpr int NO = 4 * R;
     constexpr int SLI = 4 * LPE;                 // input channels the gather layout covers
-    constexpr int FSTB = SLI * R * 4;            // bytes per filter row in LDS
     constexpr int KP = KT * 16;                  // padded k extent (C*R rounded up to 16)
     constexpr int LDA = KP + 4;                  // A-tile row stride (floats): conflict-free ds_read_b128 across rows
     float* lfilt = lds;                                          // [F + 1][R][SLI]
@@ -49,16 +39,9 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
     const int wave = uniform(tid >> 6);
     const int lane = lane_id();
 
-    // ---- depthwise filter table -> LDS (dwconv_fwd_multi's layout), zero row F for padding slots ----
-    for (int e = tid * 4; e < F * CR; e += kScWaves * 64 * 4) {
-        const int f = e / CR;
-        const int cl = e - f * CR;
-        const int l4 = cl / (4 * R), q = (cl >> 2) % R;
-        *reinterpret_cast<float4*>(&lfilt[f * (SLI * R) + q * SLI + l4 * 4]) = *reinterpret_cast<const float4*>(&dwFilter[(size_t)f * CR + cl]);
-    }
-    for (int e = tid; e < SLI * R; e += kScWaves * 64) lfilt[F * (SLI * R) + e] = 0.f;
+    sep_load_filter<R, SLI>(lfilt, dwFilter, F, CR, tid);
     // columns of the A tile beyond C*R (k padding) stay zero for the whole launch
-    for (int e = tid; e < 2 * kScTile * LDA; e += kScWaves * 64) atile[e] = 0.f;
+    for (int e = tid; e < 2 * kScTile * LDA; e += kSepWaves * 64) atile[e] = 0.f;
 
     // ---- this wave's block of the product: rows rb*16.., columns cb*16..; its W columns in registers ----
     const int ncb = Cout >> 4;
@@ -66,13 +49,7 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
     const bool gemm_wave = rb < (kScTile / 16);
     const int i16 = lane & 15, kq = lane >> 4;
     float wreg[KT][4];
-#pragma unroll
-    for (int t = 0; t < KT; t++)
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int k = 16 * t + 4 * kq + u;
-            wreg[t][u] = (gemm_wave && k < CR) ? W[(size_t)k * Cout + cb * 16 + i16] : 0.f;
-        }
+    sep_load_w<KT>(wreg, W, CR, Cout, cb, i16, kq, gemm_wave);
     const int col = cb * 16 + i16;
     const float bv = (gemm_wave && bias != nullptr) ? bias[col] : 0.f;
     const float sc = (gemm_wave && scale != nullptr) ? scale[col] : 1.f;
@@ -81,13 +58,9 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
 
     // ---- tiles of this workgroup: contiguous range of the tiles of its XCD's clouds ----
     const int tpc = (M + kScTile - 1) / kScTile;                  // tiles per cloud
-    const int WPX = (int)gridDim.x >> 3;
-    const int xcd = (int)blockIdx.x & 7, wi = (int)blockIdx.x >> 3;
-    const bool affine = (B & 7) == 0;
-    long long total, part, parts;
-    if (affine) { total = (long long)(B >> 3) * tpc; part = wi; parts = WPX; }
-    else { total = (long long)B * tpc; part = (long long)xcd * WPX + wi; parts = 8LL * WPX; }
-    const int f_begin = (int)(total * part / parts), f_end = (int)(total * (part + 1) / parts);
+    bool affine;
+    int xcd, f_begin, f_end;
+    sep_units(B, tpc, affine, xcd, f_begin, f_end);
 
     const int g = lane / LPE, li = lane - g * LPE;
     const bool actl = li * 4 < C;
@@ -103,54 +76,12 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
         const char* inb = reinterpret_cast<const char*>(input + (size_t)b * N * C);
 #pragma unroll 1
         for (int h = 0; h < 2; h++) {                 // wave w takes points m0 + w and m0 + w + 16
-            const int p = wave + kScWaves * h;
+            const int p = wave + kSepWaves * h;
             const int m = m0 + p;
-            float acc[NO];
-#pragma unroll
-            for (int v = 0; v < NO; v++) acc[v] = 0.f;
-            int cnt = 0;
-            if (m < M) {
-                const size_t row = (size_t)b * M + m;
-                cnt = uniform(nnCount[row]);
-                for (int kt = 0; kt < cnt; kt += 64) {
-                    const int myk = kt + lane;
-                    const int kn = (cnt - kt) < 64 ? (cnt - kt) : 64;
-                    const int mykc = myk < cnt ? myk : kt;
-                    const int idxv = nnIndex[row * K + mykc];
-                    int binv = binIndex[row * K + mykc];
-                    binv = binv < 0 ? 0 : (binv >= F ? F - 1 : binv);
-                    binv = myk < cnt ? binv : F;
-                    const unsigned pk = ((unsigned)idxv & 0xffffffu) | ((unsigned)binv << 24);
-                    for (int k0 = 0; k0 < kn; k0 += 4 * EPL) {
-                        float4 x[4];
-                        unsigned fo[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const int kq2 = k0 + u * EPL + g;
-                            const unsigned pp = (unsigned)__shfl((int)pk, kq2);
-                            const unsigned off = __umul24(pp, rowb) + cicb;
-                            fo[u] = __umul24(pp >> 24, (unsigned)FSTB) + cicb;
-                            x[u] = *reinterpret_cast<const float4*>(inb + off);
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const float xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
-#pragma unroll
-                            for (int q = 0; q < R; q++) {
-                                const float4 w4 = *reinterpret_cast<const float4*>(lfb + fo[u] + q * (SLI * 4));
-                                acc[4 * q + 0] = fmaf(xs[(4 * q + 0) / R], w4.x, acc[4 * q + 0]);
-                                acc[4 * q + 1] = fmaf(xs[(4 * q + 1) / R], w4.y, acc[4 * q + 1]);
-                                acc[4 * q + 2] = fmaf(xs[(4 * q + 2) / R], w4.z, acc[4 * q + 2]);
-                                acc[4 * q + 3] = fmaf(xs[(4 * q + 3) / R], w4.w, acc[4 * q + 3]);
-                            }
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = LPE; o < 64; o <<= 1)
-#pragma unroll
-                for (int v = 0; v < NO; v++) acc[v] += __shfl_xor(acc[v], o);
+            const size_t row = (size_t)b * M + m;
+            const SepSums<R> sums = sep_gather<R, LPE>(lane, g, inb, m < M, row, K, F, nnCount, nnIndex, binIndex, lfb, rowb, cicb, cicb);
+            const int cnt = sums.cnt;
+            const float* acc = sums.v;
             if (actl && g == 0) {
                 const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.f;        // rows past M / empty rows: zeros
                 float* ap = abuf + (size_t)p * LDA + li * 4 * R;
@@ -163,26 +94,15 @@ __global__ __launch_bounds__(1024) void sepconv_fused_kernel(
     };
     auto product_tile = [&](int b, int m0, const float* abuf) {
         if (!gemm_wave) return;
-        // four independent accumulation chains (one per k-slot of the 16-byte read), added at the end: one chain of 4 KT
-        // dependent MFMAs leaves the wave waiting for its own previous result (skinny.hip: 46 -> 33 us from the same change)
-        sc_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0, d2 = d0, d3 = d0;
-        const float* arow = abuf + (size_t)(rb * 16 + i16) * LDA + 4 * kq;
-#pragma unroll
-        for (int t = 0; t < KT; t++) {
-            const sc_f32x4 a = *reinterpret_cast<const sc_f32x4*>(arow + 16 * t);
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wreg[t][0], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wreg[t][1], d1, 0, 0, 0);
-            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wreg[t][2], d2, 0, 0, 0);
-            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wreg[t][3], d3, 0, 0, 0);
-        }
-        const sc_f32x4 d = (d0 + d1) + (d2 + d3);
+        const SepChains c = sep_product<KT>(abuf + (size_t)(rb * 16 + i16) * LDA + 4 * kq, wreg);
+        const sep_f32x4 d = (c.d0 + c.d1) + (c.d2 + c.d3);
         // D layout of 16x16x4: lane holds rows 4*(lane/16) + r, r < 4, of column lane % 16
 #pragma unroll
         for (int r4 = 0; r4 < 4; r4++) {
             const int m = m0 + rb * 16 + 4 * kq + r4;
             if (m < M) {
                 float y = d[r4] + bv;
-                if (act == 1) y = sc_elu(y);
+                if (act == 1) y = elu1(y);
                 output[((size_t)b * M + m) * Cout + col] = fmaf(y, sc, sh);
             }
         }
@@ -231,15 +151,12 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
     float* __restrict__ output)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int EPL = 64 / LPE;
-    constexpr int NO = 4 * R;
     constexpr int SLI = 4 * LPE;                 // input channels per slice
-    constexpr int FSTB = SLI * R * 4;            // bytes per filter row in LDS
     constexpr int KP = SLI * R;                  // k extent of a slice
     constexpr int KT = KP / 16;
     constexpr int LDA = KP + 4;
     constexpr int TP = 16 * RBK;                 // points per tile
-    constexpr int PPW = (TP + kScWaves - 1) / kScWaves;      // points a wave gathers per tile and slice
+    constexpr int PPW = (TP + kSepWaves - 1) / kSepWaves;      // points a wave gathers per tile and slice
     float* lfilt = lds;                                          // [F + 1][R][SLI]
     float* atile = lds + (size_t)(F + 1) * SLI * R;              // [TP][LDA]
     const int CR = C * R;
@@ -251,34 +168,30 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
     const int i16 = lane & 15, kq = lane >> 4;
 
     const int tpc = (M + TP - 1) / TP;                           // tiles per cloud
-    const int WPX = (int)gridDim.x >> 3;
-    const int xcd = (int)blockIdx.x & 7, wi = (int)blockIdx.x >> 3;
-    const bool affine = (B & 7) == 0;
-    long long total, part, parts;
-    if (affine) { total = (long long)(B >> 3) * tpc; part = wi; parts = WPX; }
-    else { total = (long long)B * tpc; part = (long long)xcd * WPX + wi; parts = 8LL * WPX; }
-    const int f_begin = (int)(total * part / parts), f_end = (int)(total * (part + 1) / parts);
+    bool affine;
+    int xcd, f_begin, f_end;
+    sep_units(B, tpc, affine, xcd, f_begin, f_end);
 
     const int g = lane / LPE, li = lane - g * LPE;
     const unsigned rowb = (unsigned)C * 4u;
     const char* lfb = reinterpret_cast<const char*>(lfilt);
-    for (int e = tid; e < SLI * R; e += kScWaves * 64) lfilt[F * (SLI * R) + e] = 0.f;      // zero filter row of padding slots
+    for (int e = tid; e < SLI * R; e += kSepWaves * 64) lfilt[F * (SLI * R) + e] = 0.f;      // zero filter row of padding slots
 
     int cl = f_begin / tpc, tl = f_begin - cl * tpc;
     for (int it = f_begin; it < f_end; it++) {
         const int b = affine ? xcd + 8 * cl : cl;
         const int m0 = tl * TP;
-        sc_f32x4 d[2][RBK];
+        sep_f32x4 d[2][RBK];
 #pragma unroll
         for (int c2 = 0; c2 < 2; c2++)
 #pragma unroll
-            for (int rb = 0; rb < RBK; rb++) d[c2][rb] = sc_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int rb = 0; rb < RBK; rb++) d[c2][rb] = sep_f32x4{0.f, 0.f, 0.f, 0.f};
         for (int s = 0; s < nslices; s++) {
             const int c0 = s * SLI;
             const int SLc = (C - c0) < SLI ? (C - c0) : SLI;             // channels of this slice (multiple of 4)
             __syncthreads();                                              // the previous slice's product is done with LDS
             // ---- filter slice -> LDS ----
-            for (int e = tid * 4; e < F * SLc * R; e += kScWaves * 64 * 4) {
+            for (int e = tid * 4; e < F * SLc * R; e += kSepWaves * 64 * 4) {
                 const int f = e / (SLc * R);
                 const int cl4 = e - f * (SLc * R);
                 const int l4 = cl4 / (4 * R), q = (cl4 >> 2) % R;
@@ -293,55 +206,13 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
             const char* inb = reinterpret_cast<const char*>(input + (size_t)b * N * C);
 #pragma unroll 1
             for (int h = 0; h < PPW; h++) {
-                const int p = wave + kScWaves * h;
+                const int p = wave + kSepWaves * h;
                 if (p >= TP) break;
                 const int m = m0 + p;
-                float acc[NO];
-#pragma unroll
-                for (int v = 0; v < NO; v++) acc[v] = 0.f;
-                int cnt = 0;
-                if (m < M) {
-                    const size_t row = (size_t)b * M + m;
-                    cnt = uniform(nnCount[row]);
-                    for (int kt = 0; kt < cnt; kt += 64) {
-                        const int myk = kt + lane;
-                        const int kn = (cnt - kt) < 64 ? (cnt - kt) : 64;
-                        const int mykc = myk < cnt ? myk : kt;
-                        const int idxv = nnIndex[row * K + mykc];
-                        int binv = binIndex[row * K + mykc];
-                        binv = binv < 0 ? 0 : (binv >= F ? F - 1 : binv);
-                        binv = myk < cnt ? binv : F;
-                        const unsigned pk = ((unsigned)idxv & 0xffffffu) | ((unsigned)binv << 24);
-                        for (int k0 = 0; k0 < kn; k0 += 4 * EPL) {
-                            float4 x[4];
-                            unsigned fo[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const int kq2 = k0 + u * EPL + g;
-                                const unsigned pp = (unsigned)__shfl((int)pk, kq2);
-                                const unsigned off = __umul24(pp, rowb) + cicb;
-                                fo[u] = __umul24(pp >> 24, (unsigned)FSTB) + ficb;
-                                x[u] = *reinterpret_cast<const float4*>(inb + off);
-                            }
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const float xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
-#pragma unroll
-                                for (int q = 0; q < R; q++) {
-                                    const float4 w4 = *reinterpret_cast<const float4*>(lfb + fo[u] + q * (SLI * 4));
-                                    acc[4 * q + 0] = fmaf(xs[(4 * q + 0) / R], w4.x, acc[4 * q + 0]);
-                                    acc[4 * q + 1] = fmaf(xs[(4 * q + 1) / R], w4.y, acc[4 * q + 1]);
-                                    acc[4 * q + 2] = fmaf(xs[(4 * q + 2) / R], w4.z, acc[4 * q + 2]);
-                                    acc[4 * q + 3] = fmaf(xs[(4 * q + 3) / R], w4.w, acc[4 * q + 3]);
-                                }
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int o = LPE; o < 64; o <<= 1)
-#pragma unroll
-                    for (int v = 0; v < NO; v++) acc[v] += __shfl_xor(acc[v], o);
+                const size_t row = (size_t)b * M + m;
+                const SepSums<R> sums = sep_gather<R, LPE>(lane, g, inb, m < M, row, K, F, nnCount, nnIndex, binIndex, lfb, rowb, cicb, ficb);
+                const int cnt = sums.cnt;
+                const float* acc = sums.v;
                 if (g == 0) {
                     // lanes beyond the slice's channels write zeros: k columns the product multiplies with W rows that do not exist
                     const float inv = (cnt > 0 && actl) ? 1.0f / (float)cnt : 0.f;
@@ -357,7 +228,7 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
             const int kbase = c0 * R;                                    // first k row of the slice in W
 #pragma unroll
             for (int c2 = 0; c2 < 2; c2++) {
-                const int cb = wave + kScWaves * c2;
+                const int cb = wave + kSepWaves * c2;
                 if (cb >= ncb) break;
                 const float* wp = W + (size_t)kbase * Cout + cb * 16 + i16;
 #pragma unroll 1
@@ -368,10 +239,10 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
                         const int k = 16 * t + 4 * kq + u;
                         bw[u] = k < SLc * R ? wp[(size_t)k * Cout] : 0.f;
                     }
-                    sc_f32x4 a[RBK];
+                    sep_f32x4 a[RBK];
 #pragma unroll
                     for (int rb = 0; rb < RBK; rb++)
-                        a[rb] = *reinterpret_cast<const sc_f32x4*>(atile + (size_t)(rb * 16 + i16) * LDA + 16 * t + 4 * kq);
+                        a[rb] = *reinterpret_cast<const sep_f32x4*>(atile + (size_t)(rb * 16 + i16) * LDA + 16 * t + 4 * kq);
                     // (u outer, row blocks inner: consecutive MFMAs write different accumulators)
 #pragma unroll
                     for (int u = 0; u < 4; u++)
@@ -384,7 +255,7 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
         // ---- epilogue: bias -> ELU -> per-channel affine; D layout: lane holds rows 4*(lane/16) + r of column lane % 16 ----
 #pragma unroll
         for (int c2 = 0; c2 < 2; c2++) {
-            const int cb = wave + kScWaves * c2;
+            const int cb = wave + kSepWaves * c2;
             if (cb >= ncb) break;
             const int col = cb * 16 + i16;
             const float bv = bias != nullptr ? bias[col] : 0.f;
@@ -397,7 +268,7 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
                     const int m = m0 + rb * 16 + 4 * kq + r4;
                     if (m < M) {
                         float y = d[c2][rb][r4] + bv;
-                        if (act == 1) y = sc_elu(y);
+                        if (act == 1) y = elu1(y);
                         output[((size_t)b * M + m) * Cout + col] = fmaf(y, sc, sh);
                     }
                 }
@@ -406,83 +277,66 @@ __global__ __launch_bounds__(1024) void sepconv_general_kernel(
     }
 }
 
-// shapes of the general kernel: C <= 128 (one, possibly partial, slice) or a multiple of 128; Cout a multiple of 16, <= 512
-// LDS of the general kernel: the depthwise filter slice (F + 1 rows) + the A tile of rbk row blocks
-static size_t sc_general_lds(int F, int C, int r, int rbk)
+// ---- the launcher: the kernel a plan names (sepconv.hpp: sep_plan).  Only the instantiations some plan reaches are compiled ---
+typedef void (*SepTileKernel)(int, int, int, int, int, int, int, int, const int*, const int*, const int*, const float*, const float*,
+                              const float*, const float*, const float*, const float*, float*);
+
+static SepTileKernel sc_kernel(const SepPlan& p)
 {
-    const size_t lpe = C <= 64 ? 16 : 32;
-    return sizeof(float) * ((size_t)(F + 1) * 4 * lpe * r + (size_t)(16 * rbk) * (4 * lpe * r + 4));
+    if (p.kernel == kSepSmall)
+        return sep_with_triple(p, [](auto R, auto L, auto KT) -> SepTileKernel { return sepconv_fused_kernel<R(), L(), KT()>; });
+    // general: R in {1, 2} x LPE in {16, 32} x RBK in {1, 2, 4}
+    auto with_rbk = [&](auto R, auto L) -> SepTileKernel {
+        if (p.RBK == 4) return sepconv_general_kernel<R(), L(), 4>;
+        if (p.RBK == 2) return sepconv_general_kernel<R(), L(), 2>;
+        return p.RBK == 1 ? sepconv_general_kernel<R(), L(), 1> : nullptr;
+    };
+    using std::integral_constant;
+    auto with_lpe = [&](auto R) -> SepTileKernel {
+        if (p.LPE == 16) return with_rbk(R, integral_constant<int, 16>{});
+        return p.LPE == 32 ? with_rbk(R, integral_constant<int, 32>{}) : nullptr;
+    };
+    if (p.R == 1) return with_lpe(integral_constant<int, 1>{});
+    return p.R == 2 ? with_lpe(integral_constant<int, 2>{}) : nullptr;
 }
 
-static bool sc_general_ok(int N, int F, int C, int r, int K, int Cout)
+int sep_launch(const SepPlan& p, const SepArgs& a, hipStream_t st)
 {
-    // "supported" is exactly what the launcher can run: the smallest tile (one row block) must fit the CU's LDS next to the
-    // filter slice (F <= 254 alone let kernels with ~95+ bins through, which then failed at launch)
-    return (r == 1 || r == 2) && sc_general_lds(F, C, r, 1) <= 160 * 1024 && C % 4 == 0 && C >= 4 && (C <= 128 || (C % 128 == 0 && C <= 4096)) && Cout % 16 == 0 && Cout >= 16 &&
-           Cout <= 512 && F <= 254 && N <= (1 << 24) && K > 0 && (unsigned long long)N * C * 4ull + 1024ull < (1ull << 32);
-}
-
-template <int R, int LPE>
-static int sc_launch_general(int B, int N, int M, int F, int C, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                             const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                             const float* scale, const float* shift, float* output, hipStream_t st)
-{
-    // tile height: as many row blocks as still leave every CU a tile
-    const long long pts = (long long)B * M;
-    int rbk = pts >= 64LL * 512 ? 4 : (pts >= 32LL * 256 ? 2 : 1);
-    while (rbk > 1 && sc_general_lds(F, C, R, rbk) > 160 * 1024) rbk >>= 1;      // many bins: a lower tile beside the larger filter slice
-    const size_t lds = sizeof(float) * ((size_t)(F + 1) * 4 * LPE * R + (size_t)(16 * rbk) * (4 * LPE * R + 4));
-    SPH3D_REQUIRE(lds <= 160 * 1024, "SeparableConv3dFused: %zu B of LDS needed", lds);
-    auto kern = rbk == 4 ? sepconv_general_kernel<R, LPE, 4> : (rbk == 2 ? sepconv_general_kernel<R, LPE, 2> : sepconv_general_kernel<R, LPE, 1>);
-    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dFused", B, N, M, F, C, K, Cout, act, nn_index,
-                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output);
+    if (p.grid == 0) return SPH3D_OK;
+    const bool ring = p.kernel == kSepRing;
+    const char* who = ring ? "SeparableConv3dRing" : "SeparableConv3dFused";
+    const SepRingKernel rk = ring ? sepring_kernel(p) : nullptr;
+    const SepTileKernel tk = ring ? nullptr : sc_kernel(p);
+    SPH3D_REQUIRE((rk != nullptr || tk != nullptr) && p.lds > 0 && (size_t)p.lds <= kSepLds,
+                  "%s: no kernel for plan %d <%d,%d,%d|%d> with %d B of LDS", who, p.kernel, p.R, p.LPE, p.KT, p.RBK, p.lds);
+    const int rc = ring ? launch_lds<48 * 1024>(rk, dim3(p.grid), dim3(1024), p.lds, st, who, a.B, a.N, a.M, a.F, a.C, a.K, a.Cout, a.act, p.NB,
+                                                a.nn_index, a.nn_count, a.bin_index, a.input, a.dw_filter, a.W, a.bias, a.scale, a.shift,
+                                                a.output, a.dw_out, a.stats)
+                        : launch_lds<48 * 1024>(tk, dim3(p.grid), dim3(1024), p.lds, st, who, a.B, a.N, a.M, a.F, a.C, a.K, a.Cout, a.act,
+                                                a.nn_index, a.nn_count, a.bin_index, a.input, a.dw_filter, a.W, a.bias, a.scale, a.shift,
+                                                a.output);
     if (rc) return rc;
-    return check_launch("sph3d_separable_conv3d_fused (general)");
+    return check_launch(ring ? "sph3d_separable_conv3d_ring"
+                             : (p.kernel == kSepSmall ? "sph3d_separable_conv3d_fused" : "sph3d_separable_conv3d_fused (general)"));
 }
-
-static size_t sc_small_lds(int F, int C, int r)
-{
-    const size_t lpe = C <= 64 ? 16 : 32;
-    const int KT = (C * r + 15) / 16;
-    const int KTP = KT <= 4 ? 4 : (KT <= 8 ? 8 : 16);
-    return sizeof(float) * ((size_t)(F + 1) * 4 * lpe * r + 2 * (size_t)kScTile * (KTP * 16 + 4));
-}
-
-static bool sc_shape_ok(int N, int F, int C, int r, int K, int Cout)
-{
-    return (r == 1 || r == 2) && sc_small_lds(F, C, r) <= 160 * 1024 && C % 4 == 0 && C >= 4 && C <= 128 && C * r <= 256 && Cout % 16 == 0 && Cout >= 16 && Cout <= 128 &&
-           F <= 254 && N <= (1 << 24) && K > 0 && (unsigned long long)N * C * 4ull + 1024ull < (1ull << 32);
-}
-
-template <int R, int LPE>
-static int sc_launch(int B, int N, int M, int F, int C, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                     const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                     const float* scale, const float* shift, float* output, hipStream_t st)
-{
-    const int KT = (C * R + 15) / 16;
-    const int KTP = KT <= 4 ? 4 : (KT <= 8 ? 8 : 16);           // the k extent the kernel is instantiated for
-    const size_t lds = sizeof(float) * ((size_t)(F + 1) * 4 * LPE * R + 2 * (size_t)kScTile * (KTP * 16 + 4));
-    SPH3D_REQUIRE(lds <= 160 * 1024, "SeparableConv3dFused: %zu B of LDS needed", lds);
-    auto kern = KTP == 4 ? sepconv_fused_kernel<R, LPE, 4> : (KTP == 8 ? sepconv_fused_kernel<R, LPE, 8> : sepconv_fused_kernel<R, LPE, 16>);
-    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dFused", B, N, M, F, C, K, Cout, act, nn_index,
-                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output);
-    if (rc) return rc;
-    return check_launch("sph3d_separable_conv3d_fused");
-}
-
-// sepring.hip: the same layer without barriers (claim counter + ring of row blocks); covers C <= 128, C*r <= 256, Cout a power of two
-bool sepring_infer_ok(int N, int F, int C, int r, int K, int Cout);
-int sepring_infer(int B, int N, int M, int F, int C, int r, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                  const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                  const float* scale, const float* shift, float* output, hipStream_t st);
 
 }  // namespace sph3d
 
 using namespace sph3d;
 
+extern "C" int sph3d_separable_conv3d_plan(int train, int B, int N, int M, int F, int C, int r, int K, int Cout, int* out)
+{
+    SPH3D_REQUIRE((train | 1) == 1 && out != nullptr, "separable_conv3d_plan: train is 0 or 1, out is not NULL");
+    if (int rc = sep_check_dims("separable_conv3d_plan", B, N, M, F, C, K, Cout)) return rc;
+    const SepPlan p = sep_plan(train != 0, B, N, M, F, C, r, K, Cout);
+    static_assert(offsetof(SepPlan, train) == SPH3D_SEP_PLAN_FIELDS * sizeof(int), "the plan starts with the documented fields, in their order");
+    memcpy(out, &p, SPH3D_SEP_PLAN_FIELDS * sizeof(int));
+    return SPH3D_OK;
+}
+
 extern "C" int sph3d_separable_conv3d_fused_supported(int N, int F, int C, int r, int K, int Cout)
 {
-    return (sc_shape_ok(N, F, C, r, K, Cout) || sc_general_ok(N, F, C, r, K, Cout)) ? 1 : 0;
+    return sep_plan(false, 0, N, 0, F, C, r, K, Cout).kernel != kSepNone;
 }
 
 extern "C" int sph3d_separable_conv3d_fused(int B, int N, int M, int F, int C, int r, int K, int Cout, int act,
@@ -491,40 +345,15 @@ extern "C" int sph3d_separable_conv3d_fused(int B, int N, int M, int F, int C, i
                                             const float* bias, const float* scale, const float* shift, float* output,
                                             sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && F > 0 && C > 0 && K > 0 && Cout > 0,
-                  "SeparableConv3dFused: bad dims B=%d N=%d M=%d F=%d C=%d K=%d Cout=%d", B, N, M, F, C, K, Cout);
+    if (int rc = sep_check_dims("SeparableConv3dFused", B, N, M, F, C, K, Cout)) return rc;
     SPH3D_REQUIRE(act == 0 || act == 1, "SeparableConv3dFused: act must be 0 (none) or 1 (ELU), got %d", act);
-    const bool small = sc_shape_ok(N, F, C, r, K, Cout);
-    if (!small && !sc_general_ok(N, F, C, r, K, Cout)) {
+    const SepPlan p = sep_plan(false, B, N, M, F, C, r, K, Cout);
+    if (p.kernel == kSepNone) {
         set_error("SeparableConv3dFused: shape C=%d r=%d Cout=%d F=%d not covered (C %% 4 == 0 and C <= 128 or a multiple of 128; "
                   "Cout <= 512 in multiples of 16; r in {1, 2})", C, r, Cout, F);
         return SPH3D_EUNSUPPORTED;
     }
-    if (B == 0 || M == 0) return SPH3D_OK;
-    hipStream_t st = as_stream(stream);
-    // the barrier-free kernel wherever it covers the shape
-    if (sepring_infer_ok(N, F, C, r, K, Cout))
-        return sepring_infer(B, N, M, F, C, r, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                             pointwise_weights, bias, scale, shift, output, st);
-    if (!small) {
-        // the layers whose pointwise weights do not fit a wave's registers: accumulators resident, W streamed per k slice
-        if (C <= 64)
-            return r == 2 ? sc_launch_general<2, 16>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                                     pointwise_weights, bias, scale, shift, output, st)
-                          : sc_launch_general<1, 16>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                                     pointwise_weights, bias, scale, shift, output, st);
-        return r == 2 ? sc_launch_general<2, 32>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                                 pointwise_weights, bias, scale, shift, output, st)
-                      : sc_launch_general<1, 32>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                                 pointwise_weights, bias, scale, shift, output, st);
-    }
-    if (C <= 64)
-        return r == 2 ? sc_launch<2, 16>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                         pointwise_weights, bias, scale, shift, output, st)
-                      : sc_launch<1, 16>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                         pointwise_weights, bias, scale, shift, output, st);
-    return r == 2 ? sc_launch<2, 32>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                     pointwise_weights, bias, scale, shift, output, st)
-                  : sc_launch<1, 32>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter,
-                                     pointwise_weights, bias, scale, shift, output, st);
+    // (B == 0 or M == 0: the plan's grid is 0, nothing is launched)
+    return sep_launch(p, {B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, depthwise_filter, pointwise_weights, bias, scale,
+                          shift, output, nullptr, nullptr}, as_stream(stream));
 }

@@ -23,19 +23,13 @@
 // one wave execute in order, so "row written, then counter raised" needs no fence, only a compiler barrier.
 // Spins are bounded: a wave that polls ~2^22 times raises a device flag and the workgroup drains (results wrong, no hang);
 // sph3d_separable_conv3d_ring_failures() reads the flag (tests).
-#include "common.hpp"
+#include "sepconv.hpp"
 
 namespace sph3d {
 
-typedef float sr_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kSrWaves = 16;
-constexpr int kSrRows = 16;                 // points per row block (one MFMA row block)
 constexpr int kSrSpinLimit = 1 << 22;
 
 __device__ int g_sr_fail = 0;
-
-__device__ __forceinline__ float sr_elu(float y) { return y > 0.f ? y : __expf(y) - 1.f; }      // == norm.hip: elu1
 
 __device__ __forceinline__ int sr_peek(const int* p)
 {
@@ -63,10 +57,8 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
     float* __restrict__ output, float* __restrict__ dwOut, float* __restrict__ stats)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int EPL = 64 / LPE;
     constexpr int NO = 4 * R;
     constexpr int SLI = 4 * LPE;                 // input channels the gather layout covers
-    constexpr int FSTB = SLI * R * 4;            // bytes per filter row in LDS
     constexpr int KP = KT * 16;                  // padded k extent (C*R rounded up to 16)
     constexpr int LDA = KP + 4;                  // ring row stride (floats): conflict-free ds_read_b128 across rows
     constexpr int RBF = kSrRows * LDA;           // floats per row block
@@ -80,32 +72,19 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
     const int wave = uniform(tid >> 6);
     const int lane = lane_id();
 
-    // ---- depthwise filter table -> LDS (dwconv_fwd_multi's layout), zero row F for padding slots ----
-    for (int e = tid * 4; e < F * CR; e += kSrWaves * 64 * 4) {
-        const int f = e / CR;
-        const int cl = e - f * CR;
-        const int l4 = cl / (4 * R), q = (cl >> 2) % R;
-        *reinterpret_cast<float4*>(&lfilt[f * (SLI * R) + q * SLI + l4 * 4]) = *reinterpret_cast<const float4*>(&dwFilter[(size_t)f * CR + cl]);
-    }
-    for (int e = tid; e < SLI * R; e += kSrWaves * 64) lfilt[F * (SLI * R) + e] = 0.f;
+    sep_load_filter<R, SLI>(lfilt, dwFilter, F, CR, tid);
     // ring columns beyond C*R (k padding) stay zero for the whole launch
-    for (int e = tid; e < NB * RBF; e += kSrWaves * 64) ring[e] = 0.f;
-    for (int e = tid; e < 2 + 2 * NB; e += kSrWaves * 64) ctrl[e] = 0;
+    for (int e = tid; e < NB * RBF; e += kSepWaves * 64) ring[e] = 0.f;
+    for (int e = tid; e < 2 + 2 * NB; e += kSepWaves * 64) ctrl[e] = 0;
 
     // ---- this wave's column block of the product; its W columns in registers ----
     const int ncb = Cout >> 4;                                   // column blocks (<= 16)
-    const int G = kSrWaves / ncb;                                // wave groups: group g multiplies the row blocks j = g (mod G)
+    const int G = kSepWaves / ncb;                                // wave groups: group g multiplies the row blocks j = g (mod G)
     const int grp = wave / ncb, cb = wave - grp * ncb;
     const bool gemm_wave = grp < G;
     const int i16 = lane & 15, kq = lane >> 4;
     float wreg[KT][4];
-#pragma unroll
-    for (int t = 0; t < KT; t++)
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int k = 16 * t + 4 * kq + u;
-            wreg[t][u] = (gemm_wave && k < CR) ? W[(size_t)k * Cout + cb * 16 + i16] : 0.f;
-        }
+    sep_load_w<KT>(wreg, W, CR, Cout, cb, i16, kq, gemm_wave);
     const int col = cb * 16 + i16;
     const float bv = (gemm_wave && bias != nullptr) ? bias[col] : 0.f;
     const float sc = (!TRAIN && gemm_wave && scale != nullptr) ? scale[col] : 1.f;
@@ -115,13 +94,9 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
 
     // ---- row blocks of this workgroup: a contiguous range of the row blocks of its XCD's clouds ----
     const int rpc = (M + kSrRows - 1) / kSrRows;                 // row blocks per cloud
-    const int WPX = (int)gridDim.x >> 3;
-    const int xcd = (int)blockIdx.x & 7, wi = (int)blockIdx.x >> 3;
-    const bool affine = (B & 7) == 0;
-    long long total, part, parts;
-    if (affine) { total = (long long)(B >> 3) * rpc; part = wi; parts = WPX; }
-    else { total = (long long)B * rpc; part = (long long)xcd * WPX + wi; parts = 8LL * WPX; }
-    const int j_begin = (int)(total * part / parts), j_end = (int)(total * (part + 1) / parts);
+    bool affine;
+    int xcd, j_begin, j_end;
+    sep_units(B, rpc, affine, xcd, j_begin, j_end);
     const int nrb = j_end - j_begin;
     const int npts = nrb * kSrRows;
 
@@ -138,55 +113,13 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
         const int b = affine ? xcd + 8 * cl : cl;
         const int m = rbi * kSrRows + (p & 15);
         const char* inb = reinterpret_cast<const char*>(input + (size_t)b * N * C);
-        float acc[NO];
-#pragma unroll
-        for (int v = 0; v < NO; v++) acc[v] = 0.f;
-        int cnt = 0;
         const size_t row = (size_t)b * M + (m < M ? m : 0);
-        if (m < M) {
-            cnt = uniform(nnCount[row]);
-            for (int kt = 0; kt < cnt; kt += 64) {
-                const int myk = kt + lane;
-                const int kn = (cnt - kt) < 64 ? (cnt - kt) : 64;
-                const int mykc = myk < cnt ? myk : kt;
-                const int idxv = nnIndex[row * K + mykc];
-                int binv = binIndex[row * K + mykc];
-                binv = binv < 0 ? 0 : (binv >= F ? F - 1 : binv);
-                binv = myk < cnt ? binv : F;
-                const unsigned pk = ((unsigned)idxv & 0xffffffu) | ((unsigned)binv << 24);
-                for (int k0 = 0; k0 < kn; k0 += 4 * EPL) {
-                    float4 x[4];
-                    unsigned fo[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int kq2 = k0 + u * EPL + g;
-                        const unsigned pp = (unsigned)__shfl((int)pk, kq2);
-                        const unsigned off = __umul24(pp, rowb) + cicb;
-                        fo[u] = __umul24(pp >> 24, (unsigned)FSTB) + cicb;
-                        x[u] = *reinterpret_cast<const float4*>(inb + off);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const float xs[4] = {x[u].x, x[u].y, x[u].z, x[u].w};
-#pragma unroll
-                        for (int q = 0; q < R; q++) {
-                            const float4 w4 = *reinterpret_cast<const float4*>(lfb + fo[u] + q * (SLI * 4));
-                            acc[4 * q + 0] = fmaf(xs[(4 * q + 0) / R], w4.x, acc[4 * q + 0]);
-                            acc[4 * q + 1] = fmaf(xs[(4 * q + 1) / R], w4.y, acc[4 * q + 1]);
-                            acc[4 * q + 2] = fmaf(xs[(4 * q + 2) / R], w4.z, acc[4 * q + 2]);
-                            acc[4 * q + 3] = fmaf(xs[(4 * q + 3) / R], w4.w, acc[4 * q + 3]);
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int o = LPE; o < 64; o <<= 1)
-#pragma unroll
-            for (int v = 0; v < NO; v++) acc[v] += __shfl_xor(acc[v], o);
+        const SepSums<R> sums = sep_gather<R, LPE>(lane, g, inb, m < M, row, K, F, nnCount, nnIndex, binIndex, lfb, rowb, cicb, cicb);
+        const int cnt = sums.cnt;
+        float acc[NO];
         const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.f;            // rows past M / empty rows: zeros
 #pragma unroll
-        for (int v = 0; v < NO; v++) acc[v] *= inv;
+        for (int v = 0; v < NO; v++) acc[v] = sums.v[v] * inv;
         if (actl && g == 0) {
             float* ap = ring + (size_t)s * RBF + (size_t)(p & 15) * LDA + li * 4 * R;
 #pragma unroll
@@ -205,20 +138,11 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
 
     // ---- product of local row block jl (ring slot s) with this wave's W columns ----
     auto product_block = [&](int jl, int s) {
-        sr_f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = d0, d2 = d0, d3 = d0;
-        const float* arow = ring + (size_t)s * RBF + (size_t)i16 * LDA + 4 * kq;
-#pragma unroll
-        for (int t = 0; t < KT; t++) {
-            const sr_f32x4 a = *reinterpret_cast<const sr_f32x4*>(arow + 16 * t);
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wreg[t][0], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wreg[t][1], d1, 0, 0, 0);
-            d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wreg[t][2], d2, 0, 0, 0);
-            d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wreg[t][3], d3, 0, 0, 0);
-        }
+        const SepChains c = sep_product<KT>(ring + (size_t)s * RBF + (size_t)i16 * LDA + 4 * kq, wreg);
         // the slot's rows are in registers / the matrix pipe: hand the slot back before the epilogue's HBM stores
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         sr_raise(&consumed[s], lane);
-        const sr_f32x4 d = (d0 + d1) + (d2 + d3);
+        const sep_f32x4 d = (c.d0 + c.d1) + (c.d2 + c.d3);
         const int j = j_begin + jl;
         const int cl = j / rpc, rbi = j - cl * rpc;
         const int b = affine ? xcd + 8 * cl : cl;
@@ -230,11 +154,11 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
                 float y = d[r4] + bv;
                 if (TRAIN) {
                     output[((size_t)b * M + m) * Cout + col] = y;
-                    const float z = sr_elu(y);
+                    const float z = elu1(y);
                     sz += z;
                     sq = fmaf(z, z, sq);
                 } else {
-                    if (act == 1) y = sr_elu(y);
+                    if (act == 1) y = elu1(y);
                     output[((size_t)b * M + m) * Cout + col] = fmaf(y, sc, sh);
                 }
             }
@@ -305,76 +229,12 @@ __global__ __launch_bounds__(1024) void sepconv_ring_kernel(
     }
 }
 
-static size_t sr_filter_floats(int F, int C, int r)
+// the instantiation a plan names (sepconv.hpp: sep_launch)
+SepRingKernel sepring_kernel(const SepPlan& p)
 {
-    const size_t lpe = C <= 64 ? 16 : 32;
-    return (size_t)(F + 1) * 4 * lpe * r;
-}
-
-static int sr_ktp(int C, int r)
-{
-    const int KT = (C * r + 15) / 16;
-    return KT <= 4 ? 4 : (KT <= 8 ? 8 : 16);
-}
-
-// ring depth: as many 16-point row blocks as fit beside the filter table (at most 8)
-static int sr_ring_depth(int F, int C, int r)
-{
-    const size_t rb = sizeof(float) * kSrRows * (size_t)(sr_ktp(C, r) * 16 + 4);
-    const size_t fixed = sizeof(float) * sr_filter_floats(F, C, r) + 256;
-    if (fixed + 3 * rb > 160 * 1024) return 0;
-    size_t nb = (160 * 1024 - fixed) / rb;
-    return nb > 8 ? 8 : (int)nb;
-}
-
-static bool sr_shape_ok(int N, int F, int C, int r, int K, int Cout)
-{
-    // Cout: 16 column-block owners must divide the 16 waves
-    const bool cout_ok = Cout == 16 || Cout == 32 || Cout == 64 || Cout == 128 || Cout == 256;
-    return (r == 1 || r == 2) && C % 4 == 0 && C >= 4 && C <= 128 && C * r <= 256 && cout_ok && F <= 254 && N <= (1 << 24) && K > 0 &&
-           (unsigned long long)N * C * 4ull + 1024ull < (1ull << 32) && sr_ring_depth(F, C, r) >= 3;
-}
-
-template <int R, int LPE, bool TRAIN>
-static int sr_launch(int B, int N, int M, int F, int C, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                     const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                     const float* scale, const float* shift, float* output, float* dw_out, float* stats, hipStream_t st)
-{
-    const int KTP = sr_ktp(C, R);
-    const int NB = sr_ring_depth(F, C, R);
-    const size_t lds = sizeof(float) * (sr_filter_floats(F, C, R) + (size_t)NB * kSrRows * (KTP * 16 + 4)) + sizeof(int) * (2 + 2 * NB);
-    SPH3D_REQUIRE(NB >= 3 && lds <= 160 * 1024, "SeparableConv3dRing: %zu B of LDS needed", lds);
-    auto kern = KTP == 4 ? sepconv_ring_kernel<R, LPE, 4, TRAIN> : (KTP == 8 ? sepconv_ring_kernel<R, LPE, 8, TRAIN> : sepconv_ring_kernel<R, LPE, 16, TRAIN>);
-    int rc = launch_lds<48 * 1024>(kern, dim3(256), dim3(1024), lds, st, "SeparableConv3dRing", B, N, M, F, C, K, Cout, act, NB, nn_index,
-                                   nn_count, bin_index, input, dw_filter, W, bias, scale, shift, output, dw_out, stats);
-    if (rc) return rc;
-    return check_launch("sph3d_separable_conv3d_ring");
-}
-
-template <bool TRAIN>
-static int sr_dispatch(int B, int N, int M, int F, int C, int r, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                       const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                       const float* scale, const float* shift, float* output, float* dw_out, float* stats, hipStream_t st)
-{
-    if (C <= 64)
-        return r == 2 ? sr_launch<2, 16, TRAIN>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, dw_filter, W, bias, scale,
-                                                shift, output, dw_out, stats, st)
-                      : sr_launch<1, 16, TRAIN>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, dw_filter, W, bias, scale,
-                                                shift, output, dw_out, stats, st);
-    return r == 2 ? sr_launch<2, 32, TRAIN>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, dw_filter, W, bias, scale,
-                                            shift, output, dw_out, stats, st)
-                  : sr_launch<1, 32, TRAIN>(B, N, M, F, C, K, Cout, act, nn_index, nn_count, bin_index, input, dw_filter, W, bias, scale,
-                                            shift, output, dw_out, stats, st);
-}
-
-// used by sepconv.hip: the inference layer through the ring kernel where it covers the shape
-bool sepring_infer_ok(int N, int F, int C, int r, int K, int Cout) { return sr_shape_ok(N, F, C, r, K, Cout); }
-int sepring_infer(int B, int N, int M, int F, int C, int r, int K, int Cout, int act, const int* nn_index, const int* nn_count,
-                  const int* bin_index, const float* input, const float* dw_filter, const float* W, const float* bias,
-                  const float* scale, const float* shift, float* output, hipStream_t st)
-{
-    return sr_dispatch<false>(B, N, M, F, C, r, K, Cout, act, nn_index, nn_count, bin_index, input, dw_filter, W, bias, scale, shift,
-                              output, nullptr, nullptr, st);
+    return sep_with_triple(p, [&](auto R, auto L, auto KT) -> SepRingKernel {
+        return p.train ? sepconv_ring_kernel<R(), L(), KT(), true> : sepconv_ring_kernel<R(), L(), KT(), false>;
+    });
 }
 
 }  // namespace sph3d
@@ -383,13 +243,12 @@ using namespace sph3d;
 
 extern "C" int sph3d_separable_conv3d_train_supported(int N, int F, int C, int r, int K, int Cout)
 {
-    return sr_shape_ok(N, F, C, r, K, Cout) ? 1 : 0;
+    return sep_plan(true, 0, N, 0, F, C, r, K, Cout).kernel != kSepNone;
 }
 
 extern "C" int sph3d_separable_conv3d_train_blocks(int Cout)
 {
-    if (Cout < 16 || Cout > 256 || (Cout & (Cout - 1)) != 0) return 0;
-    return 256 * (kSrWaves / (Cout >> 4));
+    return sep_plan(true, 0, 1, 0, 1, 4, 1, 1, Cout).stats_blocks;      // Cout alone decides: the plan of the narrowest layer
 }
 
 extern "C" int sph3d_separable_conv3d_train(int B, int N, int M, int F, int C, int r, int K, int Cout,
@@ -398,17 +257,16 @@ extern "C" int sph3d_separable_conv3d_train(int B, int N, int M, int F, int C, i
                                             const float* bias, float* depthwise_output, float* y, float* partial,
                                             sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && F > 0 && C > 0 && K > 0 && Cout > 0,
-                  "SeparableConv3dTrain: bad dims B=%d N=%d M=%d F=%d C=%d K=%d Cout=%d", B, N, M, F, C, K, Cout);
-    if (!sr_shape_ok(N, F, C, r, K, Cout)) {
+    if (int rc = sep_check_dims("SeparableConv3dTrain", B, N, M, F, C, K, Cout)) return rc;
+    const SepPlan p = sep_plan(true, B, N, M, F, C, r, K, Cout);
+    if (p.kernel == kSepNone) {
         set_error("SeparableConv3dTrain: shape C=%d r=%d Cout=%d F=%d not covered (C %% 4 == 0, C <= 128, C*r <= 256, "
                   "Cout in {16, 32, 64, 128, 256}, r in {1, 2})", C, r, Cout, F);
         return SPH3D_EUNSUPPORTED;
     }
     SPH3D_REQUIRE(depthwise_output != nullptr && y != nullptr && partial != nullptr, "SeparableConv3dTrain: NULL output");
-    // (B == 0 or M == 0: the launch still writes the all-zero partial rows the statistics finalize reads)
-    return sr_dispatch<true>(B, N, M, F, C, r, K, Cout, 0, nn_index, nn_count, bin_index, input, depthwise_filter, pointwise_weights,
-                             bias, nullptr, nullptr, y, depthwise_output, partial, as_stream(stream));
+    return sep_launch(p, {B, N, M, F, C, K, Cout, 0, nn_index, nn_count, bin_index, input, depthwise_filter, pointwise_weights, bias, nullptr,
+                          nullptr, y, depthwise_output, partial}, as_stream(stream));
 }
 
 extern "C" int sph3d_separable_conv3d_ring_failures(void)

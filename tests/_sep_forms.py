@@ -1,7 +1,9 @@
-"""The launchers' rules of csrc/sepring.hip and csrc/sepconv.hip, restated (copied from the launchers: which of the three
-one-kernel separable layers a call takes, which instantiation, which ring depth or tile height, and how the 256 workgroups share
-the row blocks or tiles), and the case lists of tests/test_gpu_sep_forms.py that are chosen by those rules.  Plain Python: no
-torch, no library, so the CPU test of the case lists' coverage (tests/test_sep_ref.py) and the GPU tests share one statement.
+"""The launchers' rules of csrc/sepring.hip and csrc/sepconv.hip, restated (copied from the launchers as they stood before the
+choice was gathered into csrc/sepconv.hpp: sep_plan — which of the three one-kernel separable layers a call takes, which
+instantiation, which ring depth or tile height, and how the 256 workgroups share the row blocks or tiles), and the case lists of
+tests/test_gpu_sep_forms.py that are chosen by those rules.  Plain Python: no torch, no library, so the CPU test of the case lists'
+coverage (tests/test_sep_ref.py) and the GPU tests share one statement; tests/test_sep_forms.py holds the library's host-only
+query (sph3d_separable_conv3d_plan) to plan() below, field for field.
 
   sepconv_ring_kernel<R, LPE, KT, TRAIN>   sepring.hip   tag "ring<R,LPE,KT> NBn Gg wrapw"   (training: "train<R,LPE,KT> ...")
       NB ring slots, G = 16 / (Cout / 16) wave groups, w = how often the busiest workgroup comes back to a slot it has used
@@ -107,12 +109,37 @@ def wave_groups(Cout):
     return WAVES // (Cout >> 4)
 
 
-def _ring_form(kind, B, M, F, C, r, Cout):
-    NB, G = sr_ring_depth(F, C, r), wave_groups(Cout)
+# the order in which sph3d_separable_conv3d_plan writes its output; kernel: 0 unsupported, 1 ring, 2 small, 3 general
+FIELDS = ("kernel", "R", "LPE", "KT", "RBK", "rbk_by_points", "NB", "G", "lds", "grid", "stats_blocks")
+UNSUPPORTED, RING, SMALL, GENERAL = range(4)
+
+
+def plan(train, B, N, M, F, C, r, K, Cout):
+    """what sph3d_separable_conv3d_train (train = 1) or sph3d_separable_conv3d_fused (0) launches -> a dict of FIELDS (all 0:
+    SPH3D_EUNSUPPORTED; grid 0: nothing is launched).  No partition(): cheap enough for a grid of shapes"""
+    p = dict.fromkeys(FIELDS, 0)
+    ring, small = sr_shape_ok(N, F, C, r, K, Cout), sc_shape_ok(N, F, C, r, K, Cout)
+    if not ring if train else not (small or sc_general_ok(N, F, C, r, K, Cout)):
+        return p
+    p.update(R=r, LPE=lpe_of(C), grid=WORKGROUPS if train or (B > 0 and M > 0) else 0)
+    if ring:
+        NB, KT = sr_ring_depth(F, C, r), sr_ktp(C, r)
+        p.update(kernel=RING, KT=KT, NB=NB, G=wave_groups(Cout), stats_blocks=train_blocks(Cout) if train else 0,
+                 lds=4 * (sr_filter_floats(F, C, r) + NB * SR_ROWS * (KT * 16 + 4)) + 4 * (2 + 2 * NB))
+    elif small:
+        p.update(kernel=SMALL, KT=sr_ktp(C, r), lds=sc_small_lds(F, C, r))
+    else:
+        by_points, rbk = general_rbk(B, M, F, C, r)
+        p.update(kernel=GENERAL, RBK=rbk, rbk_by_points=by_points, lds=sc_general_lds(F, C, r, rbk))
+    return p
+
+
+def _ring_form(kind, p, B, M):
+    NB, G = p["NB"], p["G"]
     per_wg = [len(u) for u in partition(B, (M + SR_ROWS - 1) // SR_ROWS)]
     nrb_max = max(per_wg)
     wrap = max(nrb_max - 1, 0) // NB
-    inst = (r, lpe_of(C), sr_ktp(C, r))
+    inst = (p["R"], p["LPE"], p["KT"])
     return dict(kernel=kind, inst=inst, NB=NB, G=G, nrb_max=nrb_max, wrap=wrap, idle=per_wg.count(0), units=sum(per_wg),
                 affine=(B & 7) == 0, tag="%s<%d,%d,%d> NB%d G%d wrap%d" % ((kind,) + inst + (NB, G, wrap)))
 
@@ -120,32 +147,32 @@ def _ring_form(kind, B, M, F, C, r, Cout):
 def infer_form(B, N, M, F, C, r, K, Cout):
     """sph3d_separable_conv3d_fused -> a dict; "tag" names the launch form ("unsupported": SPH3D_EUNSUPPORTED, "empty": nothing is
     launched)"""
-    small = sc_shape_ok(N, F, C, r, K, Cout)
-    if not small and not sc_general_ok(N, F, C, r, K, Cout):
+    p = plan(0, B, N, M, F, C, r, K, Cout)
+    if p["kernel"] == UNSUPPORTED:
         return dict(kernel="unsupported", tag="unsupported")
-    if B == 0 or M == 0:
+    if p["grid"] == 0:
         return dict(kernel="empty", tag="empty")
-    if sr_shape_ok(N, F, C, r, K, Cout):
-        return _ring_form("ring", B, M, F, C, r, Cout)
+    if p["kernel"] == RING:
+        return _ring_form("ring", p, B, M)
     affine = (B & 7) == 0
-    if not small:
-        by_points, rbk = general_rbk(B, M, F, C, r)
-        lpe = lpe_of(C)
+    if p["kernel"] == GENERAL:
+        rbk, lpe = p["RBK"], p["LPE"]
         per_wg = [len(u) for u in partition(B, (M + 16 * rbk - 1) // (16 * rbk))]
         nslices = (C + 4 * lpe - 1) // (4 * lpe)
-        return dict(kernel="general", inst=(r, lpe, rbk), rbk=rbk, rbk_by_points=by_points, nslices=nslices, ncb=Cout >> 4,
+        return dict(kernel="general", inst=(r, lpe, rbk), rbk=rbk, rbk_by_points=p["rbk_by_points"], nslices=nslices, ncb=Cout >> 4,
                     partial_slice=C % (4 * lpe) != 0, idle=per_wg.count(0), units=sum(per_wg), affine=affine,
                     tag="general<%d,%d,%d> slices%d" % (r, lpe, rbk, nslices))
     per_wg = [len(u) for u in partition(B, (M + SC_TILE - 1) // SC_TILE)]
-    inst = (r, lpe_of(C), sr_ktp(C, r))
+    inst = (p["R"], p["LPE"], p["KT"])
     return dict(kernel="small", inst=inst, idle=per_wg.count(0), units=sum(per_wg), affine=affine, tag="small<%d,%d,%d>" % inst)
 
 
 def train_form(B, N, M, F, C, r, K, Cout):
     """sph3d_separable_conv3d_train: the ring kernel or SPH3D_EUNSUPPORTED; B = 0 or M = 0 still launch (all-zero partial rows)"""
-    if not sr_shape_ok(N, F, C, r, K, Cout):
+    p = plan(1, B, N, M, F, C, r, K, Cout)
+    if p["kernel"] == UNSUPPORTED:
         return dict(kernel="unsupported", tag="unsupported")
-    return _ring_form("train", B, M, F, C, r, Cout)
+    return _ring_form("train", p, B, M)
 
 
 def train_blocks(Cout):
@@ -160,7 +187,7 @@ def train_blocks(Cout):
 TRIPLES = {(1, 16, 4): (4, 64, 1), (2, 16, 4): (4, 32, 2), (2, 16, 8): (36, 64, 2), (1, 32, 8): (68, 128, 1),
            (2, 32, 16): (68, 128, 2)}                                  # -> (smallest C, largest C, r)
 GENERAL_INSTS = [(R, lpe, rbk) for R in (1, 2) for lpe in (16, 32) for rbk in (1, 2, 4)]
-# compiled by the launchers' ternaries and reached by no shape: C <= 64 gives C r <= 128 (KT <= 8), and r = 1 with C <= 64
+# the triples no (C, r) yields, which the library does not contain: C <= 64 gives C r <= 128 (KT <= 8), and r = 1 with C <= 64
 # gives KT <= 4; C >= 68 gives KT >= 5 (r = 1: <= 8) and, r = 2, KT >= 9
 UNREACHED_TRIPLES = [(1, 16, 8), (1, 16, 16), (2, 16, 16), (1, 32, 4), (1, 32, 16), (2, 32, 4), (2, 32, 8)]
 

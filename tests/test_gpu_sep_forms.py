@@ -3,8 +3,10 @@ sepconv_fused_kernel and sepconv_general_kernel) per element against float64 (te
 the C ABI.
 
 sph3d_separable_conv3d_fused picks one of three kernels and an instantiation from the dimensions; every case restates the rule
-that selects its form as an assertion — the functions of tests/_sep_forms.py are copied from the launchers, and the two
-predicates the library can be asked about are compared with its answer over a sweep that crosses each boundary.  Outputs are
+that selects its form as an assertion — the functions of tests/_sep_forms.py are copied from the launchers as they stood before
+csrc/sepconv.hpp: sep_plan — and every call asserts that the library's own plan for it (sph3d_separable_conv3d_plan) is that
+form: kernel, instantiation, ring depth, wave groups.  The two predicates the library can be asked about are compared with its
+answer over a sweep that crosses each boundary.  Outputs are
 pre-filled with NaN, the statistics partials included (an idle workgroup's row that is not written shows); after every ring launch
 sph3d_separable_conv3d_ring_failures() must be 0.  Graphs come from make_graph (rows of count 0, 1, 2, K - 1 and K in every cloud),
 bin ids are synthetic, data differ per cloud.  The checks print the used fraction of each derived bound behind a [form] tag:
@@ -12,6 +14,7 @@ DESIGN.md §2 quotes the maxima.
 
 Left out on purpose: the ring's spin limit and abort flag (they are for a broken launch), the 32-bit-offset limits (N C near
 2^32, N above 2^24) and neighbour ids outside [0, N)."""
+import ctypes
 import functools
 
 import numpy as np
@@ -19,7 +22,7 @@ import pytest
 import torch
 
 from _conv_ref import clamp_bins, make_values
-from _sep_forms import (EDGE_CASES, GENERAL_FORM_CASES, GENERAL_LDS_CASES, GENERAL_RBK_CASES, GENERAL_SLICE_CASES, K130_CASES,
+from _sep_forms import (EDGE_CASES, FIELDS, GENERAL_FORM_CASES, GENERAL_LDS_CASES, GENERAL_RBK_CASES, GENERAL_SLICE_CASES, K130_CASES,
                         PARTITION_CASES, RING_FORM_CASES, RING_REUSE_CASES, SMALL_FORM_CASES, SUPPORT_SWEEP, case_id, form_of,
                         fused_supported, infer_form, sr_shape_ok, train_blocks, train_form)
 from _sep_ref import SepRef, check_infer, check_train, make_inputs
@@ -58,8 +61,22 @@ def _out(t, dev):
     return P(t) if t.numel() else P(torch.zeros(1, dtype=torch.float32, device=dev))
 
 
+def _assert_library_plan(c, train):
+    """what the library launches for the case is the form the restated rules give: kernel, instantiation, ring depth, wave groups"""
+    out = (ctypes.c_int * len(FIELDS))()
+    assert _lib.lib().sph3d_separable_conv3d_plan(train, *_shape(c), ctypes.cast(out, ctypes.c_void_p)) == OK
+    p, form = dict(zip(FIELDS, out)), (train_form if train else infer_form)(*_shape(c))
+    if form["kernel"] in ("unsupported", "empty"):
+        assert (p["kernel"] == 0) == (form["kernel"] == "unsupported") and p["grid"] == 0, (p, form)
+        return
+    assert p["kernel"] == {"ring": 1, "train": 1, "small": 2, "general": 3}[form["kernel"]] and p["grid"] == 256, (p, form)
+    assert (p["R"], p["LPE"], p["RBK"] if form["kernel"] == "general" else p["KT"]) == form["inst"], (p, form)
+    assert (p["NB"], p["G"]) == (form.get("NB", 0), form.get("G", 0)), (p, form)
+
+
 def _infer(dev, c, d, tail, bins=None, x=None, expect=OK):
     """sph3d_separable_conv3d_fused into a NaN-filled output -> [B, M, Cout]"""
+    _assert_library_plan(c, 0)
     with_bias, act, bn = {"none": (0, 0, 0), "bias": (1, 0, 0), "bias+elu+bn": (1, 1, 1)}[tail]
     l = _lib.lib()
     args = [_t(d["idx"], dev), _t(d["cnt"], dev), _t(d["bins"] if bins is None else bins, dev), _t(d["x"] if x is None else x, dev),
@@ -75,6 +92,7 @@ def _infer(dev, c, d, tail, bins=None, x=None, expect=OK):
 
 def _train(dev, c, d, with_bias, bins=None, x=None):
     """sph3d_separable_conv3d_train into NaN-filled outputs -> (depthwise [B, M, C r], y [B, M, Cout], partial [nblk, 2, Cout])"""
+    _assert_library_plan(c, 1)
     l = _lib.lib()
     nblk = l.sph3d_separable_conv3d_train_blocks(c.Cout)
     assert nblk == train_blocks(c.Cout)

@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-__device__ __forceinline__ float elu1(float y) { return y > 0.f ? y : __expf(y) - 1.f; }      // == sepring.hip: sr_elu
+__device__ __forceinline__ float elu1(float y) { return y > 0.f ? y : __expf(y) - 1.f; }      // a copy of csrc/common.hpp: elu1 (this program stands alone)
 
 constexpr int kBlocks = 4096, kThreads = 256;
 
