@@ -69,7 +69,8 @@ const char* sph3d_build_info(void);          /* "gfx950 hipcc <ver> ..." */
  * When no query of a call needs that growth, the radius of a query is a function of its position in the chain alone, and
  * every query is independent (csrc/nngrid.hip): the early positions — radius <= 3 * radius, the queries that would otherwise
  * scan the whole cloud for a handful of hits — are searched over a cell grid, the late ones by an early-stopping scan per
- * query.  Whenever some query does need the growth (device-side flag, no host round trip) the chain walk over the cloud
+ * query; clouds of at most 1024 points (3 to 32 of them) go through that scan alone, no grid, with a workspace of
+ * about a kilobyte.  Whenever some query does need the growth (device-side flag, no host round trip) the chain walk over the cloud
  * (csrc/nnquery.hip) computes the call.  Same rows bit for bit either way.
  * Where the grid lives: the entry points WITH the reference launcher's signature (no workspace argument:
  * sph3d_build_sphere_neighbor[_fixed], sph3d_build_sphere_graph[_ocml]) are conveniences that keep one library-owned
@@ -81,7 +82,7 @@ const char* sph3d_build_info(void);          /* "gfx950 hipcc <ver> ..." */
  * current device (call it before destroying the stream), sph3d_release_all_scratch() every buffer of the current device;
  * both return the number of buffers freed. */
 #define SPH3D_MAX_GROWTH_PASSES 4096
-/* diagnostic: calls so far in this process whose early positions went through the cell grid */
+/* diagnostic: calls so far in this process that went through the cell grid or, on small clouds, through its scan alone */
 long long sph3d_nngrid_launches(void);
 int sph3d_build_sphere_neighbor(int B, int N, int M, int nn_sample, float radius,
                                 const float* database, const float* query,

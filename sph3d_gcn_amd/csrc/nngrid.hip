@@ -118,6 +118,20 @@ __device__ __forceinline__ void sort_by_cell(int n, int ncell, int* hist, int* t
     __syncthreads();
 }
 
+// The radius of every chain position in use (<= kMaxPositions) and the exact threshold of its predicate: wave `w` of `nw`
+// computes T(r_k) for k = w, w + nw, ... (wave-cooperative search: all 64 lanes).  The clouds b, b + 32, ... share a reference
+// block, whose chains go on from cloud to cloud (position = (b / 32) * slices per cloud + j / 1024)
+__device__ __forceinline__ void fill_radii(int fixed, int clouds, int M, float radius, GridRadii* __restrict__ radii, int w, int nw)
+{
+    const int have = fixed ? 1 : ((clouds + kRefGrid - 1) / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock);
+    for (int k0 = w; k0 < have; k0 += nw) {
+        float rk = radius;
+        for (int k = 0; k < k0; k++) rk = (float)((double)rk + 0.05);  // tf_nnquery_gpu.cu:59, the chain kernel's sequence
+        const float T = range_threshold(rk);
+        if (lane_id() == 0) { radii->thr[k0] = T; radii->rk[k0] = rk; }
+    }
+}
+
 // npos: chain positions the grid takes (queries j < npos * 1024; `fixed` mode: every query is position 0, npos = 1 and all M)
 __global__ __launch_bounds__(1024) void nngrid_build_kernel(
     int N, int M, int npos, int fixed, float radius, const float* __restrict__ database,
@@ -155,18 +169,7 @@ __global__ __launch_bounds__(1024) void nngrid_build_kernel(
     __syncthreads();
     if (nonfinite) bad = 1;
     __syncthreads();
-    // the radius of position k and the exact threshold of its predicate: wave k computes T(r_k) (wave-cooperative search)
-    if (b == 0) {
-        // positions in use (<= kMaxPositions): the clouds b, b + 32, ... share a reference block, whose chains go on from cloud
-        // to cloud (position = (b / 32) * slices per cloud + j / 1024)
-        const int have = fixed ? 1 : (((int)gridDim.x + kRefGrid - 1) / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock);
-        for (int k0 = w; k0 < have; k0 += 16) {
-            float rk = radius;
-            for (int k = 0; k < k0; k++) rk = (float)((double)rk + 0.05);  // tf_nnquery_gpu.cu:59, the chain kernel's sequence
-            const float T = range_threshold(rk);
-            if (lane == 0) { radii->thr[k0] = T; radii->rk[k0] = rk; }
-        }
-    }
+    if (b == 0) fill_radii(fixed, (int)gridDim.x, M, radius, radii, w, 16);
     if (tid == 0) {
         float l3[3], h3[3];
         for (int a = 0; a < 3; a++) {
@@ -406,7 +409,7 @@ __global__ __launch_bounds__(64) void nngrid_search_kernel(
 constexpr int kDenseQ = 4;              // queries per wave: they share every trip's points
 template <bool FUSE>
 __global__ __launch_bounds__(256) void nndense_kernel(
-    int B, int N, int M, int K, int j0, int parts, GraphFuse fx, int* __restrict__ flag, const GridRadii* __restrict__ radii,
+    int B, int N, int M, int K, int j0, int parts, int fixed, GraphFuse fx, int* __restrict__ flag, const GridRadii* __restrict__ radii,
     const GridHdr* __restrict__ hdr, const float* __restrict__ database, const float* __restrict__ query,
     int* __restrict__ nnIndex, int* __restrict__ nnCount, float* __restrict__ nnDist)
 {
@@ -420,7 +423,7 @@ __global__ __launch_bounds__(256) void nndense_kernel(
     int* h = lhits + w * kDenseQ * K;
     const float* db = database + (size_t)b * N * 3;
     if (jw < hdr[b].nq) return;                       // this cloud's early positions: the grid's
-    const float T = radii->thr[(b / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock) + jw / kRefBlock];
+    const float T = radii->thr[fixed ? 0 : (b / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock) + jw / kRefBlock];
     float qx[kDenseQ], qy[kDenseQ], qz[kDenseQ];
     int s[kDenseQ];
     bool live[kDenseQ];
@@ -527,14 +530,94 @@ __global__ __launch_bounds__(256) void nndense_kernel(
     }
 }
 
+// Clouds of at most 1024 points (nnsmall_search): no cell grid pays there, and the scan above needs none — what it reads of the
+// build kernel's output is the table of thresholds and, per cloud, a header that says "valid, nothing taken by the grid"
+// (nx != 0, nq = 0).  ONE workgroup, a wave per cloud (B <= 32 clouds over 16 waves), writes exactly that and the flag itself: 0, or
+// 1 for non-finite coordinates as the build raises it — so the call needs no memset in front.
+__global__ __launch_bounds__(1024) void nnsmall_prepare_kernel(int B, int N, int M, int fixed, float radius,
+                                                               const float* __restrict__ database, int* __restrict__ flag,
+                                                               GridRadii* __restrict__ radii, GridHdr* __restrict__ hdr)
+{
+    __shared__ int anybad;
+    const int lane = lane_id(), w = (int)threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
+    if (threadIdx.x == 0) anybad = 0;
+    __syncthreads();
+    for (int b = w; b < B; b += nw) {                 // wave-uniform
+        const float* db = database + (size_t)b * N * 3;
+        // (no short circuit: the loads do not wait for each other)
+        float worst = 0.0f;
+        for (int e = lane; e < N * 3; e += 64) {
+            const float a = fabsf(db[e]);
+            worst = a < INFINITY ? worst : INFINITY;              // NaN and +-inf
+        }
+        const bool bad = __builtin_amdgcn_ballot_w64(worst != 0.0f) != 0ull;
+        if (lane == 0) {
+            GridHdr H{};
+            H.nx = bad ? 0 : 1; H.ny = 1; H.nz = 1;
+            H.nq = 0;
+            hdr[b] = H;
+            if (bad) anybad = 1;
+        }
+    }
+    fill_radii(fixed, B, M, radius, radii, w, nw);
+    __syncthreads();
+    if (threadIdx.x == 0) *flag = anybad;
+}
+
 static std::atomic<long long> g_grid_launches{0};
 
-// bytes of the cell grid of one call: header + flag, cell starts, the cloud in cell order, the query orders
+// the shapes nnsmall_search takes (minus what depends on K): where the grid declines, every query of a small cloud as an
+// independent wave.  Beyond 32 clouds (two clouds per reference block) the chain kernel keeps the call — and so do batches of
+// one or two clouds: there its launch holds two CUs at most, so a step has nothing to win back from it, and the suite pins
+// those batches to "no workspace, no launch counted" (test_abi, test_gpu_nngrid)
+constexpr int kSmallMinClouds = 3;
+static bool small_shape(int B, int N, int M)
+{
+    return B >= kSmallMinClouds && B <= kRefGrid && N >= 1 && N <= 1024 && M >= 1 && M <= kMaxPositions * kRefBlock;
+}
+// ... and their memory: flag, thresholds, one header per cloud
+static size_t small_bytes(int B) { return (1024 + sizeof(GridHdr) * (size_t)B + 15) & ~(size_t)15; }
+
+// The search's device memory (`total` bytes): the caller's workspace (the `_ws` entry points: no allocation, legal under stream
+// capture), or — the convenience entry points with the reference's signature — the library's buffer of this (device, stream);
+// *ws == nullptr afterwards: none.  0, or the error status of a workspace that is too small or misaligned
+static int search_memory(void* workspace, size_t workspace_bytes, bool library_scratch, hipStream_t st, size_t total,
+                         unsigned char** ws)
+{
+    *ws = (unsigned char*)workspace;
+    if (*ws != nullptr) {
+        if (workspace_bytes < total || (reinterpret_cast<size_t>(*ws) & 15) != 0) {
+            set_error("BuildSphereNeighbor: workspace %zu B < required %zu B (or not 16-byte aligned)", workspace_bytes, total);
+            return SPH3D_EWORKSPACE;
+        }
+    } else if (library_scratch) {
+        *ws = (unsigned char*)stream_scratch(st, total);
+    }
+    return SPH3D_OK;
+}
+
+// the queries j >= j0 of every cloud
+static void launch_dense(int B, int N, int M, int K, int j0, int fixed, const GraphFuse* fuse, int* flag, const GridRadii* radii,
+                         const GridHdr* hdr, const float* database, const float* query, int* nn_index, int* nn_count,
+                         float* nn_dist, hipStream_t st)
+{
+    const int dparts = (M - j0 + 4 * kDenseQ - 1) / (4 * kDenseQ);
+    const size_t dlds = sizeof(int) * 4 * kDenseQ * (size_t)K;
+    if (fuse != nullptr)
+        hipLaunchKernelGGL(nndense_kernel<true>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fixed,
+                           *fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist);
+    else
+        hipLaunchKernelGGL(nndense_kernel<false>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fixed,
+                           GraphFuse{}, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist);
+}
+
+// bytes of the search's memory of one call.  The cell grid: header + flag, cell starts, the cloud in cell order, the query orders
 size_t nngrid_workspace_bytes(int B, int N, int M)
 {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     // shapes the grid never takes (the same test as nngrid_search, minus what depends on K and the radius mode)
-    if (N < 1024 || N > 65536 || M < 64 || M > kMaxPositions * kRefBlock || (long long)N * M < (1LL << 22)) return 0;
+    if (N < 1024 || N > 65536 || M < 64 || M > kMaxPositions * kRefBlock || (long long)N * M < (1LL << 22))
+        return small_shape(B, N, M) ? small_bytes(B) : 0;
     const size_t hdrBytes = 1024 + sizeof(GridHdr) * (size_t)B;
     const size_t csBytes = sizeof(int) * (size_t)B * (kGridMaxCells + 1);
     const size_t ptBytes = sizeof(float4) * (size_t)B * N;
@@ -574,25 +657,17 @@ int nngrid_search(int B, int N, int M, int K, float radius, int fixed, const flo
     const size_t qoBytes = sizeof(int) * (size_t)B * M;
     const size_t a16 = 15;
     const size_t total = ((hdrBytes + a16) & ~a16) + ((csBytes + a16) & ~a16) + ptBytes + qoBytes;
-    // the grid's memory: the caller's workspace (the `_ws` entry points: no allocation, legal under stream capture), or — the
-    // convenience entry points with the reference's signature — the library's buffer of this (device, stream); none: no grid
-    unsigned char* ws = (unsigned char*)workspace;
-    if (ws != nullptr) {
-        if (workspace_bytes < total || (reinterpret_cast<size_t>(ws) & 15) != 0) {
-            set_error("BuildSphereNeighbor: workspace %zu B < required %zu B (or not 16-byte aligned)", workspace_bytes, total);
-            return SPH3D_EWORKSPACE;
-        }
-    } else if (library_scratch) {
-        ws = (unsigned char*)stream_scratch(st, total);
-    }
-    if (ws == nullptr) return 0;
+    unsigned char* ws;
+    int rc = search_memory(workspace, workspace_bytes, library_scratch, st, total, &ws);
+    if (rc) return rc;
+    if (ws == nullptr) return 0;          // no memory: no grid
     int* flag = (int*)ws;
     GridRadii* radii = (GridRadii*)(ws + 64);
     GridHdr* hdr = (GridHdr*)(ws + 1024);
     int* cellStart = (int*)(ws + ((hdrBytes + a16) & ~a16));
     float4* pts = (float4*)((unsigned char*)cellStart + ((csBytes + a16) & ~a16));
     int* qorder = (int*)((unsigned char*)pts + ptBytes);
-    int rc = check_hip(hipMemsetAsync(flag, 0, 16, st), "nngrid: memset");
+    rc = check_hip(hipMemsetAsync(flag, 0, 16, st), "nngrid: memset");
     if (rc) return rc;
     const size_t ldsBuild = sizeof(int) * (size_t)kGridMaxCells;
     hipLaunchKernelGGL(nngrid_build_kernel, dim3(B), dim3(1024), ldsBuild, st, N, M, npos, fixed, radius, database, flag,
@@ -622,17 +697,36 @@ int nngrid_search(int B, int N, int M, int K, float radius, int fixed, const flo
         sl = sl < 0 ? 0 : (sl > S ? S : sl);
         j0 = sl * kRefBlock < M ? sl * kRefBlock : M;
     }
-    if (j0 < M) {
-        const int dparts = (M - j0 + 4 * kDenseQ - 1) / (4 * kDenseQ);
-        const size_t dlds = sizeof(int) * 4 * kDenseQ * (size_t)K;
-        if (fuse != nullptr)
-            hipLaunchKernelGGL(nndense_kernel<true>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fx, flag,
-                               radii, hdr, database, query, nn_index, nn_count, nn_dist);
-        else
-            hipLaunchKernelGGL(nndense_kernel<false>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fx, flag,
-                               radii, hdr, database, query, nn_index, nn_count, nn_dist);
-    }
+    if (j0 < M) launch_dense(B, N, M, K, j0, fixed, fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist, st);
     rc = check_launch("nngrid_search");
+    if (rc) return rc;
+    g_grid_launches.fetch_add(1, std::memory_order_relaxed);
+    *gate = flag;
+    *grid_done = 1 << 20;          // every query is done unless the flag is up
+    return 1;
+}
+
+// Clouds of at most 1024 points, where the grid declines: the chain kernel would put one 16-wave workgroup per cloud on the
+// device and walk ~48 queries per wave one after the other.  Under the grid's own condition — no empty pass, verified on the
+// device — every query is independent here too (M <= 1024: all at position 0; beyond: the tabulated radii), so the
+// early-stopping scan takes ALL of them, j0 = 0, behind a prepare launch instead of a grid build.  Same contract as
+// nngrid_search: same memory rules, same flag, same counter; the gated chain kernel behind it is the fallback.
+int nnsmall_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
+                   int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t st, const int** gate, int* grid_done,
+                   void* workspace, size_t workspace_bytes, bool library_scratch)
+{
+    if (!small_shape(B, N, M) || K > kGridMaxK) return 0;
+    unsigned char* ws;
+    int rc = search_memory(workspace, workspace_bytes, library_scratch, st, small_bytes(B), &ws);
+    if (rc) return rc;
+    if (ws == nullptr) return 0;
+    int* flag = (int*)ws;
+    GridRadii* radii = (GridRadii*)(ws + 64);
+    GridHdr* hdr = (GridHdr*)(ws + 1024);
+    hipLaunchKernelGGL(nnsmall_prepare_kernel, dim3(1), dim3(64 * (B < 16 ? B : 16)), 0, st, B, N, M, fixed, radius, database, flag,
+                       radii, hdr);
+    launch_dense(B, N, M, K, 0, fixed, fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist, st);
+    rc = check_launch("nnsmall_search");
     if (rc) return rc;
     g_grid_launches.fetch_add(1, std::memory_order_relaxed);
     *gate = flag;

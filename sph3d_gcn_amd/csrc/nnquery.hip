@@ -489,8 +489,12 @@ static int sphere_neighbor(int fixed, int B, int N, int M, int nn_sample, float 
     // (device flag `gate`) the chain kernel below recomputes the call, after the fused counters have been cleared again.
     const int* gate = nullptr;
     int grid_done = 0;
-    const int g = nngrid_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
-                                &grid_done, search_ws, search_ws_bytes, library_scratch);
+    int g = nngrid_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
+                          &grid_done, search_ws, search_ws_bytes, library_scratch);
+    // ... and where it declines, clouds of at most 1024 points through its early-stopping scan alone (same flag, same fallback)
+    if (g == 0)
+        g = nnsmall_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
+                           &grid_done, search_ws, search_ws_bytes, library_scratch);
     if (g < 0) return g;
     if (g > 0 && fuse != nullptr && fuse->deg != nullptr) {
         const long long cnt = (long long)B * N * fuse->F + fuse->F;

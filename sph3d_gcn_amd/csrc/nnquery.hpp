@@ -69,6 +69,12 @@ struct GraphFuse {
 int nngrid_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
                   int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t stream, const int** gate, int* grid_done,
                   void* workspace, size_t workspace_bytes, bool library_scratch);
+// Where the grid declines and the cloud has at most 1024 points (3 <= B <= 32, K <= 256): every query through the grid's
+// early-stopping scan, no grid.  Same arguments, same return values, same flag and memory rules as nngrid_search.
+int nnsmall_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
+                   int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t stream, const int** gate, int* grid_done,
+                   void* workspace, size_t workspace_bytes, bool library_scratch);
+// bytes of `workspace` for either of them (0: the shape is the chain kernel's)
 size_t nngrid_workspace_bytes(int B, int N, int M);
 
 
