@@ -360,6 +360,23 @@ int sph3d_farthest_point_sample(int b, int n, int m, const float* inp, int* out,
                                 void* workspace, size_t workspace_bytes,
                                 sph3d_stream_t stream);
 
+/* Keyed inverse-density sampling (csrc/idsample.hip): what inverse_density_sample (tf_ops/sampling/tf_sample.py:27-41, stock TF
+ * ops on the global generator in the reference) draws, as a pure function of (nn_dist, nn_count, seed, step, level).
+ * nn_dist [B,N,K] fp32, nn_count [B,N] i32 (an intra graph's) -> out [B,S] i32.  Point i of cloud b:
+ *   w = (((d[0] + d[1]) + ...) + d[c-1]) / float(c), c = min(nn_count, K): sequential fp32 adds, correctly rounded division, slots
+ *       >= c are not used; invalid if c <= 0 or w is not finite or w <= 0;
+ *   u = ((hi >> 8) + 1) * 2^-24, hi = high word of feed_draw(feed_cloud_key(seed, step, b), 8 + level, i) (csrc/feed_draws.hpp);
+ *   t = sph3d_neglog32(u) / w in fp32 (include/sph3d_log32.h), +inf for an invalid point; key = (bits(t) << 32) | i;
+ * out = the low words of the S smallest keys in ascending key order (invalid points last, by index).  harness/idsample.py states
+ * this in numpy; the two agree bit for bit.  Clouds of more than sph3d_ids_sample_chunk() points sort in chunks and need
+ * sph3d_ids_sample_workspace(B,N) bytes (8-byte aligned; 0 otherwise).  SPH3D_EINVAL: dimensions that are not positive, S > N,
+ * level outside 0..7, a null pointer; SPH3D_EUNSUPPORTED: N > 2^20. */
+size_t sph3d_ids_sample_workspace(int B, int N);
+int sph3d_ids_sample_chunk(void);
+int sph3d_ids_sample(int B, int N, int K, int S, const float* nn_dist, const int* nn_count, unsigned long long seed,
+                     unsigned long long step, int level, int* out, void* workspace, size_t workspace_bytes,
+                     sph3d_stream_t stream);
+
 /* tf.gather_nd with [.., 2] (cloud, point) index pairs, as the model graphs use it on coordinates, neighbour lists and
  * counts of the sampled points (models/SPH3D_s3dis.py:68-72; TensorFlow's stock op in the reference): params is
  * [B, N, row] 4-byte elements, pairs [S, 2] int32, out [S, row].  Out-of-range pairs are clamped. */

@@ -24,6 +24,7 @@ _U64 = np.uint64
 _GOLD = _U64(0x9e3779b97f4a7c15)
 ROUNDS = 6
 PERM, REPL, TURN, TILT, JITTER = 1, 2, 3, 4, 5          # the `purpose` of a draw
+IDS = 8                                                 # .. of the keyed inverse-density sampler: IDS + level (harness/idsample.py)
 
 ANGLE_SIGMA, ANGLE_CLIP = 0.06, 0.18                    # utils/data_util.py:140
 JITTER_SIGMA, JITTER_CLIP = 0.01, 0.02                  # utils/data_util.py:166

@@ -60,10 +60,11 @@ def normalize_xyz(points):
     return points / scale
 
 
-def get_model(points, is_training, config=None, dropout_generator=None, points_ready=None):
+def get_model(points, is_training, config=None, dropout_generator=None, points_ready=None, sample_key=(0, 0)):
     """models/SPH3D_modelnet.py:33-107: points [B, N, 3] -> logits [B, num_cls]
     points_ready: optional event after which `points` is valid (GraphPlan: the plan of this step then overlaps the previous
-    step's backward pass instead of waiting for it)"""
+    step's backward pass instead of waiting for it); sample_key: (seed, step) of the keyed inverse-density sampler
+    (config.sample == 'IDS')"""
     batch_size, num_point = points.shape[0], points.shape[1]
     end_points = {}
     assert num_point == config.num_input
@@ -72,10 +73,10 @@ def get_model(points, is_training, config=None, dropout_generator=None, points_r
     # issued ahead of the feature path on the sampling and graph streams, like the segmentation nets' (s3dis_net.GraphPlan):
     # the normalisation of the coordinates and the global viewing point (:35-44) are its first kernels there
     plan = None
-    if points.is_cuda and config.sample == 'FPS':
+    if points.is_cuda and config.sample in ('FPS', 'IDS'):
         plan = GraphPlan(points[:, :, 0:3], config, decoder=False, global_kernel=[8, 2, 1], global_query="centroid",
                          prepare_input=False, points_ready=points_ready,
-                         xyz_transform=normalize_xyz if config.normalize else None)
+                         xyz_transform=normalize_xyz if config.normalize else None, sample_key=sample_key)
         xyz = plan.xyz0()
         query = None
     else:
@@ -96,7 +97,8 @@ def get_model(points, is_training, config=None, dropout_generator=None, points_r
             xyz = plan.xyz_layers[l]
         else:
             intra_idx, intra_cnt, intra_dst, indices = s3g_util.build_graph(
-                xyz, config.radius[l], config.nn_uplimit[l], config.num_sample[l], sample_method=config.sample)
+                xyz, config.radius[l], config.nn_uplimit[l], config.num_sample[l], sample_method=config.sample,
+                **({"sample_key": sample_key, "level": l} if config.sample == 'IDS' else {}))
             filt_idx = s3g_util.spherical_kernel(xyz, xyz, intra_idx, intra_cnt, intra_dst, config.radius[l],
                                                  kernel=config.kernel)
         net = _separable_conv3d_block(net, config.channels[l], config.binSize, intra_idx, intra_cnt, filt_idx,
@@ -166,9 +168,10 @@ class SPH3DModelNet(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else modelnet_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, is_training=True, dropout_generator=None, points_ready=None):
+    def forward(self, points, is_training=True, dropout_generator=None, points_ready=None, sample_key=(0, 0)):
         with s3g_util.variable_store(self.store):
-            return get_model(points, is_training, self.config, dropout_generator=dropout_generator, points_ready=points_ready)
+            return get_model(points, is_training, self.config, dropout_generator=dropout_generator, points_ready=points_ready,
+                             sample_key=sample_key)
 
     def loss(self, pred, label):
         """train_modelnet.py:162-164: classification loss + the weight-decay 'losses' collection + the BN regularisers

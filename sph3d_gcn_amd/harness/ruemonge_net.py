@@ -49,10 +49,11 @@ def net_input(points, config):
     return torch.cat((norm_xyz, points[:, :, 3:]), dim=2)
 
 
-def get_model(points, is_training, config=None, graphs=None, points_ready=None):
+def get_model(points, is_training, config=None, graphs=None, points_ready=None, sample_key=(0, 0)):
     """models/SPH3D_ruemonge2014.py:33-113: s3dis_net.get_model on the nine-channel input.  A plan handed in as `graphs` is
     GraphPlan(points, config, net_input=ruemonge_net.net_input)."""
-    return s3dis_net.get_model(points, is_training, config, graphs=graphs, points_ready=points_ready, net_input=net_input)
+    return s3dis_net.get_model(points, is_training, config, graphs=graphs, points_ready=points_ready, net_input=net_input,
+                               sample_key=sample_key)
 
 
 def get_loss(pred, label, end_points=None):
@@ -74,9 +75,9 @@ class SPH3DRueMonge(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else ruemonge_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, is_training=True, graphs=None, points_ready=None):
+    def forward(self, points, is_training=True, graphs=None, points_ready=None, sample_key=(0, 0)):
         with s3g_util.variable_store(self.store):
-            return get_model(points, is_training, self.config, graphs=graphs, points_ready=points_ready)
+            return get_model(points, is_training, self.config, graphs=graphs, points_ready=points_ready, sample_key=sample_key)
 
     def loss(self, pred, label):
         return get_loss(pred, label)

@@ -100,6 +100,8 @@ class GraphPlan:
     results as the build_graph / build_graph_deconv / spherical_kernel calls of models/SPH3D_s3dis.py:53-98; only
     the ISSUE ORDER and the STREAMS differ.  On the GPU three HIP streams run concurrently:
       * sampling stream: the FPS chain — m strictly sequential rounds on one workgroup per cloud (16 of 256 CUs);
+                         (config.sample == 'IDS': only the coordinates and the input — level l's sample is drawn from level
+                         l's intra graph, on the graph stream, right behind that graph and in front of its pooling rows)
       * graph stream   : every neighbour search, kernel binning, pooled-row gather and (for the backward pass) the
                          transposed graphs, level by level — VALU / integer-atomic bound work;
       * main stream    : the feature path (convolutions, GEMMs, normalisation) — L2 / MFMA / HBM bound work,
@@ -107,7 +109,7 @@ class GraphPlan:
     On CPU tensors (oracle-backed tests) everything is built lazily on the spot."""
 
     def __init__(self, points, config, overlap=True, points_ready=None, decoder=True, global_kernel=None, global_radius=100.0,
-                 global_query=None, prepare_input=True, need_backward=None, xyz_transform=None, net_input=None):
+                 global_query=None, prepare_input=True, need_backward=None, xyz_transform=None, net_input=None, sample_key=(0, 0)):
         """decoder=False: an encoder-only plan (the classification net); global_kernel: also the global graph of
         models/SPH3D_modelnet.py:83-93 (query = centroid of the last level's points, every remaining point a neighbour) with
         the bins of that kernel (global_query: the query points [B, 1, 3], default the centroid of the last level);
@@ -119,11 +121,17 @@ class GraphPlan:
         SAMPLING STREAM before anything else: the plan is built on its result (xyz_layers[0]; `xyz0()` hands it to the feature
         path), so that with points_ready the whole plan depends on the input batch alone.  global_query="centroid": the
         global graph's query is the mean of those coordinates (models/SPH3D_modelnet.py:44), computed there as well.
+        sample_key: (seed, step) of the keyed inverse-density sampler (config.sample == 'IDS'; tf_sample.inverse_density_sample_keyed:
+        level l draws with level=l) — what a training loop passes to its feed; FPS and random plans do not read it.
         points_ready: optional event after which `points` is valid.  With it the two side streams wait only for the
         INPUT, not for everything queued on the main stream — so when the host runs ahead (it issues a step in about
         half the time the GPU needs), the sampling / graph construction of step t+1 overlaps the backward pass of step
         t instead of idling the main stream at every step boundary (measured: 5.8 ms of main-stream idle per step)."""
         self.config = config
+        if config.sample not in ('FPS', 'random', 'IDS'):
+            raise ValueError('Unknown sampling method.')
+        self._ids = config.sample == 'IDS'
+        self.sample_key = (int(sample_key[0]), int(sample_key[1]))
         self.need_backward = torch.is_grad_enabled() if need_backward is None else bool(need_backward)
         self.decoder = bool(decoder)
         self.global_kernel, self.global_radius, self.global_query = global_kernel, float(global_radius), global_query
@@ -230,29 +238,42 @@ class GraphPlan:
         return self.xyz_layers[0]
 
     def _sampling_chain(self, side):
-        """FPS level after level (each level samples the previous level's samples)."""
+        """FPS level after level (each level samples the previous level's samples).  Inverse-density sampling needs level l's
+        graph for level l's sample: with side streams it is issued by _build_all on the graph stream, without them here, graph
+        and sample in turn (enc(l) then finds the graph built)."""
         config = self.config
+        if self._ids and side is not None:
+            return
         for l in range(len(config.radius)):
-            if config.num_sample[l] > 1:
-                cur = self.xyz_layers[-1]
-                if config.sample == 'FPS':
-                    sample_index = s3g_util.farthest_point_sample(config.num_sample[l], cur)
-                elif config.sample == 'random':
-                    sample_index = s3g_util.random_sample(config.num_sample[l], cur)
-                else:
-                    raise ValueError('Unknown sampling method.')
-                B = cur.shape[0]
-                batch_indices = torch.arange(B, dtype=torch.int32, device=cur.device).view(-1, 1, 1)
-                indices = torch.cat([batch_indices.expand(B, config.num_sample[l], 1),
-                                     sample_index.unsqueeze(2).to(torch.int32)], dim=2)      # util.py:43-45
-                self.indices.append(indices)
-                self.xyz_layers.append(s3g_util.gather_nd(cur, indices))
+            if self._ids:
+                self._enc[l] = self._make_enc(l)
+            self._sample_level(l, side)
+
+    def _sample_level(self, l, stream):
+        """sample level l -> indices[l], xyz_layers[l + 1] and (on a side stream) the level's event, on the current stream"""
+        config = self.config
+        if config.num_sample[l] > 1:
+            cur = self.xyz_layers[-1]
+            if config.sample == 'FPS':
+                sample_index = s3g_util.farthest_point_sample(config.num_sample[l], cur)
+            elif config.sample == 'random':
+                sample_index = s3g_util.random_sample(config.num_sample[l], cur)
             else:
-                self.indices.append(None)
-            if side is not None:
-                ev = torch.cuda.Event()
-                ev.record(side)
-                self.events.append(ev)
+                g = self._enc[l]
+                sample_index = s3g_util.inverse_density_sample_keyed(config.num_sample[l], g["intra_dst"], g["intra_cnt"],
+                                                                     self.sample_key[0], self.sample_key[1], level=l)
+            B = cur.shape[0]
+            batch_indices = torch.arange(B, dtype=torch.int32, device=cur.device).view(-1, 1, 1)
+            indices = torch.cat([batch_indices.expand(B, config.num_sample[l], 1),
+                                 sample_index.unsqueeze(2).to(torch.int32)], dim=2)      # util.py:43-45
+            self.indices.append(indices)
+            self.xyz_layers.append(s3g_util.gather_nd(cur, indices))
+        else:
+            self.indices.append(None)
+        if stream is not None:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            self.events.append(ev)
 
     # ---- graph construction proper (called on the graph stream, or lazily on CPU) ----
     def _make_enc(self, l):
@@ -260,6 +281,8 @@ class GraphPlan:
         xyz = self.xyz_layers[l]
         # util.py:29 + models/SPH3D_s3dis.py:57: neighbour graph and bins of one point set, one fused kernel on the GPU
         idx, cnt, dst, filt = s3g_util.build_intra_graph(xyz, c.radius[l], c.nn_uplimit[l], c.kernel, **self._bw_kw())
+        if self._ids:
+            return dict(intra_idx=idx, intra_cnt=cnt, filt_idx=filt, intra_dst=dst)      # (the level's sample reads the distances)
         return dict(intra_idx=idx, intra_cnt=cnt, filt_idx=filt)
 
     def _bw_kw(self):
@@ -336,7 +359,10 @@ class GraphPlan:
         self._enc[0] = g
         mark(self._enc_ev, 0)
         for s in range(L):                       # s = sampling level that has just become available
-            stream.wait_event(self.events[s])
+            if self._ids:
+                self._sample_level(s, stream)    # (from the graph _make_enc(s) has just queued on this stream)
+            else:
+                stream.wait_event(self.events[s])
             if c.num_sample[s] > 1:
                 self._make_pool(s, self._enc[s])
                 mark(self._pool_ev, s)
@@ -398,7 +424,9 @@ class GraphPlan:
         """rows of the level-l intra graph at the sampled points"""
         g = self.enc(l)
         if self.use_side:
-            self._sync(("pool", l), self._pool_ev[l], [g["inter_idx"], g["inter_cnt"]] + self.xyz_layers[l + 1:l + 2])
+            # (an inverse-density plan's samples are made on the graph stream, in front of the pooling rows: the same event)
+            self._sync(("pool", l), self._pool_ev[l], [g["inter_idx"], g["inter_cnt"]] + self.xyz_layers[l + 1:l + 2]
+                       + (self.indices[l:l + 1] if self._ids else []))
         elif "inter_idx" not in g:
             self._make_pool(l, g)
         return g
@@ -411,9 +439,9 @@ class GraphPlan:
         return self._dec[l]
 
 
-def build_graphs(points, config, overlap=True):
+def build_graphs(points, config, overlap=True, sample_key=(0, 0)):
     """Eagerly build every graph of one forward -> GraphPlan (kept for tests / smoke that inspect the graphs)."""
-    plan = GraphPlan(points, config, overlap=overlap)
+    plan = GraphPlan(points, config, overlap=overlap, sample_key=sample_key)
     for l in range(len(config.radius)):
         plan.enc(l)
         if config.num_sample[l] > 1:
@@ -423,12 +451,13 @@ def build_graphs(points, config, overlap=True):
     return plan
 
 
-def get_model(points, is_training, config=None, graphs=None, points_ready=None, net_input=None):
+def get_model(points, is_training, config=None, graphs=None, points_ready=None, net_input=None, sample_key=(0, 0)):
     """models/SPH3D_s3dis.py:35-113 (config lists are not reversed in place here).  net_input: GraphPlan's (a plan handed in as
-    `graphs` must have been built with the same one)."""
+    `graphs` must have been built with the same one).  sample_key: GraphPlan's (seed, step) for config.sample == 'IDS'."""
     end_points = {}
     reuse = None
-    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready, net_input=net_input)
+    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready, net_input=net_input,
+                                                                sample_key=sample_key)
     if net_input is not None and plan._input_fn is not net_input:
         raise ValueError("get_model: `graphs` was built with another net_input")
     net = plan.input(points)
@@ -537,9 +566,9 @@ class SPH3DS3DIS(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else s3dis_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, is_training=True, graphs=None, points_ready=None):
+    def forward(self, points, is_training=True, graphs=None, points_ready=None, sample_key=(0, 0)):
         with s3g_util.variable_store(self.store):
-            return get_model(points, is_training, self.config, graphs=graphs, points_ready=points_ready)
+            return get_model(points, is_training, self.config, graphs=graphs, points_ready=points_ready, sample_key=sample_key)
 
     def loss(self, pred, label, inner_label):
         return get_loss(pred, label, None, inner_label)

@@ -50,14 +50,14 @@ def small_config(num_input=512):
     return c
 
 
-def _features(points, is_training, config, graphs=None, points_ready=None):
+def _features(points, is_training, config, graphs=None, points_ready=None, sample_key=(0, 0)):
     """the body the two models share (models/SPH3D_shapenet.py:33-104 = models/SPH3D_shapenet_onehot.py:34-108; config lists are
     not reversed in place here): mlp1, encoder, decoder, mlp2 -> (mlp2 output [B, N, mlp], mlp1 features [B, N, mlp])"""
     reuse = None
     net = s3g_util.pointwise_conv3d(points, config.mlp, 'mlp1', weight_decay=config.weight_decay,
                                     with_bn=config.with_bn, with_bias=config.with_bias, reuse=reuse,
                                     is_training=is_training)
-    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready)
+    plan = graphs if graphs is not None else GraphPlan(points, config, points_ready=points_ready, sample_key=sample_key)
     encoder = [net]
     for l in range(len(config.radius)):
         g = plan.enc(l)
@@ -93,10 +93,10 @@ def _features(points, is_training, config, graphs=None, points_ready=None):
     return net, encoder[-1]
 
 
-def get_model(points, num_cls, is_training, config=None, graphs=None, points_ready=None):
-    """models/SPH3D_shapenet.py:33-113"""
+def get_model(points, num_cls, is_training, config=None, graphs=None, points_ready=None, sample_key=(0, 0)):
+    """models/SPH3D_shapenet.py:33-113.  sample_key: GraphPlan's (seed, step) for config.sample == 'IDS'."""
     end_points = {}
-    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready)
+    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready, sample_key=sample_key)
     net = torch.cat((net, skip), dim=2)
     end_points['feats'] = net
     net = s3g_util.pointwise_conv3d(net, num_cls, scope='logits', with_bn=False, with_bias=config.with_bias,
@@ -108,12 +108,12 @@ NUM_CATEGORIES = 16                     # models/SPH3D_shapenet_onehot.py:13
 
 
 def get_model_onehot(points, cls_label, num_cls, is_training, config=None, graphs=None, points_ready=None,
-                     num_categories=NUM_CATEGORIES):
+                     num_categories=NUM_CATEGORIES, sample_key=(0, 0)):
     """models/SPH3D_shapenet_onehot.py:34-121: the same encoder and decoder; the classifier reads the mlp2 output, the mlp1
     features and a one-hot tile of the shape's category (cls_label [B] integers) and gives the logits of all num_cls parts.
     end_points['feats'] is the reference's [B, N, 2 mlp + num_categories] tensor, built on first access: the fused classifier
     (s3g_util.pointwise_conv3d_onehot) never materialises it."""
-    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready)
+    net, skip = _features(points, is_training, config, graphs=graphs, points_ready=points_ready, sample_key=sample_key)
     end_points = _EndPoints()
     end_points.feats_parts = (net, skip, lambda: s3g_util.one_hot_tile(cls_label, num_categories, net.shape[1]))
     net = s3g_util.pointwise_conv3d_onehot(net, skip, cls_label, num_categories, num_cls, scope='logits', with_bn=False,
@@ -134,9 +134,10 @@ class SPH3DShapeNet(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else shapenet_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, is_training=True, graphs=None, points_ready=None):
+    def forward(self, points, is_training=True, graphs=None, points_ready=None, sample_key=(0, 0)):
         with s3g_util.variable_store(self.store):
-            return get_model(points, self.num_cls, is_training, self.config, graphs=graphs, points_ready=points_ready)
+            return get_model(points, self.num_cls, is_training, self.config, graphs=graphs, points_ready=points_ready,
+                             sample_key=sample_key)
 
     def loss(self, pred, label):
         return get_loss(pred, label)
@@ -152,10 +153,10 @@ class SPH3DShapeNetOneHot(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else shapenet_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, cls_label, is_training=True, graphs=None, points_ready=None):
+    def forward(self, points, cls_label, is_training=True, graphs=None, points_ready=None, sample_key=(0, 0)):
         with s3g_util.variable_store(self.store):
             return get_model_onehot(points, cls_label, self.num_cls, is_training, self.config, graphs=graphs,
-                                    points_ready=points_ready, num_categories=self.num_categories)
+                                    points_ready=points_ready, num_categories=self.num_categories, sample_key=sample_key)
 
     def loss(self, pred, label):
         return get_loss(pred, label)

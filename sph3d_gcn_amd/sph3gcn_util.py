@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from . import tf_conv3d, tf_pool3d, tf_unpool3d
 from .tf_nnquery import build_sphere_neighbor, build_cube_neighbor
-from .tf_sample import farthest_point_sample, inverse_density_sample, random_sample
+from .tf_sample import farthest_point_sample, inverse_density_sample, inverse_density_sample_keyed, random_sample
 from .tf_buildkernel import spherical_kernel
 from . import tf_gemm, tf_norm, _lib
 
@@ -179,7 +179,9 @@ def build_global_graph(xyz, query, radius):
     return nn_idx, nn_cnt, nn_dst
 
 
-def build_graph(xyz, radius, nn_uplimit, num_sample, sample_method=None):
+def build_graph(xyz, radius, nn_uplimit, num_sample, sample_method=None, sample_key=None, level=0):
+    """utils/sph3gcn_util.py:28-49.  sample_key=(seed, step) (with sample_method='IDS'): the keyed inverse-density sampler
+    (tf_sample.inverse_density_sample_keyed, draws of `level`) instead of the one that draws from torch's global generator."""
     intra_idx, intra_cnt, intra_dst = neighbor_fn(xyz, xyz, radius=radius, nnsample=nn_uplimit)
 
     if num_sample is not None:
@@ -187,6 +189,8 @@ def build_graph(xyz, radius, nn_uplimit, num_sample, sample_method=None):
             sample_index = random_sample(num_sample, xyz)
         elif sample_method == 'FPS':
             sample_index = farthest_point_sample(num_sample, xyz)
+        elif sample_method == 'IDS' and sample_key is not None:
+            sample_index = inverse_density_sample_keyed(num_sample, intra_dst, intra_cnt, sample_key[0], sample_key[1], level=level)
         elif sample_method == 'IDS':
             prob = torch.sum(intra_dst, dim=-1) / intra_cnt.float()
             sample_index = inverse_density_sample(num_sample, prob)
