@@ -578,6 +578,33 @@ int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int Ca, int Cb
 int sph3d_adam_step(long long n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                     float beta2, float eps, int step, sph3d_stream_t stream);
 
+/* ---- the reference's own optimiser forms (train_s3dis.py:223-226: tf.train.AdamOptimizer(lr, epsilon=1e-4) or
+ * tf.train.MomentumOptimizer(lr, momentum, use_nesterov=True)) over flat fp32 buffers of n elements: one streaming pass, 16-byte
+ * lanes where every pointer is 16-byte aligned, scalar lanes otherwise.  With g = grad_scale * grad (grad_scale: 1 / world size
+ * when a mean loss is sharded over ranks), every operation rounded once:
+ *   rule 0, TensorFlow's Adam (slot0 = m, slot1 = v):  m += (1 - b1)(g - m);  v += (1 - b2)(g g - v);
+ *           p -= (lr_t m) / (sqrt(v) + eps),  lr_t = lr sqrt(1 - b2^step) / (1 - b1^step) computed here in double and rounded
+ *           once; step = 1 for the first update.  (sph3d_adam_step is torch's form, eps outside the bias correction.)
+ *   rule 1, TensorFlow's Nesterov momentum (slot0 = accum, slot1 may be NULL; beta2, eps are not read):
+ *           accum = momentum accum + g;  p -= g lr + (accum momentum) lr.
+ * nonfinite (device, nullable): += the number of elements whose g is not finite; those elements are updated as written.
+ * n == 0 is a no-op; SPH3D_EINVAL: a rule outside {0, 1}, step < 1, n < 0, a null buffer with n > 0. */
+int sph3d_train_update(long long n, float* param, const float* grad, float* slot0, float* slot1, int rule, float lr,
+                       float beta1_or_momentum, float beta2, float eps, int step, float grad_scale, long long* nonfinite,
+                       sph3d_stream_t stream);
+
+/* ---- the reference's per-step training metrics and its one-pass validation counts (train_s3dis.py:371-376, :461-474) on the
+ * device, without the copy of the logits to the host.  logits [B,N,C] fp32, label [B,N] int32, inner [B,N] int32 or NULL (every
+ * row counts: the ShapeNet, RueMonge and ModelNet lines; ModelNet with N = 1).  For every counted row (inner > 0): with the
+ * label outside [0, C) counters[2] += 1 and nothing else; otherwise pred = the first maximum of the row's C logits (a NaN counts
+ * as a maximum, as np.argmax and sph3d_vote_finalize), confusion[label * C + pred] += 1, counters[0] (seen) += 1, counters[1]
+ * (correct) += pred == label, counters[3] += 1 if a logit of the row is not finite.  counters[4] += 1 per call.  loss_sum[0]
+ * (double) += the loss_parts fp32 values at loss_part, added in index order in float64 by one thread (loss_part may be NULL).
+ * confusion [C*C] and counters [5] are int64; everything is accumulated, nothing zeroed, no floating-point atomic is used and the
+ * result is a pure function of the inputs and the order of the calls.  C <= 64 (SPH3D_EUNSUPPORTED above). */
+int sph3d_train_metrics(int B, int N, int C, const float* logits, const int* label, const int* inner, const float* loss_part,
+                        int loss_parts, long long* confusion, long long* counters, double* loss_sum, sph3d_stream_t stream);
+
 /* ---- the input side of the S3DIS training loop (train_s3dis.py:114-142,343-347) on the device: one launch assembles a batch
  * from a resident pool of parsed blocks.  rows [T,8] fp32: all blocks back to back, a row = xyz, rgb, label, inner (what
  * parse_fn builds); offsets [P+1] int64; block_ids [B] int32 (device): the blocks of this batch in batch order.  Per cloud b

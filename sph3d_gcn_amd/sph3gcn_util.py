@@ -340,8 +340,9 @@ def separable_conv3d(inputs,
     # inputs may be a PAIR (a, b): the layer of the reference applied to tf.concat((a, b), axis=2) — same variables, same result —
     # with the depthwise kernels reading the two tensors in place (tf_conv3d.depthwise_conv3d_concat)
     pair = inputs if isinstance(inputs, (tuple, list)) else None
+    # (only on the HIP device: the oracle-backed CPU stand-ins of the tests have no one-kernel layer)
     infer_fused = (FUSE_SEPARABLE_INFERENCE and is_training is not None and not bool(is_training) and not torch.is_grad_enabled()
-                   and (activation_fn is elu or activation_fn is None))
+                   and (activation_fn is elu or activation_fn is None) and (pair[0] if pair is not None else inputs).is_cuda)
     if pair is not None and infer_fused and pair[0].is_cuda and getattr(tf_conv3d, "separable_fused_supported_dims", None) is not None \
             and tf_conv3d.separable_fused_supported_dims(pair[0].shape[1], kernel_size, pair[0].shape[-1] + pair[1].shape[-1],
                                                          depth_multiplier, nn_index.shape[2], num_out_channels) \
