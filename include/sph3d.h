@@ -466,6 +466,34 @@ int sph3d_elu_bn_forward_partials(int R, int C, int nblk, const float* partial, 
                                   const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                                   float* out, float* save_mean, float* save_rstd, sph3d_stream_t stream);
 
+/* ---- the same tail with training-mode statistics over the rows of SEVERAL ranks ---------------------------
+ * sph3d_elu_bn_forward / _backward cut at the statistics: `*_sums` leaves this rank's per-channel sums on the device as doubles,
+ * the caller adds the other ranks' buffers on top (one all-reduce, ordered on `stream`), `*_apply` forms the statistics from the
+ * summed buffer and runs the apply pass.  Nothing returns to the host, nothing is allocated, no entry point synchronises; with the
+ * buffer left as `*_sums` wrote it the pair computes sph3d_elu_bn_forward / _backward (training) bit for bit.  Same shapes
+ * (C % 4 == 0, C <= 1024, R > 0: every rank needs at least one row); workspace: sph3d_elu_bn_workspace(R, C) of the rank's own R. */
+/* sums [2C + 1] (double) = sum elu(y), sum elu(y)^2 per channel, then the row count R.  partial == NULL: the statistics pass over y
+ * runs here (needs the workspace; nblk is ignored); else partial[nblk][2][C] as sph3d_elu_bn_forward_partials takes it (y and the
+ * workspace are not read). */
+int sph3d_elu_bn_forward_sums(int R, int C, int nblk, const float* partial, const float* y, double* sums,
+                              void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+/* sums: the summed [2C + 1] buffer.  mean = S / Rg, var = max(Q / Rg - mean^2, 0) (double); writes save_mean / save_rstd, updates
+ * the running statistics with the biased variance (NULL: not kept), writes the global row count Rg to count [1] (double, read by
+ * sph3d_elu_bn_backward_apply on the device), then out = (elu(y) - mean) * rstd * gamma + beta over this rank's R rows. */
+int sph3d_elu_bn_forward_apply(int R, int C, const double* sums, const float* y, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, float momentum, float eps,
+                               float* out, float* save_mean, float* save_rstd, double* count, sph3d_stream_t stream);
+/* dgamma / dbeta [C]: this rank's sums in fp32 — they stay local, the gradient all-reduce adds the ranks' like any parameter
+ * gradient.  sums [2C] (double) = sum dout, sum dout * zhat per channel. */
+int sph3d_elu_bn_backward_sums(int R, int C, const float* y, const float* dout, const float* save_mean, const float* save_rstd,
+                               float* dgamma, float* dbeta, double* sums,
+                               void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+/* sums: the summed [2C] buffer; count: what sph3d_elu_bn_forward_apply wrote.  dy over this rank's R rows with the two mean terms
+ * S / Rg, Q / Rg. */
+int sph3d_elu_bn_backward_apply(int R, int C, const double* sums, const double* count, const float* y, const float* dout,
+                                const float* gamma, const float* save_mean, const float* save_rstd, float* dy,
+                                void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+
 /* ---- fused separable convolution for inference ---------------------------------------------------------
  * The whole layer of utils/sph3gcn_util.py:134-161 with is_training=False in one kernel: DepthwiseConv3d
  * (tf_conv3d.cpp:34-107 / tf_conv3d_gpu.cu:7-29) -> matmul with pointwise_weights[C*r][Cout] -> + bias[Cout] (NULL: none)

@@ -133,6 +133,10 @@ SIGNATURES = {
     "sph3d_elu_bn_forward_partials": (_I, [_I] * 3 + [_P] * 6 + [_F, _F] + [_P] * 4),
     "sph3d_elu_bn_forward": (_I, [_I, _I, _P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P, _P, _S, _P]),
     "sph3d_elu_bn_backward": (_I, [_I, _I] + [_P] * 5 + [_I] + [_P] * 3 + [_P, _S, _P]),
+    "sph3d_elu_bn_forward_sums": (_I, [_I] * 3 + [_P] * 3 + [_P, _S, _P]),
+    "sph3d_elu_bn_forward_apply": (_I, [_I] * 2 + [_P] * 6 + [_F, _F] + [_P] * 4 + [_P]),
+    "sph3d_elu_bn_backward_sums": (_I, [_I] * 2 + [_P] * 7 + [_P, _S, _P]),
+    "sph3d_elu_bn_backward_apply": (_I, [_I] * 2 + [_P] * 8 + [_P, _S, _P]),
 }
 # test-only hook exported by the library but not part of the reference surface
 _EXTRA = {

@@ -172,6 +172,73 @@ __global__ __launch_bounds__(1024) void norm_bwd_finalize(int R, int C, int nblk
     coef[C + c] = training ? (float)(q / R) : 0.f;
 }
 
+// ---- the same two finalizes cut at the statistics (batch norm over the rows of several ranks) ---------------
+// A rank's per-channel sums leave in double, a collective the caller issues adds the other ranks' on top, and the statistics are
+// formed from what comes back.  The arithmetic after the cut is norm_fwd_finalize's / norm_bwd_finalize's, expression for
+// expression, with the row count a double read from the buffer: unchanged sums give bit-identical statistics.
+
+// forward, before the cut: sums[0..C) = sum z, sums[C..2C) = sum z*z, sums[2C] = R
+__global__ __launch_bounds__(1024) void norm_fwd_sums(int R, int C, int nblk, const float* __restrict__ partial,
+                                                      double* __restrict__ sums)
+{
+    const int c = blockIdx.x * 32 + ((int)threadIdx.x & 31);
+    const int py = (int)threadIdx.x >> 5;
+    double s, q;
+    sum_partials_32x8(C, nblk, partial, c, py, s, q);
+    if (c >= C || py != 0) return;
+    sums[c] = s;
+    sums[C + c] = q;
+    if (c == 0) sums[2 * C] = (double)R;
+}
+
+// forward, after the cut: mean / rstd / running statistics from the summed buffer; the global row count stays on the device
+__global__ __launch_bounds__(256) void norm_fwd_stats_from_sums(int C, const double* __restrict__ sums, float eps, float momentum,
+                                                                float* __restrict__ mean, float* __restrict__ rstd,
+                                                                float* __restrict__ run_mean, float* __restrict__ run_var,
+                                                                double* __restrict__ count)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double s = sums[c], q = sums[C + c], R = sums[2 * C];
+    const double m = s / R;
+    double var = q / R - m * m;
+    if (var < 0.0) var = 0.0;
+    mean[c] = (float)m;
+    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (run_mean != nullptr) {
+        run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * m);
+        run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * var);
+    }
+    if (c == 0) count[0] = R;
+}
+
+// backward, before the cut: this rank's dgamma / dbeta (they stay local sums: the gradient all-reduce adds the ranks') and
+// sums[0..C) = sum dout, sums[C..2C) = sum dout * zhat
+__global__ __launch_bounds__(1024) void norm_bwd_sums(int C, int nblk, const float* __restrict__ partial, float* __restrict__ dgamma,
+                                                      float* __restrict__ dbeta, double* __restrict__ sums)
+{
+    const int c = blockIdx.x * 32 + ((int)threadIdx.x & 31);
+    const int py = (int)threadIdx.x >> 5;
+    double s, q;
+    sum_partials_32x8(C, nblk, partial, c, py, s, q);
+    if (c >= C || py != 0) return;
+    dbeta[c] = (float)s;
+    dgamma[c] = (float)q;
+    sums[c] = s;
+    sums[C + c] = q;
+}
+
+// backward, after the cut: the two per-channel means over the global rows
+__global__ __launch_bounds__(256) void norm_bwd_coef_from_sums(int C, const double* __restrict__ sums, const double* __restrict__ count,
+                                                               float* __restrict__ coef)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const double R = count[0];
+    coef[c] = (float)(sums[c] / R);
+    coef[C + c] = (float)(sums[C + c] / R);
+}
+
 // BWD = false: out = (elu(y) - mean) * rstd * gamma + beta
 // BWD = true : dy  = gamma * rstd * (dout - c0 - zhat * c1) * elu'(y)
 template <bool BWD>
@@ -308,4 +375,94 @@ extern "C" int sph3d_elu_bn_backward(int R, int C, const float* y, const float* 
     hipLaunchKernelGGL(norm_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, total4, C, y, dout, save_mean,
                        save_rstd, gamma, nullptr, coef, dy);
     return check_launch("sph3d_elu_bn_backward");
+}
+
+// ---- batch norm over several ranks' rows: the two ops above cut at the statistics (include/sph3d.h) -------------------------
+static int norm_apply_blocks(long long total4)
+{
+    long long blocks = (total4 + 255) / 256;
+    return (int)(blocks > 4096 ? 4096 : blocks);
+}
+
+// partial == NULL: the statistics pass over y runs here, into the workspace; else partial[nblk][2][C] as in
+// sph3d_elu_bn_forward_partials (no workspace needed).  sums: double [2C + 1] = sum elu(y), sum elu(y)^2, R.
+extern "C" int sph3d_elu_bn_forward_sums(int R, int C, int nblk, const float* partial, const float* y, double* sums,
+                                         void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_forward_sums: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
+    SPH3D_REQUIRE(sums != nullptr, "elu_bn_forward_sums: sums is NULL");
+    hipStream_t st = as_stream(stream);
+    if (partial == nullptr) {
+        const size_t need = sph3d_elu_bn_workspace(R, C);
+        if (workspace == nullptr || workspace_bytes < need) {
+            set_error("elu_bn_forward_sums: workspace %zu B < required %zu B", workspace_bytes, need);
+            return SPH3D_EWORKSPACE;
+        }
+        SPH3D_REQUIRE(y != nullptr, "elu_bn_forward_sums: y is NULL");
+        nblk = norm_blocks(R);
+        hipLaunchKernelGGL(norm_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, R, C, y, nullptr, nullptr, nullptr, (float*)workspace);
+        partial = (const float*)workspace;
+    } else {
+        SPH3D_REQUIRE(nblk > 0, "elu_bn_forward_sums: nblk=%d partial row blocks", nblk);
+    }
+    hipLaunchKernelGGL(norm_fwd_sums, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, R, C, nblk, partial, sums);
+    return check_launch("sph3d_elu_bn_forward_sums");
+}
+
+// sums: the [2C + 1] buffer after the ranks' buffers were added up.  count [1] receives the global row count (a double on the
+// device: sph3d_elu_bn_backward_apply reads it there).
+extern "C" int sph3d_elu_bn_forward_apply(int R, int C, const double* sums, const float* y, const float* gamma, const float* beta,
+                                          float* running_mean, float* running_var, float momentum, float eps,
+                                          float* out, float* save_mean, float* save_rstd, double* count, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_forward_apply: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
+    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "elu_bn_forward_apply: sums / count is NULL");
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(norm_fwd_stats_from_sums, dim3((C + 255) / 256), dim3(256), 0, st, C, sums, eps, momentum, save_mean, save_rstd,
+                       running_mean, running_var, count);
+    const long long total4 = (long long)R * C / 4;
+    hipLaunchKernelGGL(norm_apply_kernel<false>, dim3((unsigned)norm_apply_blocks(total4)), dim3(256), 0, st, total4, C, y, nullptr,
+                       save_mean, save_rstd, gamma, beta, nullptr, out);
+    return check_launch("sph3d_elu_bn_forward_apply");
+}
+
+// dgamma / dbeta [C]: this rank's sums (fp32, as sph3d_elu_bn_backward writes them); sums: double [2C] = sum dout, sum dout*zhat.
+extern "C" int sph3d_elu_bn_backward_sums(int R, int C, const float* y, const float* dout, const float* save_mean,
+                                          const float* save_rstd, float* dgamma, float* dbeta, double* sums,
+                                          void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_backward_sums: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
+    SPH3D_REQUIRE(sums != nullptr, "elu_bn_backward_sums: sums is NULL");
+    const size_t need = sph3d_elu_bn_workspace(R, C);
+    if (workspace == nullptr || workspace_bytes < need) {
+        set_error("elu_bn_backward_sums: workspace %zu B < required %zu B", workspace_bytes, need);
+        return SPH3D_EWORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    float* partial = (float*)workspace;
+    const int nblk = norm_blocks(R);
+    hipLaunchKernelGGL(norm_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, R, C, y, dout, save_mean, save_rstd, partial);
+    hipLaunchKernelGGL(norm_bwd_sums, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, C, nblk, partial, dgamma, dbeta, sums);
+    return check_launch("sph3d_elu_bn_backward_sums");
+}
+
+// sums: the [2C] buffer after the ranks' buffers were added up; count: what sph3d_elu_bn_forward_apply wrote.
+extern "C" int sph3d_elu_bn_backward_apply(int R, int C, const double* sums, const double* count, const float* y, const float* dout,
+                                           const float* gamma, const float* save_mean, const float* save_rstd, float* dy,
+                                           void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_backward_apply: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
+    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "elu_bn_backward_apply: sums / count is NULL");
+    const size_t need = sph3d_elu_bn_workspace(R, C);
+    if (workspace == nullptr || workspace_bytes < need) {
+        set_error("elu_bn_backward_apply: workspace %zu B < required %zu B", workspace_bytes, need);
+        return SPH3D_EWORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    float* coef = (float*)workspace + (size_t)norm_blocks(R) * 2 * C;
+    hipLaunchKernelGGL(norm_bwd_coef_from_sums, dim3((C + 255) / 256), dim3(256), 0, st, C, sums, count, coef);
+    const long long total4 = (long long)R * C / 4;
+    hipLaunchKernelGGL(norm_apply_kernel<true>, dim3((unsigned)norm_apply_blocks(total4)), dim3(256), 0, st, total4, C, y, dout,
+                       save_mean, save_rstd, gamma, nullptr, coef, dy);
+    return check_launch("sph3d_elu_bn_backward_apply");
 }

@@ -102,6 +102,21 @@ def shard_range(total, rank, world):
     return begin, begin + base + (1 if rank < rem else 0)
 
 
+STAT_STATS = {"stat_allreduce_calls": 0}
+
+
+def stat_all_reduce(buf):
+    """The reducer of tf_norm.set_sync / tf_norm.sync: `buf` (a rank's float64 batch-norm sums) is replaced in place by its sum
+    over the ranks — one dist.all_reduce on the default group, the identity with one replica (unless SPH3D_FORCE_COLLECTIVES
+    issues it anyway).  With RCCL the call is synchronous in the stream sense only: the communication stream is ordered after
+    the current stream's work so far, the current stream after the collective, and the host goes on.  It shares the group's
+    stream with the gradient buckets, so during the backward pass it queues behind the buckets already started."""
+    STAT_STATS["stat_allreduce_calls"] += 1
+    if dist.is_initialized() and (dist.get_world_size() > 1 or FORCE_COLLECTIVES):
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    return buf
+
+
 class FlatGradAllReduce:
     """All parameters and all gradients live in two flat fp32 buffers (the nn.Parameters are views), the optimiser
     update is one elementwise kernel over ``flat_param`` (pass ``[self.flat_param]`` to the optimiser), and the

@@ -21,13 +21,14 @@ No step reads from the device: the counters live there (csrc/train.hip: sph3d_tr
 copy brings the confusion matrix, the counters, the loss sum and the optimiser's count of non-finite gradients to the host.
 """
 import collections
+import contextlib
 import os
 import re
 
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, tf_norm
 from . import dist as hdist
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -266,17 +267,21 @@ class Trainer:
     constructor runs ONE forward on it in inference mode without gradients, which creates the variables in their usual order
     and leaves the moving statistics untouched, then moves the parameters into the flat buffers.  No update, no step counted.
     seed: the feed's seed, with global_step the `sample_key` of every plan.  grad_scale: what the optimiser multiplies the summed
-    gradient by (1 / world size for a loss that is a mean over the global batch)."""
+    gradient by (1 / world size for a loss that is a mean over the global batch).  sync_bn: train_step runs its forward and
+    backward pass under tf_norm.sync(hdist.stat_all_reduce) — batch-norm statistics over the global batch; every
+    rank must then run the same layer sequence with at least one row per layer (the ranks' row counts may differ: the count
+    travels in the collective's buffer).  Evaluation is inference mode and issues no collective."""
 
     def __init__(self, model, loss_fn, optimizer_factory, schedule, num_cls, line=s3dis_line, prime=None, seed=0, log_every=50,
-                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print):
+                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False):
         if prime is None:
             raise ValueError("Trainer: `prime` (one batch of the training shapes) is needed to create the variables")
         self.model, self.loss_fn, self.schedule, self.line = model, loss_fn, schedule, line
         self.num_cls, self.seed, self.log_every, self.max_to_keep = int(num_cls), int(seed), int(log_every), int(max_to_keep)
         self.class_names = list(class_names) if class_names is not None else ["class %d" % c for c in range(self.num_cls)]
         self.log = log
-        self.global_step, self.epoch = 0, -1            # updates done; the last finished epoch
+        self.sync_bn = bool(sync_bn)
+        self.global_step, self.epoch = 0, -1           # updates done; the last finished epoch
         self.rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
         batch = self.line(tuple(prime))
         with torch.no_grad():
@@ -316,8 +321,11 @@ class Trainer:
 
     def train_step(self, item, feed=None):
         """plan / forward, loss, backward, all-reduce, update, metrics; nothing is read from the device"""
-        batch, pred, loss, ready = self._forward(item, True)
-        self.flat.backward(loss)
+        # sync_bn: every training-mode batch norm takes its statistics over all ranks' rows, one small all-reduce per layer and
+        # direction (every rank runs the same layers, each with at least one row; the row counts may differ)
+        with (tf_norm.sync(hdist.stat_all_reduce) if self.sync_bn else contextlib.nullcontext()):
+            batch, pred, loss, ready = self._forward(item, True)
+            self.flat.backward(loss)
         self.flat.all_reduce()
         self.opt.lr = self.schedule(self.global_step)
         self.opt.step()

@@ -623,6 +623,42 @@ def _elu_batch_normalization(data, is_training, name):
     return tf_norm.elu_batch_norm(data, gamma, beta, moving_mean, moving_var, training)
 
 
+class _SyncBatchNormFn(torch.autograd.Function):
+    """training-mode batch norm of flat[R, C] with statistics over all ranks' rows: float64 sums of this rank's rows, summed
+    over the ranks by `reducer` (tf_norm's reducer contract: one call per forward pass with [sum x, sum x^2, R], one per backward
+    pass with [sum dout, sum dout * xhat]); the moving statistics take the biased global variance.  dgamma / dbeta are this
+    rank's sums: the gradient all-reduce adds the ranks'."""
+
+    @staticmethod
+    def forward(ctx, flat, gamma, beta, moving_mean, moving_var, reducer):
+        C = flat.shape[1]
+        x = flat.double()
+        buf = torch.cat((x.sum(0), (x * x).sum(0), x.new_full((1,), float(flat.shape[0]))))
+        reducer(buf)
+        count = buf[2 * C:].clone()
+        mean = buf[:C] / count
+        var = (buf[C:2 * C] / count - mean * mean).clamp_min_(0.0)
+        rstd = torch.rsqrt(var + 1e-3)
+        moving_mean.mul_(0.99).add_(mean.to(moving_mean.dtype), alpha=1.0 - 0.99)
+        moving_var.mul_(0.99).add_(var.to(moving_var.dtype), alpha=1.0 - 0.99)
+        ctx.save_for_backward(flat, gamma, mean, rstd, count)
+        ctx.reducer = reducer
+        return ((x - mean) * rstd * gamma.double() + beta.double()).to(flat.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        flat, gamma, mean, rstd, count = ctx.saved_tensors
+        g = dout.double()
+        xhat = (flat.double() - mean) * rstd
+        C = gamma.shape[0]
+        dbeta, dgamma = g.sum(0), (g * xhat).sum(0)
+        buf = torch.cat((dbeta, dgamma))
+        ctx.reducer(buf)
+        dbeta, dgamma = dbeta.to(gamma.dtype), dgamma.to(gamma.dtype)
+        dx = gamma.double() * rstd * (g - buf[:C] / count - xhat * (buf[C:] / count))
+        return dx.to(flat.dtype), dgamma, dbeta, None, None, None
+
+
 def batch_normalization(data, is_training, name, reuse=None):
     """tf.layers.batch_normalization(momentum=0.99, epsilon=1e-3 [TF default], axis=-1) with the
     l2 regularisers on beta/gamma (utils/sph3gcn_util.py:328-332).  Statistics over all but the last axis."""
@@ -631,7 +667,10 @@ def batch_normalization(data, is_training, name, reuse=None):
     gamma, beta, moving_mean, moving_var = _bn_variables(store, name, C)
     training = True if is_training is None else bool(is_training)
     flat = data.reshape(-1, C)
-    if training:
+    if training and tf_norm.sync_reducer() is not None:
+        # statistics over all ranks' rows (tf_norm.set_sync): the same statement cut at its sums
+        out = _SyncBatchNormFn.apply(flat, gamma, beta, moving_mean, moving_var, tf_norm.sync_reducer())
+    elif training:
         # batch statistics for the output; the moving statistics take the BIASED batch variance, as the non-fused
         # tf.layers path (tf.nn.moments) does — F.batch_norm would store the Bessel-corrected one
         out = F.batch_norm(flat, None, None, gamma, beta, training=True, momentum=0.0, eps=1e-3)

@@ -4,7 +4,11 @@ epsilon=1e-3); stock TF ops in the reference, SURVEY §8f item 3 here).
 
 ``elu_batch_norm(y, gamma, beta, moving_mean, moving_var, training)`` == batch_norm(elu(y)) over all but the last axis,
 as ONE custom op (``sph3d::elu_bn``) whose backward needs only y.
+
+``set_sync(reducer)`` / ``with sync(reducer):`` switch every training-mode batch norm of the layer functions to statistics over
+all ranks' rows: the ops are cut at the statistics, and ``reducer`` sums the cut's float64 buffer over the ranks.
 """
+import contextlib
 from typing import Optional, Tuple
 
 import torch
@@ -17,6 +21,36 @@ EPSILON = 1e-3        # TF default epsilon
 
 def supported(C):
     return C % 4 == 0 and C <= 1024
+
+
+# ---- batch statistics over all ranks' rows -----------------------------------------------------------------------------------
+# A reducer is a callable reducer(buf): it replaces the 1-D float64 tensor `buf` IN PLACE by its sum over the ranks, orders the
+# CURRENT stream after the result and does not block the host (harness/dist.py: stat_all_reduce).  While one is set, every
+# training-mode batch norm calls it exactly once per forward pass, with [sum x, sum x^2, rows] = [2C + 1] values, and once per
+# backward pass, with [sum dout, sum dout * xhat] = [2C]; the backward pass uses the reducer that was set in its forward pass.
+# Inference mode never calls it.  Every rank must run the same sequence of layers, each with at least one row; the ranks' row
+# counts may differ (the count travels in the buffer).
+_sync = None
+
+
+def set_sync(reducer):
+    """reducer: a callable as described above, or None (each rank's own rows: the default) -> the previous value"""
+    global _sync
+    prev, _sync = _sync, reducer
+    return prev
+
+
+def sync_reducer():
+    return _sync
+
+
+@contextlib.contextmanager
+def sync(reducer):
+    prev = set_sync(reducer)
+    try:
+        yield reducer
+    finally:
+        set_sync(prev)
 
 
 def _fwd_impl(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, moving_mean: torch.Tensor,
@@ -69,6 +103,130 @@ def _(y, dout, gamma, save_mean, save_rstd, training):
     return torch.empty_like(y), torch.empty_like(gamma), torch.empty_like(gamma)
 
 
+# ---- the two ops cut at the statistics (csrc/norm.hip: sph3d_elu_bn_{forward,backward}_{sums,apply}) ------------------------------
+def elu_bn_forward_sums(y: torch.Tensor, partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> float64 [2C + 1]: per-channel sum elu(y), sum elu(y)^2 over this rank's rows, then the row count.  partial [nblk, 2, C]:
+    the statistics' partial sums where a producer of y already wrote them (the GEMM's epilogue, the one-kernel separable layer)"""
+    _lib.require_device(y)
+    y = _lib.f32(y)
+    C = y.shape[-1]
+    R = y.numel() // C
+    sums = torch.empty((2 * C + 1,), dtype=torch.float64, device=y.device)
+    l = _lib.lib()
+    if partial is None:
+        wsb = l.sph3d_elu_bn_workspace(R, C)
+        ws = _lib.scratch(wsb, y.device)
+        _lib.check(l.sph3d_elu_bn_forward_sums(R, C, 0, None, _lib.ptr(y), _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    else:
+        _lib.require_device(partial)
+        partial = _lib.f32(partial)
+        if partial.dim() != 3 or partial.shape[1] != 2 or partial.shape[2] != C or partial.shape[0] < 1:
+            raise ValueError("elu_bn_forward_sums: partial should be [nblk >= 1, 2, %d]" % C)
+        _lib.check(l.sph3d_elu_bn_forward_sums(R, C, partial.shape[0], _lib.ptr(partial), _lib.ptr(y), _lib.ptr(sums), None, 0,
+                                               _lib.stream_ptr()))
+    return sums
+
+
+def elu_bn_forward_apply(y: torch.Tensor, sums: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, moving_mean: torch.Tensor,
+                         moving_var: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """sums: the [2C + 1] buffer summed over the ranks -> out, save_mean, save_rstd, count (float64 [1]: the global row count,
+    kept on the device for elu_bn_backward_apply); updates the moving statistics"""
+    _lib.require_device(y, sums, gamma, beta, moving_mean, moving_var)
+    y = _lib.f32(y)
+    C = y.shape[-1]
+    R = y.numel() // C
+    if sums.dtype != torch.float64 or sums.numel() != 2 * C + 1 or not sums.is_contiguous():
+        raise ValueError("elu_bn_forward_apply: sums should be a contiguous float64 [%d]" % (2 * C + 1))
+    out = torch.empty_like(y)
+    save_mean = torch.empty((C,), dtype=torch.float32, device=y.device)
+    save_rstd = torch.empty((C,), dtype=torch.float32, device=y.device)
+    count = torch.empty((1,), dtype=torch.float64, device=y.device)
+    _lib.check(_lib.lib().sph3d_elu_bn_forward_apply(R, C, _lib.ptr(sums), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta),
+                                                      _lib.ptr(moving_mean), _lib.ptr(moving_var), 1.0 - MOMENTUM, EPSILON,
+                                                      _lib.ptr(out), _lib.ptr(save_mean), _lib.ptr(save_rstd), _lib.ptr(count),
+                                                      _lib.stream_ptr()))
+    return out, save_mean, save_rstd, count
+
+
+def elu_bn_backward_sums(y: torch.Tensor, dout: torch.Tensor, save_mean: torch.Tensor,
+                         save_rstd: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> dgamma, dbeta (this rank's sums, fp32: the gradient all-reduce adds the ranks') and float64 [2C]: per-channel
+    sum dout, sum dout * zhat over this rank's rows"""
+    _lib.require_device(y, dout, save_mean, save_rstd)
+    y, dout = _lib.f32(y), _lib.f32(dout)
+    C = y.shape[-1]
+    R = y.numel() // C
+    dgamma = torch.empty((C,), dtype=torch.float32, device=y.device)
+    dbeta = torch.empty((C,), dtype=torch.float32, device=y.device)
+    sums = torch.empty((2 * C,), dtype=torch.float64, device=y.device)
+    l = _lib.lib()
+    wsb = l.sph3d_elu_bn_workspace(R, C)
+    ws = _lib.scratch(wsb, y.device)
+    _lib.check(l.sph3d_elu_bn_backward_sums(R, C, _lib.ptr(y), _lib.ptr(dout), _lib.ptr(save_mean), _lib.ptr(save_rstd),
+                                            _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    return dgamma, dbeta, sums
+
+
+def elu_bn_backward_apply(y: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, save_mean: torch.Tensor,
+                          save_rstd: torch.Tensor, sums: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    """sums: the [2C] buffer summed over the ranks; count: elu_bn_forward_apply's -> dy over this rank's rows"""
+    _lib.require_device(y, dout, gamma, save_mean, save_rstd, sums, count)
+    y, dout = _lib.f32(y), _lib.f32(dout)
+    C = y.shape[-1]
+    R = y.numel() // C
+    if sums.dtype != torch.float64 or sums.numel() != 2 * C or not sums.is_contiguous():
+        raise ValueError("elu_bn_backward_apply: sums should be a contiguous float64 [%d]" % (2 * C))
+    if count.dtype != torch.float64 or count.numel() != 1:
+        raise ValueError("elu_bn_backward_apply: count should be a float64 [1]")
+    dy = torch.empty_like(y)
+    l = _lib.lib()
+    wsb = l.sph3d_elu_bn_workspace(R, C)
+    ws = _lib.scratch(wsb, y.device)
+    _lib.check(l.sph3d_elu_bn_backward_apply(R, C, _lib.ptr(sums), _lib.ptr(count), _lib.ptr(y), _lib.ptr(dout), _lib.ptr(gamma),
+                                             _lib.ptr(save_mean), _lib.ptr(save_rstd), _lib.ptr(dy), _lib.ptr(ws), wsb,
+                                             _lib.stream_ptr()))
+    return dy
+
+
+_fwd_sums_op = torch.library.custom_op("sph3d::elu_bn_forward_sums", mutates_args=())(elu_bn_forward_sums)
+_fwd_apply_op = torch.library.custom_op("sph3d::elu_bn_forward_apply", mutates_args=("moving_mean", "moving_var"))(elu_bn_forward_apply)
+_bwd_sums_op = torch.library.custom_op("sph3d::elu_bn_backward_sums", mutates_args=())(elu_bn_backward_sums)
+_bwd_apply_op = torch.library.custom_op("sph3d::elu_bn_backward_apply", mutates_args=())(elu_bn_backward_apply)
+
+
+@_fwd_sums_op.register_fake
+def _(y, partial=None):
+    return y.new_empty((2 * y.shape[-1] + 1,), dtype=torch.float64)
+
+
+@_fwd_apply_op.register_fake
+def _(y, sums, gamma, beta, moving_mean, moving_var):
+    return torch.empty_like(y), torch.empty_like(gamma), torch.empty_like(gamma), sums.new_empty((1,))
+
+
+@_bwd_sums_op.register_fake
+def _(y, dout, save_mean, save_rstd):
+    return torch.empty_like(save_mean), torch.empty_like(save_mean), y.new_empty((2 * y.shape[-1],), dtype=torch.float64)
+
+
+@_bwd_apply_op.register_fake
+def _(y, dout, gamma, save_mean, save_rstd, sums, count):
+    return torch.empty_like(y)
+
+
+def _sync_fwd(reducer, y, partial, gamma, beta, moving_mean, moving_var):
+    """training-mode forward over all ranks' rows: sums -> reducer -> apply"""
+    sums = elu_bn_forward_sums(y, partial)
+    reducer(sums)
+    return elu_bn_forward_apply(y, sums, gamma, beta, moving_mean, moving_var)
+
+
+def _sync_bwd(reducer, y, dout, gamma, save_mean, save_rstd, count):
+    dgamma, dbeta, sums = elu_bn_backward_sums(y, dout, save_mean, save_rstd)
+    reducer(sums)
+    return elu_bn_backward_apply(y, dout, gamma, save_mean, save_rstd, sums, count), dgamma, dbeta
+
+
 # (sph3d::elu_bn updates the moving statistics in place, so the dispatcher accepts no autograd formula for it: the
 # gradient wiring of the fused tail is _EluBnFn below, over the functional sph3d::elu_bn_grad.)
 
@@ -76,15 +234,23 @@ def _(y, dout, gamma, save_mean, save_rstd, training):
 class _EluBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, moving_mean, moving_var, training):
-        out, save_mean, save_rstd = _fwd_impl(y, gamma, beta, moving_mean, moving_var, training)
-        ctx.save_for_backward(y, gamma, save_mean, save_rstd)
+        ctx.reducer = _sync if training else None
+        count = None
+        if ctx.reducer is not None:
+            out, save_mean, save_rstd, count = _sync_fwd(ctx.reducer, y, None, gamma, beta, moving_mean, moving_var)
+        else:
+            out, save_mean, save_rstd = _fwd_impl(y, gamma, beta, moving_mean, moving_var, training)
+        ctx.save_for_backward(y, gamma, save_mean, save_rstd, count)
         ctx.training = training
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        y, gamma, save_mean, save_rstd = ctx.saved_tensors
-        dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, ctx.training)
+        y, gamma, save_mean, save_rstd, count = ctx.saved_tensors
+        if ctx.reducer is not None:
+            dy, dgamma, dbeta = _sync_bwd(ctx.reducer, y, dout, gamma, save_mean, save_rstd, count)
+        else:
+            dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, ctx.training)
         return dy, dgamma, dbeta, None, None, None
 
 
@@ -155,16 +321,24 @@ class _GemmEluBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, gamma, beta, moving_mean, moving_var):
         y, partial = _gemm_bnstats_impl(x, w, bias)
-        out, save_mean, save_rstd = _elu_bn_partials_impl(y, partial, gamma, beta, moving_mean, moving_var)
-        ctx.save_for_backward(x, w, y, gamma, save_mean, save_rstd)
+        ctx.reducer = _sync
+        count = None
+        if ctx.reducer is not None:
+            out, save_mean, save_rstd, count = _sync_fwd(ctx.reducer, y, partial, gamma, beta, moving_mean, moving_var)
+        else:
+            out, save_mean, save_rstd = _elu_bn_partials_impl(y, partial, gamma, beta, moving_mean, moving_var)
+        ctx.save_for_backward(x, w, y, gamma, save_mean, save_rstd, count)
         ctx.has_bias = bias is not None
         return out
 
     @staticmethod
     def backward(ctx, dout):
         from . import tf_gemm
-        x, w, y, gamma, save_mean, save_rstd = ctx.saved_tensors
-        dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, True)
+        x, w, y, gamma, save_mean, save_rstd, count = ctx.saved_tensors
+        if ctx.reducer is not None:
+            dy, dgamma, dbeta = _sync_bwd(ctx.reducer, y, dout, gamma, save_mean, save_rstd, count)
+        else:
+            dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, True)
         dx = tf_gemm._pointwise_gemm_impl(dy, w, True) if ctx.needs_input_grad[0] else None
         dw = tf_gemm._pointwise_gemm_tn_impl(x, dy) if ctx.needs_input_grad[1] else None
         db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
