@@ -53,39 +53,58 @@ def sync(reducer):
         set_sync(prev)
 
 
+def _per_channel(op, C, names, *operands):
+    """every per-channel operand of a launch: on the device, float32, contiguous, exactly [C].  The kernels take them as bare
+    addresses and read C floats (write C floats into the moving statistics, which can therefore not be converted into a copy):
+    anything else is a ValueError BEFORE the launch, so nothing is read out of bounds or as another type on the device."""
+    for t in operands:
+        # (a 1-D tensor of C > 1 elements is contiguous exactly when its stride is 1; the cheapest form: 34 launches a step come here)
+        if t.stride() != _UNIT or t.numel() != C or t.dtype != _F32 or not t.is_cuda:
+            _lib.require_device(*operands)
+            for name, t in zip(names, operands):
+                if t.dtype != _F32 or t.dim() != 1 or t.numel() != C or not t.is_contiguous():
+                    raise ValueError("%s: %s should be a contiguous float32 [%d] (got %s %s, strides %s)"
+                                     % (op, name, C, str(t.dtype).replace("torch.", ""), list(t.shape), list(t.stride())))
+
+
+_F32, _UNIT = torch.float32, (1,)
+_FWD_NAMES = ("gamma", "beta", "moving_mean", "moving_var")
+_BWD_NAMES = ("gamma", "save_mean", "save_rstd")
+
+
 def _fwd_impl(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, moving_mean: torch.Tensor,
               moving_var: torch.Tensor, training: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    _lib.require_device(y, gamma, beta, moving_mean, moving_var)
+    _lib.require_device(y)
     y = _lib.f32(y)
     C = y.shape[-1]
     R = y.numel() // C
+    _per_channel("elu_bn", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
-    save_mean = torch.empty((C,), dtype=torch.float32, device=y.device)
-    save_rstd = torch.empty((C,), dtype=torch.float32, device=y.device)
+    save_mean, save_rstd = torch.empty_like(gamma), torch.empty_like(gamma)      # (gamma was just checked: float32 [C] on the device)
     l = _lib.lib()
     wsb = l.sph3d_elu_bn_workspace(R, C)
     ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_forward(R, C, _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(moving_mean),
-                                      _lib.ptr(moving_var), 1.0 - MOMENTUM, EPSILON, 1 if training else 0, _lib.ptr(out),
-                                      _lib.ptr(save_mean), _lib.ptr(save_rstd), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    _lib.check(l.sph3d_elu_bn_forward(R, C, y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), moving_mean.data_ptr(),
+                                      moving_var.data_ptr(), 1.0 - MOMENTUM, EPSILON, 1 if training else 0, out.data_ptr(),
+                                      save_mean.data_ptr(), save_rstd.data_ptr(), _lib.ptr(ws), wsb, _lib.stream_ptr()))
     return out, save_mean, save_rstd
 
 
 def _bwd_impl(y: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, save_mean: torch.Tensor,
               save_rstd: torch.Tensor, training: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    _lib.require_device(y, dout, gamma)
+    _lib.require_device(y, dout)
     y, dout = _lib.f32(y), _lib.f32(dout)
     C = y.shape[-1]
     R = y.numel() // C
+    _per_channel("elu_bn_grad", C, _BWD_NAMES, gamma, save_mean, save_rstd)
     dy = torch.empty_like(y)
-    dgamma = torch.empty((C,), dtype=torch.float32, device=y.device)
-    dbeta = torch.empty((C,), dtype=torch.float32, device=y.device)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
     l = _lib.lib()
     wsb = l.sph3d_elu_bn_workspace(R, C)
     ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_backward(R, C, _lib.ptr(y), _lib.ptr(dout), _lib.ptr(gamma), _lib.ptr(save_mean),
-                                       _lib.ptr(save_rstd), 1 if training else 0, _lib.ptr(dy), _lib.ptr(dgamma),
-                                       _lib.ptr(dbeta), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    _lib.check(l.sph3d_elu_bn_backward(R, C, y.data_ptr(), dout.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+                                       save_rstd.data_ptr(), 1 if training else 0, dy.data_ptr(), dgamma.data_ptr(),
+                                       dbeta.data_ptr(), _lib.ptr(ws), wsb, _lib.stream_ptr()))
     return dy, dgamma, dbeta
 
 
@@ -137,6 +156,7 @@ def elu_bn_forward_apply(y: torch.Tensor, sums: torch.Tensor, gamma: torch.Tenso
     R = y.numel() // C
     if sums.dtype != torch.float64 or sums.numel() != 2 * C + 1 or not sums.is_contiguous():
         raise ValueError("elu_bn_forward_apply: sums should be a contiguous float64 [%d]" % (2 * C + 1))
+    _per_channel("elu_bn_forward_apply", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
     save_mean = torch.empty((C,), dtype=torch.float32, device=y.device)
     save_rstd = torch.empty((C,), dtype=torch.float32, device=y.device)
@@ -156,6 +176,7 @@ def elu_bn_backward_sums(y: torch.Tensor, dout: torch.Tensor, save_mean: torch.T
     y, dout = _lib.f32(y), _lib.f32(dout)
     C = y.shape[-1]
     R = y.numel() // C
+    _per_channel("elu_bn_backward_sums", C, _BWD_NAMES[1:], save_mean, save_rstd)
     dgamma = torch.empty((C,), dtype=torch.float32, device=y.device)
     dbeta = torch.empty((C,), dtype=torch.float32, device=y.device)
     sums = torch.empty((2 * C,), dtype=torch.float64, device=y.device)
@@ -178,6 +199,7 @@ def elu_bn_backward_apply(y: torch.Tensor, dout: torch.Tensor, gamma: torch.Tens
         raise ValueError("elu_bn_backward_apply: sums should be a contiguous float64 [%d]" % (2 * C))
     if count.dtype != torch.float64 or count.numel() != 1:
         raise ValueError("elu_bn_backward_apply: count should be a float64 [1]")
+    _per_channel("elu_bn_backward_apply", C, _BWD_NAMES, gamma, save_mean, save_rstd)
     dy = torch.empty_like(y)
     l = _lib.lib()
     wsb = l.sph3d_elu_bn_workspace(R, C)
@@ -285,17 +307,17 @@ def _gemm_bnstats_impl(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Te
 def _elu_bn_partials_impl(y: torch.Tensor, partial: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
                           moving_mean: torch.Tensor, moving_var: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """training-mode elu_bn whose statistics come from `partial` instead of a pass over y"""
-    _lib.require_device(y, partial, gamma, beta, moving_mean, moving_var)
+    _lib.require_device(y, partial)
     y, partial = _lib.f32(y), _lib.f32(partial)
     C = y.shape[-1]
     R = y.numel() // C
+    _per_channel("elu_bn_partials", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
-    save_mean = torch.empty((C,), dtype=torch.float32, device=y.device)
-    save_rstd = torch.empty((C,), dtype=torch.float32, device=y.device)
-    _lib.check(_lib.lib().sph3d_elu_bn_forward_partials(R, C, partial.shape[0], _lib.ptr(partial), _lib.ptr(y), _lib.ptr(gamma),
-                                                         _lib.ptr(beta), _lib.ptr(moving_mean), _lib.ptr(moving_var),
-                                                         1.0 - MOMENTUM, EPSILON, _lib.ptr(out), _lib.ptr(save_mean),
-                                                         _lib.ptr(save_rstd), _lib.stream_ptr()))
+    save_mean, save_rstd = torch.empty_like(gamma), torch.empty_like(gamma)
+    _lib.check(_lib.lib().sph3d_elu_bn_forward_partials(R, C, partial.shape[0], partial.data_ptr(), y.data_ptr(), gamma.data_ptr(),
+                                                         beta.data_ptr(), moving_mean.data_ptr(), moving_var.data_ptr(),
+                                                         1.0 - MOMENTUM, EPSILON, out.data_ptr(), save_mean.data_ptr(),
+                                                         save_rstd.data_ptr(), _lib.stream_ptr()))
     return out, save_mean, save_rstd
 
 
