@@ -199,8 +199,9 @@ int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, int r, int K,
  * Cloud b's entries fill [offsets[b, 0], offsets[b, N*F]) of its slab [b*M*K, (b+1)*M*K), offsets[b, 0] = b*M*K; the rest of
  * the slab (the slots k >= nn_count of its rows) is not written, nor is active_bins behind its 1 + count words.  A bin id
  * outside [0, F-1] counts for the nearest bin, 0 or F-1, in the offsets and in active_bins.  The order of the entries inside
- * one segment is not defined.  tests/_tgraph_ref.py states all of this in numpy.
- * workspace: sph3d_graph_transpose_workspace() bytes of scratch (segment counters). */
+ * one segment is not defined — except in deterministic mode (sph3d_set_deterministic below), where every build form leaves them
+ * in the canonical order of sph3d_graph_canonical_order.  tests/_tgraph_ref.py states all of this in numpy.
+ * workspace: sph3d_graph_transpose_workspace() bytes of scratch (segment counters); deterministic mode adds B*M*K words. */
 size_t sph3d_graph_transpose_workspace(int B, int N, int M, int K, int F);
 int sph3d_graph_transpose(int B, int N, int M, int K, int F,
                           const int* nn_index, const int* nn_count,
@@ -241,6 +242,27 @@ int sph3d_graph_transpose_finish_ordered(int B, int N, int M, int K, int F,
  * `offsets` of the transposed graph with F bins), alternately descending and ascending.  order[B*N], a permutation per
  * cloud; results of the gradient are the same sums in a different order of the filter-gradient partials. */
 int sph3d_graph_balanced_order(int B, int N, int F, const int* offsets, int* order, sph3d_stream_t stream);
+/* Deterministic mode — process-wide, off by default; sph3d_set_deterministic returns the previous value (0 or 1).  While it is on,
+ * every gradient of this library is a pure function of its inputs: the same bits on every run (one device; nothing is claimed
+ * for what a collective adds between ranks).
+ *   - every build of a transposed graph (sph3d_graph_transpose, _finish[_ordered], the counted workspaces of
+ *     sph3d_build_sphere_graph and sph3d_gather_rows_count, the *_grad wrappers that build one internally) ends with the
+ *     canonical-order pass below, so the gradient gathers add a segment's terms in one fixed order;
+ *   - sph3d_graph_transpose_workspace() (and every workspace size that contains it) is B*M*K words larger: size workspaces
+ *     while the mode has the value they will be used with;
+ *   - the conv gradient runs no hub launches (float atomics), for any N; SPH3D_BWD_HUB_* are ignored;
+ *   - what can only run with float atomics refuses with SPH3D_EUNSUPPORTED: conv gradient shapes of the generic kernel
+ *     (sph3d_depthwise_conv3d_grad_t, _grad_t_cat, _grad) and sph3d_max_pool3d_grad (use sph3d_max_pool3d_grad_t).
+ * Transposed graphs built while the mode was off keep their arrival order: rebuild them after switching it on. */
+int sph3d_set_deterministic(int on);
+int sph3d_get_deterministic(void);
+/* Canonical order of a transposed graph's entries, in place: inside every segment (cloud, source, bin) ascending by row m, entries
+ * of equal m ascending by the factor's bit pattern read as an unsigned 32-bit integer.  Packed entries (ent_scale == NULL) are
+ * ordered by word & 0xffffff and the bits of 1 / (word >> 24), so a packed and an un-packed build of one graph list the same
+ * (m, factor) sequence.  N, M, K, F as the graph was built with; workspace: sph3d_graph_canonical_order_workspace() bytes. */
+size_t sph3d_graph_canonical_order_workspace(int B, int N, int M, int K, int F);
+int sph3d_graph_canonical_order(int B, int N, int M, int K, int F, const int* offsets, int* ent_key, float* ent_scale /* NULL: packed */,
+                                void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
 /* conv gradients from a prebuilt transposed graph: both gradients in one pass, no float atomics
  * (grad_input gathered in registers; grad_filter accumulated in per-lane registers by persistent workgroups
  * that sweep the clouds of their XCD, one partial table per workgroup written to `workspace` =
@@ -280,6 +302,7 @@ size_t sph3d_scatter_grad_workspace(int B, int N, int M, int K);
 int sph3d_max_pool3d(int B, int N, int M, int C, int K,
                      const int* nn_index, const int* nn_count, const float* input,
                      float* output, int* max_index, sph3d_stream_t stream);
+/* (the scatter form: float atomics, SPH3D_EUNSUPPORTED in deterministic mode) */
 int sph3d_max_pool3d_grad(int B, int N, int M, int C,
                           const int* max_index, const float* grad_output,
                           float* grad_input, sph3d_stream_t stream);

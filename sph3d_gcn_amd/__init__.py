@@ -12,6 +12,7 @@ Layout (only what the path needs):
 from . import _lib  # noqa: F401
 from . import tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm  # noqa: F401
 from . import sph3gcn_util  # noqa: F401
+from ._tgraph import set_deterministic, is_deterministic, deterministic  # noqa: F401
 
 __all__ = ["tf_nnquery", "tf_buildkernel", "tf_conv3d", "tf_pool3d", "tf_unpool3d", "tf_sample", "tf_gemm",
-           "sph3gcn_util"]
+           "sph3gcn_util", "set_deterministic", "is_deterministic", "deterministic"]

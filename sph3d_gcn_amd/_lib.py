@@ -44,6 +44,10 @@ SIGNATURES = {
     "sph3d_avg_pool3d": (_I, [_I] * 5 + [_P] * 5),
     "sph3d_avg_pool3d_grad": (_I, [_I] * 5 + [_P] * 4 + [_P, _S, _P]),
     "sph3d_graph_balanced_order": (_I, [_I, _I, _I, _P, _P, _P]),
+    "sph3d_set_deterministic": (_I, [_I]),
+    "sph3d_get_deterministic": (_I, []),
+    "sph3d_graph_canonical_order_workspace": (_S, [_I] * 5),
+    "sph3d_graph_canonical_order": (_I, [_I] * 5 + [_P] * 3 + [_P, _S, _P]),
     "sph3d_gather_nd": (_I, [_I, _I, ctypes.c_longlong, _I, _P, _P, _P, _P]),
     "sph3d_gather_rows_count": (_I, [_I] * 4 + [_P] * 5 + [_P, _S, _P]),
     "sph3d_graph_transpose_workspace": (_S, [_I] * 5),
@@ -205,15 +209,28 @@ class _Proxy:
     def __init__(self, cdll):
         self._cdll = cdll
         self._cache = {}
+        self._memos = []
 
     def __getattr__(self, name):
         # (reached once per symbol: the result is stored on the instance, so later look-ups never come here — 180 look-ups per
         # step at 2 us each otherwise)
         fn = getattr(self._cdll, name)     # AttributeError if not exported
+        if name == "sph3d_set_deterministic":
+            # the one call that changes what the memoised size functions below answer (the transposed graph's workspace grows in
+            # deterministic mode): their answers are dropped with every change of the value
+            def switch(on, _fn=fn, _memos=self._memos):
+                prev = _fn(on)
+                if (prev != 0) != (on != 0):
+                    for m in _memos:
+                        m.clear()
+                return prev
+            self.__dict__[name] = switch
+            return switch
         if any(k in name for k in _PURE) and name != "sph3d_pointwise_gemm_bnstats_blocks":
             # pure functions of their integer arguments (workspace sizes, shape predicates): a step asks ~75 of them, always
             # for the same shapes — answered from a dict instead of a foreign call each time
             memo = {}
+            self._memos.append(memo)
 
             def cached(*args, _fn=fn, _memo=memo):
                 r = _memo.get(args)

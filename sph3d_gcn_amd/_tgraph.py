@@ -7,6 +7,7 @@ to the tensors it was built from, so their storage (and therefore the data_ptr i
 recycled for a different graph while the entry is alive; in-place edits are caught by the version counter.
 """
 import collections
+import contextlib
 
 import torch
 
@@ -35,6 +36,31 @@ def clear():
     _orders.clear()
     _unique.clear()
     _generation[0] += 1
+
+
+# ---- deterministic mode (include/sph3d.h: sph3d_set_deterministic) ----
+def is_deterministic():
+    return bool(_lib.lib().sph3d_get_deterministic())
+
+
+def set_deterministic(flag):
+    """process-wide: every transposed graph built from now on is in canonical entry order, the conv gradient runs no hub
+    launches, and what can only run with float atomics raises.  A change of the value empties this cache, so a transpose built
+    in arrival order is never served while the mode is on -> the previous value"""
+    flag = bool(flag)
+    prev = bool(_lib.lib().sph3d_set_deterministic(1 if flag else 0))
+    if prev != flag:
+        clear()
+    return prev
+
+
+@contextlib.contextmanager
+def deterministic(flag=True):
+    prev = set_deterministic(flag)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
 
 
 # processing order of the source points of a graph (a permutation per cloud, spatially sorted): optional hint for

@@ -76,6 +76,9 @@ static inline int test_hook(const char* name, int unset)
     return e ? atoi(e) : unset;
 }
 
+// gemm.hip: deterministic mode (sph3d_set_deterministic) is on
+bool deterministic_on();
+
 // graph.hip: stream-ordered zero fill of `bytes` bytes at `p` (4-byte aligned, bytes % 4 == 0).  hipMemsetAsync's fill kernel
 // runs 256 workgroups whatever the size: 245 us for the 17 MB of level-0 segment counters (70 GB/s; rocprofv3 trace of round 5);
 // large fills go through a kernel that covers the chip (8 us for the same buffer), small ones stay with the runtime.

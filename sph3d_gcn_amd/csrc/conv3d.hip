@@ -973,7 +973,9 @@ static int launch_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int 
     const bool compact = active_bins != nullptr && V == 4 && MAXF > kCompactBins && F <= 63;
     const int* ab = compact ? active_bins : nullptr;
     // big clouds: hub sources are left out of the sweep and shared among the waves of the hub launch (see the kernel)
-    const bool hubs = V == 4 && N >= hub_min_n();
+    // (deterministic mode: never — the hub list is appended with an atomic and the hub launch adds its grad_input sums with float
+    // atomics; the sweep alone takes every source, its static partition and reduce_filter_partials sum in a fixed order)
+    const bool hubs = V == 4 && !deterministic_on() && N >= hub_min_n();
     int* hub_list = nullptr;
     int T = 0;
     if (hubs) {
@@ -1060,6 +1062,11 @@ extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, 
         return run_bwd_t_vec(L, B, N, M, F, C, r, offsets, ent_key, ent_scale, source_order, active_bins, input, filter, grad_output,
                              grad_input, grad_filter, workspace, workspace_bytes, st);
     // generic path (odd channel counts, other multipliers, F > 64): LDS float atomics, slow but general
+    if (deterministic_on()) {
+        set_error("DepthwiseConv3dGrad: deterministic mode is on and F=%d C=%d r=%d takes the generic kernel, which sums with float "
+                  "atomics (shapes with C*r %% 4 == 0, r in {1, 2} and F <= 33 or 65 run the fixed-order kernels)", F, C, r);
+        return SPH3D_EUNSUPPORTED;
+    }
     rc = check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
     if (rc) return rc;
     SPH3D_REQUIRE(r <= 256, "DepthwiseConv3dGrad: depth multiplier %d > 256 unsupported", r);

@@ -1083,6 +1083,15 @@ extern "C" int sph3d_pointwise_gemm_mode(int mode)
     return g_split_mode.load();
 }
 
+// deterministic mode (include/sph3d.h): read by graph.hip, conv3d.hip and pool3d.hip on every call
+static std::atomic<int> g_deterministic{0};
+namespace sph3d {
+bool deterministic_on() { return g_deterministic.load(std::memory_order_relaxed) != 0; }
+}  // namespace sph3d
+
+extern "C" int sph3d_set_deterministic(int on) { return g_deterministic.exchange(on != 0 ? 1 : 0); }
+extern "C" int sph3d_get_deterministic(void) { return g_deterministic.load(); }
+
 extern "C" int sph3d_pointwise_gemm_plan(int product, int R, int Cin, int Cout, int aligned, int mode, int exchange_ok, int* out)
 {
     SPH3D_REQUIRE(product >= kNN && product <= kTN && plan_args_ok(R, Cin, Cout), "pointwise_gemm_plan: bad product %d or dims R=%d Cin=%d Cout=%d",

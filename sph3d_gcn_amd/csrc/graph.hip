@@ -17,7 +17,8 @@
 //   ent_scale[B*M*K]   1/nn_count[m]  (or weight[b,m,k] when a weight array is given)
 // Built in three steps: segment count (integer atomics), per-cloud exclusive scan, fill (integer atomic
 // cursor).  The fill order within one list is not deterministic, so float sums may differ in the last bits
-// between runs — as with the reference's atomics, but without their cost.
+// between runs — as with the reference's atomics, but without their cost.  Deterministic mode
+// (sph3d_set_deterministic) adds a fourth step that sorts every list into its canonical order.
 #include "common.hpp"
 
 namespace sph3d {
@@ -314,6 +315,140 @@ __global__ __launch_bounds__(1024) void spatial_order_kernel(int N, int bpa, con
     for (int n = tid; n < N; n += 1024) order[(size_t)b * N + atomicAdd(&hist[key_of(n)], 1)] = n;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Canonical order of the entries (deterministic mode).  The fill pass above puts an edge where an integer
+// atomic's arrival order sent it, so the float sums of the gradient gathers change in the last bit from build to build.
+// This pass sorts every segment in place: ascending by row m, equal rows ascending by the factor's bit pattern as an
+// unsigned — the same sequence for packed and separate entries.  One wave per source (b, n), walking the source's contiguous
+// range [off[n*F], off[(n+1)*F]) in windows of 64 entries that start on a segment boundary:
+//   segments that end inside the window   every lane holds one entry and counts the smaller keys of its own segment through
+//                                         wave shuffles, then stores its entry once at segment start + rank
+//   a segment longer than 64 entries      rank-sorted strip by strip (64 entries in registers against all of the segment)
+//                                         into the staging words, then copied back: no limit on the length, O(s^2 / 64)
+// Entries that tie on both fields are identical; the tie is broken by position so that every rank is taken once.
+// No atomics of any kind.
+// ---------------------------------------------------------------------------------------------------------------
+template <bool PACKED>
+__device__ __forceinline__ unsigned long long canon_key(unsigned word, unsigned scale_bits)
+{
+    if (PACKED) return ((unsigned long long)(word & kTgKeyMask) << 32) | (unsigned)__float_as_int(tg_packed_scale((int)word));
+    return ((unsigned long long)word << 32) | scale_bits;
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void tg_canonical_order(int B, int N, int F, const int* __restrict__ offsets, unsigned* entKey,
+                                                          unsigned* entScale, unsigned* stageKey, unsigned* stageScale)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const long long nsrc = (long long)B * N;
+    const long long wstride = (long long)gridDim.x * 4;
+    for (long long s = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6); s < nsrc; s += wstride) {
+        const int b = (int)(s / N);
+        const int n = (int)(s - (long long)b * N);
+        const int* __restrict__ ob = offsets + (size_t)b * ((size_t)N * F + 1) + (size_t)n * F;     // the F + 1 bounds of the source's segments
+        const int r0 = uniform(ob[0]), r1 = uniform(ob[F]);
+        int pos = r0;                                   // always the first entry of a segment
+        while (r1 - pos > 1) {
+            const int p = pos + lane;
+            const bool valid = p < r1;
+            int slo = pos, shi = pos;
+            unsigned kw = 0u, sw = 0u;
+            if (valid) {
+                int lo = 0, hi = F;                     // ob[lo] <= p < ob[hi]: the segment that holds p (empty ones are passed over)
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ob[mid] <= p) lo = mid; else hi = mid;
+                }
+                slo = ob[lo];
+                shi = ob[hi];
+                kw = entKey[p];
+                if (!PACKED) sw = entScale[p];
+            }
+            const bool complete = valid && shi <= pos + 64;         // the lane's whole segment lies in this window
+            const unsigned long long rest = __ballot(valid && !complete);
+            if (rest & 1ull) {
+                // the segment at `pos` is longer than a window: strips of 64 against the whole segment, through the staging words
+                const int s0 = pos, s1 = uniform(__shfl(shi, 0));
+                for (int t = s0; t < s1; t += 64) {
+                    const int e = t + lane;
+                    unsigned ek = 0u, es = 0u;
+                    if (e < s1) {
+                        ek = entKey[e];
+                        if (!PACKED) es = entScale[e];
+                    }
+                    const unsigned long long mine = canon_key<PACKED>(ek, es);
+                    int rank = 0;
+                    for (int u = s0; u < s1; u += 64) {
+                        const int q = u + lane;
+                        unsigned qk = 0u, qs = 0u;
+                        if (q < s1) {
+                            qk = entKey[q];
+                            if (!PACKED) qs = entScale[q];
+                        }
+                        const unsigned long long other = canon_key<PACKED>(qk, qs);
+                        const int ohi = (int)(unsigned)(other >> 32), olo = (int)(unsigned)other;
+                        const int cnt = (s1 - u) < 64 ? (s1 - u) : 64;
+                        for (int j = 0; j < cnt; j++) {
+                            const unsigned long long o = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(ohi, j) << 32) |
+                                                         (unsigned)__builtin_amdgcn_readlane(olo, j);
+                            rank += (o < mine || (o == mine && u + j < e)) ? 1 : 0;
+                        }
+                    }
+                    if (e < s1) {
+                        stageKey[s0 + rank] = ek;
+                        if (!PACKED) stageScale[s0 + rank] = es;
+                    }
+                }
+                __threadfence();                        // the staged words were written by other lanes of this wave
+                for (int e = s0 + lane; e < s1; e += 64) {
+                    entKey[e] = stageKey[e];
+                    if (!PACKED) entScale[e] = stageScale[e];
+                }
+                pos = s1;
+                continue;
+            }
+            // the segments that end inside the window: a segment's entries sit in consecutive lanes from `first`
+            const unsigned long long mine = canon_key<PACKED>(kw, sw);
+            const int khi = (int)(unsigned)(mine >> 32), klo = (int)(unsigned)mine;
+            const int len = complete ? shi - slo : 0;
+            const int first = slo - pos;
+            int maxlen = len;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const int v = __shfl_xor(maxlen, o);
+                maxlen = v > maxlen ? v : maxlen;
+            }
+            if (maxlen > 1) {
+                int rank = 0;
+                for (int j = 0; j < maxlen; j++) {
+                    const int src = (first + j) & 63;
+                    const unsigned long long o = ((unsigned long long)(unsigned)__shfl(khi, src) << 32) | (unsigned)__shfl(klo, src);
+                    if (j < len) rank += (o < mine || (o == mine && first + j < lane)) ? 1 : 0;
+                }
+                if (len > 1) {
+                    entKey[slo + rank] = kw;
+                    if (!PACKED) entScale[slo + rank] = sw;
+                }
+            }
+            pos = rest ? pos + (int)__builtin_ctzll(rest) : pos + 64;
+        }
+    }
+}
+
+// the pass on entries that a fill has written; `stage`: B*M*K words (packed entries), twice that (separate key / scale arrays)
+static void launch_canonical_order(int B, int N, int F, const int* offsets, int* ent_key, float* ent_scale, int* stage, size_t entries,
+                                   hipStream_t st)
+{
+    long long blocks = ((long long)B * N + 3) / 4;
+    if (blocks > 16384) blocks = 16384;
+    if (ent_scale == nullptr)
+        hipLaunchKernelGGL(tg_canonical_order<true>, dim3((unsigned)blocks), dim3(256), 0, st, B, N, F, offsets, (unsigned*)ent_key,
+                           (unsigned*)nullptr, (unsigned*)stage, (unsigned*)nullptr);
+    else
+        hipLaunchKernelGGL(tg_canonical_order<false>, dim3((unsigned)blocks), dim3(256), 0, st, B, N, F, offsets, (unsigned*)ent_key,
+                           (unsigned*)ent_scale, (unsigned*)stage, (unsigned*)stage + entries);
+}
+
 }  // namespace sph3d
 
 using namespace sph3d;
@@ -399,10 +534,35 @@ __global__ __launch_bounds__(1024) void tg_fill_order(int nob, int B, int N, int
     tg_fill_rows(nob, (int)gridDim.x - nob, B, N, M, K, F, nnIndex, nnCount, binIndex, weight, offsets, slotPos, entKey, entScale);
 }
 
-// bytes of scratch the build itself needs (common.hpp: tg_ws)
+// bytes of scratch the build itself needs (common.hpp: tg_ws).  Deterministic mode: B*M*K words more behind it — the canonical-order
+// pass stages a long segment's rows in the (then dead) slot positions and, for separate entry arrays, its factors in these
 extern "C" size_t sph3d_graph_transpose_workspace(int B, int N, int M, int K, int F)
 {
-    return sizeof(int) * tg_ws(nullptr, B, N, M, K, F).total_words;
+    const size_t words = tg_ws(nullptr, B, N, M, K, F).total_words;
+    return sizeof(int) * (deterministic_on() ? words + (size_t)B * M * K : words);
+}
+
+extern "C" size_t sph3d_graph_canonical_order_workspace(int B, int N, int M, int K, int F)
+{
+    (void)N;
+    (void)F;
+    if (B <= 0 || M <= 0 || K <= 0) return 0;
+    return sizeof(int) * 2 * (size_t)B * M * K;
+}
+
+extern "C" int sph3d_graph_canonical_order(int B, int N, int M, int K, int F, const int* offsets, int* ent_key, float* ent_scale,
+                                           void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B > 0 && N > 0 && M > 0 && K > 0 && F > 0, "graph_canonical_order: bad dims B=%d N=%d M=%d K=%d F=%d", B, N, M, K, F);
+    SPH3D_REQUIRE((long long)N * F < (1LL << 31) && (long long)B * M * K < (1LL << 31), "graph_canonical_order: N*F or B*M*K overflows int32");
+    SPH3D_REQUIRE(offsets != nullptr && ent_key != nullptr, "graph_canonical_order: offsets and ent_key must not be NULL");
+    const size_t need = sph3d_graph_canonical_order_workspace(B, N, M, K, F);
+    if (workspace == nullptr || workspace_bytes < need) {
+        set_error("graph_canonical_order: workspace %zu B < required %zu B", workspace_bytes, need);
+        return SPH3D_EWORKSPACE;
+    }
+    launch_canonical_order(B, N, F, offsets, ent_key, ent_scale, (int*)workspace, (size_t)B * M * K, as_stream(stream));
+    return check_launch("sph3d_graph_canonical_order");
 }
 
 static int tg_dims_ok(int B, int N, int M, int K, int F, const void* bin_index, const void* workspace, size_t workspace_bytes)
@@ -461,6 +621,8 @@ static int tg_finish(int B, int N, int M, int K, int F, const int* nn_index, con
     if (nob + fb > 0)
         hipLaunchKernelGGL(tg_fill_order, dim3((unsigned)(nob + fb)), dim3(1024), 0, st, nob, B, N, M, K, F, nn_index, nn_count,
                            bin_index, weight, offsets, w.slot_pos, ent_key, ent_scale, order);
+    // deterministic mode: the slot positions are dead now and stage the canonical-order pass (the words behind them: the factors)
+    if (deterministic_on() && total > 0) launch_canonical_order(B, N, F, offsets, ent_key, ent_scale, w.slot_pos, (size_t)total, st);
     return check_launch("sph3d_graph_transpose");
 }
 

@@ -571,6 +571,11 @@ extern "C" int sph3d_max_pool3d_grad(int B, int N, int M, int C, const int* max_
                                      float* grad_input, sph3d_stream_t stream)
 {
     SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && C > 0, "MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d", B, N, M, C);
+    if (deterministic_on()) {
+        set_error("MaxPool3dGrad: deterministic mode is on and the scatter form adds with float atomics; use sph3d_max_pool3d_grad_t "
+                  "on the transposed pooling graph");
+        return SPH3D_EUNSUPPORTED;
+    }
     if (B == 0) return SPH3D_OK;
     hipStream_t st = as_stream(stream);
     int rc = zero_async(grad_input, sizeof(float) * (size_t)B * N * C, st, "sph3d_max_pool3d_grad");

@@ -28,7 +28,7 @@ import re
 import numpy as np
 import torch
 
-from .. import _lib, tf_norm
+from .. import _lib, _tgraph, tf_norm
 from . import dist as hdist
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -270,10 +270,12 @@ class Trainer:
     gradient by (1 / world size for a loss that is a mean over the global batch).  sync_bn: train_step runs its forward and
     backward pass under tf_norm.sync(hdist.stat_all_reduce) — batch-norm statistics over the global batch; every
     rank must then run the same layer sequence with at least one row per layer (the ranks' row counts may differ: the count
-    travels in the collective's buffer).  Evaluation is inference mode and issues no collective."""
+    travels in the collective's buffer).  Evaluation is inference mode and issues no collective.  deterministic: train_step,
+    eval_one_epoch and fit run under sph3d_gcn_amd.deterministic() — on one rank the same seed then gives the same bits, run after
+    run and across a resume; the mode is back at its previous value when they return."""
 
     def __init__(self, model, loss_fn, optimizer_factory, schedule, num_cls, line=s3dis_line, prime=None, seed=0, log_every=50,
-                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False):
+                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False):
         if prime is None:
             raise ValueError("Trainer: `prime` (one batch of the training shapes) is needed to create the variables")
         self.model, self.loss_fn, self.schedule, self.line = model, loss_fn, schedule, line
@@ -281,6 +283,7 @@ class Trainer:
         self.class_names = list(class_names) if class_names is not None else ["class %d" % c for c in range(self.num_cls)]
         self.log = log
         self.sync_bn = bool(sync_bn)
+        self.deterministic = bool(deterministic)
         self.global_step, self.epoch = 0, -1           # updates done; the last finished epoch
         self.rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
         batch = self.line(tuple(prime))
@@ -319,8 +322,15 @@ class Trainer:
             torch.cuda.current_stream().wait_event(ready)       # (the loss reads the labels on this stream)
         return batch, pred, self._total_loss(pred, batch), ready
 
+    def _mode(self):
+        return _tgraph.deterministic(True) if self.deterministic else contextlib.nullcontext()
+
     def train_step(self, item, feed=None):
         """plan / forward, loss, backward, all-reduce, update, metrics; nothing is read from the device"""
+        with self._mode():
+            self._train_step(item, feed)
+
+    def _train_step(self, item, feed):
         # sync_bn: every training-mode batch norm takes its statistics over all ranks' rows, one small all-reduce per layer and
         # direction (every rank runs the same layers, each with at least one row; the row counts may differ)
         with (tf_norm.sync(hdist.stat_all_reduce) if self.sync_bn else contextlib.nullcontext()):
@@ -369,7 +379,7 @@ class Trainer:
         one read at the end and the reference's evaluation lines -> MetricsResult"""
         m = self.eval_metrics
         m.reset()
-        with torch.no_grad():
+        with self._mode(), torch.no_grad():
             for item in feed:
                 batch, pred, loss, ready = self._forward(item, False)
                 m.add(pred, batch.label, batch.inner, loss.reshape(1))
@@ -431,6 +441,10 @@ class Trainer:
         its epochs is set to `epoch`: its batches are functions of (seed, epoch, step) alone).  With ckpt_dir the newest
         checkpoint there is loaded first and training continues at the epoch after it (train_s3dis.py:255-288); one checkpoint
         is written per epoch."""
+        with self._mode():
+            self._fit(train_feed_factory, epochs, eval_feed_factory, ckpt_dir)
+
+    def _fit(self, train_feed_factory, epochs, eval_feed_factory, ckpt_dir):
         if ckpt_dir is not None:
             newest = latest_checkpoint(ckpt_dir)
             if newest is not None:

@@ -140,6 +140,16 @@ def _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg, addend=
     return grad_input
 
 
+def _no_scatter_when_deterministic():
+    """deterministic mode: the max-pool gradient is the gather over a unique-rows transposed pooling graph or an error, never the
+    scatter with its float atomics"""
+    if _tgraph.is_deterministic():
+        raise RuntimeError("max_pool3d backward: deterministic mode is on and no transposed pooling graph with unique rows is cached for "
+                           "this (nn_index, nn_count); the scatter form adds with float atomics.  Build the pooling graph with "
+                           "unique_rows=True (sph3gcn_util.gather_pooling_graph, or _tgraph.transpose(nn_index, nn_count, N, "
+                           "unique_rows=True)) while the mode is on")
+
+
 class _MaxPool3dFn(torch.autograd.Function):      # eager fast path (see tf_conv3d._DepthwiseConv3dFn)
     @staticmethod
     def forward(ctx, input, nn_index, nn_count):
@@ -159,6 +169,7 @@ class _MaxPool3dFn(torch.autograd.Function):      # eager fast path (see tf_conv
             tg = _tgraph.peek(nn_index, nn_count, input.shape[1], need_unique_rows=True)
         if tg is not None:
             return _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg), None, None
+        _no_scatter_when_deterministic()
         return _max_pool3d_grad_impl(input, grad_output, max_index), None, None
 
 
@@ -201,6 +212,7 @@ class _MaxPool3dSkipFn(torch.autograd.Function):
         if tg is not None:
             skip = grad_skip.contiguous() if grad_skip is not None else None
             return _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg, addend=skip), None, None
+        _no_scatter_when_deterministic()
         g = _max_pool3d_grad_impl(input, grad_output, max_index)
         return (g if grad_skip is None else g + grad_skip), None, None
 
