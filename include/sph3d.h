@@ -820,6 +820,44 @@ int sph3d_nn1(long long V, long long F, const float* ref_xyz, const float* query
 int sph3d_scene_lift(int C, long long V, long long F, const int* pred_voxel, const int* idx, const int* label_map,
                      const int* label_full, int* pred_full, long long* confusion, sph3d_stream_t stream);
 
+/* ---- surface normals from order-free integer ball moments (csrc/normals.hip; not in the reference, whose facade line reads its
+ * normals from the dataset).  harness/normals.py states every entry in numpy: moments and counts equal it bit for bit, normal and
+ * variation are held to the per-element bounds of tests/_normal_ref.py.  Every buffer is the caller's; no floating-point atomic.
+ *   offsets     query q, neighbour p, both fp32 xyz: d_a = p_a - q_a (one fp32 subtraction per axis); Q = 262144.0 / (double)radius
+ *               (one double division); t_a = rint((double)d_a * Q) (one double product, ties to even).  A neighbour is VALID when
+ *               fabs((double)d_a) * Q <= 2^21 on all three axes, evaluated in double; a non-finite coordinate fails and the
+ *               neighbour is skipped.  A query with a non-finite coordinate has no valid neighbour.
+ *   moments     ten signed 64-bit integers per query over its valid neighbours: n; S1_x, S1_y, S1_z = sum t_a; S2_xx, S2_xy, S2_xz,
+ *               S2_yy, S2_yz, S2_zz = sum t_a t_b.  |t| <= 2^21 and n < 2^16 (graph form) or |t| <= 2^18 and n <= 2^26 (ball form):
+ *               nothing overflows, and integer sums do not depend on the order the neighbours are visited in.
+ *   covariance  float64, every operation rounded once (no contraction): m_a = (double)S1_a / n, c_ab = (double)S2_ab / n - m_a m_b.
+ *   normal      l0 <= l1 <= l2 the eigenvalues of c: the unit eigenvector of l0; variation = max(l0, 0) / (l0 + l1 + l2) as fp32.
+ *               A row with n < min_count (min_count >= 3) or with a trace (c_xx + c_yy) + c_zz that is not positive gets the
+ *               normal (0, 0, 0) and variation 0; any other row a unit vector (a collinear neighbourhood: some unit vector
+ *               perpendicular to the line, and variation tells).
+ *   sign        decided on the float64 vector before the rounding to fp32: first the component of largest magnitude is made
+ *               positive (ties: the lowest axis); then, with `toward`, the normal is flipped when
+ *               n . ((double)toward - (double)q) < 0; a product of exactly 0 keeps the canonical sign.
+ *   graph_normals   database [B,N,3], query [B,M,3], nn_index [B,M,K], nn_count [B,M] as the searches leave them (compat or
+ *               fixed radius mode, M != N, 0 < K < 2^16): the neighbours of a row are its first min(nn_count, K) entries, in list
+ *               order; an entry outside [0, N) is skipped like an invalid one.  toward [B,3] or NULL.  -> normals [B,M,3];
+ *               variation [B,M], count [B,M] int32 (= n), moments [B,M,10] int64, all three nullable; counters [1] int64
+ *               (nullable): counters[0] += the skipped neighbours (accumulated, not zeroed).  No workspace.  B * M == 0: nothing
+ *               is launched.
+ *   ball_normals    xyz [V,3], a flat cloud (a facade, a room, a pool block), V <= 2^26.  The neighbours of a row are ALL rows
+ *               with the fp32 predicate (dx*dx + dy*dy) + dz*dz < r2, dx = p.x - q.x, r2 = fp32(radius * radius), every operation
+ *               rounded once as in nn1; the row itself is one of them.  toward [3] or NULL.  -> normals [V,3], count [V] int32,
+ *               variation [V] and moments [V,10] nullable.  Walks nn1's counting-sorted cell grid, built with a cell edge of at
+ *               least `radius`, and falls back to brute force on the device under nn1's conditions; both give the same moments.
+ *               The workspace holds sph3d_ball_normals_workspace(V) bytes, 16-byte aligned.  V == 0: nothing is launched. */
+int sph3d_graph_normals(int B, int N, int M, int K, float radius, int min_count, const float* database, const float* query,
+                        const int* nn_index, const int* nn_count, const float* toward, float* normals, float* variation, int* count,
+                        long long* moments, long long* counters, sph3d_stream_t stream);
+size_t sph3d_ball_normals_workspace(long long V);
+int sph3d_ball_normals(long long V, float radius, int min_count, const float* xyz, const float* toward, float* normals,
+                       float* variation, int* count, long long* moments, void* workspace, size_t workspace_bytes,
+                       sph3d_stream_t stream);
+
 /* ---- scene preparation (MATLAB pcdownsample 'gridAverage', preprocesing/s3dis_prepare_data.m:35-37; the block writer,
  * io/make_tfrecord_s3dis.py:113-242; csrc/prep.hip): a full-resolution cloud is averaged over the cells of a grid, the voxel cloud
  * is recentred, and the blocks of a pool (rows [T,8], index [T], as sph3d_feed_assemble / sph3d_scene_merge read them) are cut

@@ -108,6 +108,9 @@ SIGNATURES = {
     "sph3d_nn1_workspace": (_S, [_L, _L]),
     "sph3d_nn1": (_I, [_L, _L, _P, _P, _I, _P, _P, _S, _P]),
     "sph3d_scene_lift": (_I, [_I, _L, _L] + [_P] * 6 + [_P]),
+    "sph3d_graph_normals": (_I, [_I, _I, _I, _I, _F, _I] + [_P] * 10 + [_P]),
+    "sph3d_ball_normals_workspace": (_S, [_L]),
+    "sph3d_ball_normals": (_I, [_L, _F, _I] + [_P] * 6 + [_P, _S, _P]),
     "sph3d_prep_voxel_grid_workspace": (_S, [_L, _L]),
     "sph3d_prep_voxel_grid": (_I, [_L, _I, _P, _P, _F, _L, _P, _P, _P, _S, _P]),
     "sph3d_prep_voxel_reduce_workspace": (_S, [_L, _L, _I]),

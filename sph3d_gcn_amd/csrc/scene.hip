@@ -19,7 +19,8 @@
 //                      about one cell per two points (at most kNn1MaxCells cells and kNn1MaxDim per axis), counting sort in
 //                      global memory: count per cell, one-workgroup exclusive scan, fill of (x, y, z, index) in cell order.
 //                      The fill's order inside a cell depends on the atomics' arrival; the search's result does not (the tie
-//                      rule compares indices).
+//                      rule compares indices).  nn1_build (nn1grid.hpp) queues it; normals.hip's ball form calls it too, with
+//                      a minimum cell edge (nn1 passes 0: the grid it always had).
 //              search  a thread per query walks rings of cells (Chebyshev distance 0, 1, 2, ... from the query's cell; cells are
 //                      z-fastest, so a column's share of a ring is one contiguous run of the sorted points).  After ring k every
 //                      unvisited point differs from the query by more than (k - 4e-4) h along some axis: a point or a query lands
@@ -34,48 +35,14 @@
 //   lift       pred_full = pred_voxel[idx] (-1 where idx is -1), through label_map when given; optional confusion counts.
 #pragma clang fp contract(off)
 #include "common.hpp"
+#include "nn1grid.hpp"
 #include "../../include/sph3d_exp32.h"
 
 namespace sph3d {
 
 constexpr int kSceneMaxClasses = kVoteMaxClasses;
 constexpr int kSceneParts = 64;             // workgroups of a merge launch (row-strided)
-constexpr int kNn1MinGrid = 64;             // fewer finite reference points: brute force
-constexpr int kNn1MinCells = 64;
-constexpr int kNn1MaxCells = 1 << 21;       // 8 MB of cell ends
-constexpr int kNn1MaxDim = 1024;            // cells per axis: bounds the rounding of the cell coordinate (see above)
-constexpr int kNn1Tile = 1024;              // reference points per LDS tile of the brute-force kernel
-
-struct Nn1Hdr {
-    unsigned lo[3], hi[3];                  // bounding box as ordered integers
-    int nfin, flag;                         // finite reference points; 1: the grid cannot index this cloud
-    float minx, miny, minz, invh, h;
-    int nx, ny, nz, ncell;
-};
-constexpr size_t kNn1HdrBytes = 256;
-
-static inline long long nn1_cell_cap(long long V)
-{
-    const long long c = V / 2;
-    return c < kNn1MinCells ? kNn1MinCells : (c > kNn1MaxCells ? kNn1MaxCells : c);
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z)
-{
-    return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
-}
-// cell coordinate along one axis, clamped into the grid (a query outside the box takes the nearest cell)
-__device__ __forceinline__ int nn1_cell(float v, float lo, float invh, int n)
-{
-    const float t = floorf((v - lo) * invh);
-    return t >= 0.0f ? (t < (float)n ? (int)t : n - 1) : 0;
-}
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+// (the grid's constants, its header and nn1_cell / finite3 / wave_sum: nn1grid.hpp, shared with normals.hip)
 
 // ---- merge -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void scene_merge_kernel(int b, int C, int P, long long T, const float* __restrict__ rows,
@@ -210,8 +177,8 @@ __global__ __launch_bounds__(256) void nn1_bbox_kernel(long long V, const float*
 }
 
 // the grid's shape, by one thread: the largest h (from the longest extent down in steps of 0.8) whose grid still has at most
-// `target` cells and kNn1MaxDim - 1 steps per axis
-__global__ void nn1_setup_kernel(Nn1Hdr* __restrict__ hdr)
+// `target` cells and kNn1MaxDim - 1 steps per axis, and that is not below min_h (0 for sph3d_nn1: no such limit)
+__global__ void nn1_setup_kernel(Nn1Hdr* __restrict__ hdr, float min_h)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int nfin = hdr->nfin;
@@ -241,7 +208,7 @@ __global__ void nn1_setup_kernel(Nn1Hdr* __restrict__ hdr)
         int t3[3];
         const float h2 = h * 0.8f;
         const long long c = cells_at(h2, t3);
-        if (!(h2 > 0.0f) || c < 0 || c > target) break;
+        if (!(h2 > 0.0f) || h2 < min_h || c < 0 || c > target) break;
         h = h2;
     }
     const long long cells = cells_at(h, n3);
@@ -403,6 +370,19 @@ static unsigned strided_grid(long long n)
     return (unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));
 }
 
+int nn1_build(long long V, const float* ref_xyz, float min_h, bool grid, const Nn1Ws& w, hipStream_t s)
+{
+    hipLaunchKernelGGL(nn1_init_kernel, dim3(1), dim3(64), 0, s, w.hdr);
+    if (!grid) return SPH3D_OK;
+    if (int rc = zero_async(w.cell, w.cellBytes, s, "nn1: cell counters")) return rc;
+    hipLaunchKernelGGL(nn1_bbox_kernel, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, w.hdr);
+    hipLaunchKernelGGL(nn1_setup_kernel, dim3(1), dim3(64), 0, s, w.hdr, min_h);
+    hipLaunchKernelGGL(nn1_sort_kernel<false>, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, w.hdr, w.cell, w.pts);
+    hipLaunchKernelGGL(nn1_scan_kernel, dim3(1), dim3(1024), 0, s, w.hdr, w.cell);
+    hipLaunchKernelGGL(nn1_sort_kernel<true>, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, w.hdr, w.cell, w.pts);
+    return SPH3D_OK;
+}
+
 }  // namespace sph3d
 
 using namespace sph3d;
@@ -457,8 +437,7 @@ extern "C" int sph3d_scene_lift(int C, long long V, long long F, const int* pred
 extern "C" size_t sph3d_nn1_workspace(long long V, long long F)
 {
     if (V <= 0 || F <= 0 || V > 0x7fffffffll || F > 0x7fffffffll) return 0;
-    const size_t cells = (((size_t)nn1_cell_cap(V) + 1) * sizeof(int) + 255) & ~(size_t)255;
-    return kNn1HdrBytes + cells + (size_t)V * sizeof(float4);
+    return nn1_ws(nullptr, V).bytes;
 }
 
 extern "C" int sph3d_nn1(long long V, long long F, const float* ref_xyz, const float* query_xyz, int mode, int* idx,
@@ -470,23 +449,12 @@ extern "C" int sph3d_nn1(long long V, long long F, const float* ref_xyz, const f
     SPH3D_REQUIRE(workspace != nullptr && workspace_bytes >= sph3d_nn1_workspace(V, F) && (reinterpret_cast<size_t>(workspace) & 15) == 0,
                   "nn1: workspace of %zu bytes, 16-byte aligned, required (got %zu)", sph3d_nn1_workspace(V, F), workspace_bytes);
     hipStream_t s = as_stream(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    Nn1Hdr* hdr = reinterpret_cast<Nn1Hdr*>(ws);
-    int* cell = reinterpret_cast<int*>(ws + kNn1HdrBytes);
-    const size_t cellBytes = (((size_t)nn1_cell_cap(V) + 1) * sizeof(int) + 255) & ~(size_t)255;
-    float4* pts = reinterpret_cast<float4*>(ws + kNn1HdrBytes + cellBytes);
+    const Nn1Ws w = nn1_ws(workspace, V);
     const unsigned qblocks = (unsigned)((F + 255) / 256);
-    hipLaunchKernelGGL(nn1_init_kernel, dim3(1), dim3(64), 0, s, hdr);
-    if (mode == SPH3D_NN1_GRID) {
-        if (int rc = zero_async(cell, cellBytes, s, "nn1: cell counters")) return rc;
-        hipLaunchKernelGGL(nn1_bbox_kernel, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, hdr);
-        hipLaunchKernelGGL(nn1_setup_kernel, dim3(1), dim3(64), 0, s, hdr);
-        hipLaunchKernelGGL(nn1_sort_kernel<false>, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, hdr, cell, pts);
-        hipLaunchKernelGGL(nn1_scan_kernel, dim3(1), dim3(1024), 0, s, hdr, cell);
-        hipLaunchKernelGGL(nn1_sort_kernel<true>, dim3(strided_grid(V)), dim3(256), 0, s, V, ref_xyz, hdr, cell, pts);
-        hipLaunchKernelGGL(nn1_search_kernel, dim3(qblocks), dim3(256), 0, s, V, F, query_xyz, hdr, cell, pts, idx);
-    }
-    hipLaunchKernelGGL(nn1_brute_kernel, dim3(qblocks), dim3(256), 0, s, V, F, mode == SPH3D_NN1_BRUTE ? 1 : 0, ref_xyz, query_xyz, hdr,
-                       idx);
+    if (int rc = nn1_build(V, ref_xyz, 0.0f, mode == SPH3D_NN1_GRID, w, s)) return rc;
+    if (mode == SPH3D_NN1_GRID)
+        hipLaunchKernelGGL(nn1_search_kernel, dim3(qblocks), dim3(256), 0, s, V, F, query_xyz, w.hdr, w.cell, w.pts, idx);
+    hipLaunchKernelGGL(nn1_brute_kernel, dim3(qblocks), dim3(256), 0, s, V, F, mode == SPH3D_NN1_BRUTE ? 1 : 0, ref_xyz, query_xyz,
+                       w.hdr, idx);
     return check_launch("sph3d_nn1");
 }

@@ -132,6 +132,15 @@ class FacadePool:
         return cls([p[0] for p in pairs], [p[1] for p in pairs], device)
 
     @classmethod
+    def from_arrays_estimated(cls, xyz, rgb, label, radius, toward=None, device=None):
+        """per facade: xyz, rgb [n, 3] and label [n], no normals: they are estimated on the device, per facade, from all points
+        within `radius` (harness/normals.py: estimate_pool; toward: None or the [3] point the normals face)"""
+        from . import normals as _normals
+        self = cls.from_arrays(xyz, [np.zeros(np.shape(x), dtype=np.float32) for x in xyz], rgb, label, device)
+        self.normals = _normals.estimate_pool(self.pool, radius, toward)
+        return self
+
+    @classmethod
     def from_records(cls, paths, device=None, verify=True):
         """every record of every file is one facade, in path order"""
         pairs = [facade_blocks(*f) for p in paths for f in read_facade_records(p, verify=verify)]
