@@ -251,8 +251,12 @@ int sph3d_graph_balanced_order(int B, int N, int F, const int* offsets, int* ord
  *   - sph3d_graph_transpose_workspace() (and every workspace size that contains it) is B*M*K words larger: size workspaces
  *     while the mode has the value they will be used with;
  *   - the conv gradient runs no hub launches (float atomics), for any N; SPH3D_BWD_HUB_* are ignored;
- *   - what can only run with float atomics refuses with SPH3D_EUNSUPPORTED: conv gradient shapes of the generic kernel
- *     (sph3d_depthwise_conv3d_grad_t, _grad_t_cat, _grad) and sph3d_max_pool3d_grad (use sph3d_max_pool3d_grad_t).
+ *   - conv gradient shapes with r = 1, odd C and F <= 65 (the generic kernel's while the mode is off) run a fixed-order gather
+ *     of their own, and sph3d_depthwise_conv3d_grad_t_workspace() / _grad_workspace() return its slab bytes for them (0 more
+ *     than the transposed graph's with the mode off);
+ *   - what can only run with float atomics refuses with SPH3D_EUNSUPPORTED: the other conv gradient shapes of the generic kernel
+ *     (r outside {1, 2}, F > 65; sph3d_depthwise_conv3d_grad_t, _grad_t_cat, _grad) and sph3d_max_pool3d_grad (use
+ *     sph3d_max_pool3d_grad_t).
  * Transposed graphs built while the mode was off keep their arrival order: rebuild them after switching it on. */
 int sph3d_set_deterministic(int on);
 int sph3d_get_deterministic(void);
@@ -655,6 +659,16 @@ int sph3d_train_update(long long n, float* param, const float* grad, float* slot
  * result is a pure function of the inputs and the order of the calls.  C <= 64 (SPH3D_EUNSUPPORTED above). */
 int sph3d_train_metrics(int B, int N, int C, const float* logits, const int* label, const int* inner, const float* loss_part,
                         int loss_parts, long long* confusion, long long* counters, double* loss_sum, sph3d_stream_t stream);
+
+/* ---- keyed inverted dropout (the classifiers' tf.layers.dropout) as a pure function of its arguments: no generator state, so a
+ * resumed run drops what the uninterrupted one drops.  x, y [B, row_len] fp32 (y may be x).  Element i of row b is kept iff the
+ * high word of feed_draw(feed_cloud_key(seed, step, row0 + b), 16 + layer, i) (csrc/feed_draws.hpp) is >= threshold, and then
+ * y = x * scale; a dropped element is +0.0 whatever x holds (inf, NaN).  The caller computes threshold = min(2^32 - 1,
+ * ceil(rate * 2^32)) and scale = (float)(1 / (1 - rate)); the gradient is the same call on grad_output.  harness/dropout.py states
+ * the op in numpy; the device result equals it bit for bit.  SPH3D_EINVAL: row_len >= 2^32, a layer outside [0, 16), row0 < 0 or
+ * row0 + B > 2^32. */
+int sph3d_dropout_keyed(int B, long long row_len, const float* x, float* y, unsigned long long seed, unsigned long long step,
+                        long long row0, int layer, unsigned int threshold, float scale, sph3d_stream_t stream);
 
 /* ---- the input side of the S3DIS training loop (train_s3dis.py:114-142,343-347) on the device: one launch assembles a batch
  * from a resident pool of parsed blocks.  rows [T,8] fp32: all blocks back to back, a row = xyz, rgb, label, inner (what

@@ -91,6 +91,7 @@ SIGNATURES = {
     "sph3d_adam_step": (_I, [ctypes.c_longlong] + [_P] * 4 + [_F] * 4 + [_I, _P]),
     "sph3d_train_update": (_I, [_L] + [_P] * 4 + [_I] + [_F] * 4 + [_I, _F, _P, _P]),
     "sph3d_train_metrics": (_I, [_I] * 3 + [_P] * 4 + [_I] + [_P] * 3 + [_P]),
+    "sph3d_dropout_keyed": (_I, [_I, _L, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _L, _I, ctypes.c_uint, _F, _P]),
     "sph3d_feed_assemble": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I] + [_P] * 5),
     "sph3d_objfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
     "sph3d_facadefeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),

@@ -809,6 +809,168 @@ __global__ __launch_bounds__(256) void dwconv_bwd_t_generic(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// backward over the transposed graph for ODD row widths (r = 1, C odd: the ModelNet plan's C = 67 and 131), the fixed-order
+// form deterministic mode runs where dwconv_bwd_t_generic would sum with float atomics.  The scheme is dwconv_bwd_t_vec's
+// full-wave form — one wave per source, the F segments walked in entry order in a fully unrolled loop, four row gathers issued
+// before the first is used and the segment's last one to three edges with exactly that many, grad_input in registers and stored
+// once, grad_filter in a private [MAXF][T] register table, the four waves' tables added through LDS in turn order into one slab,
+// reduce_filter_partials over the slabs — with another ownership of the channels: a row of C floats is only 4-byte aligned, so
+// no lane can load two or four channels at once; lane l owns channels slice0 + l + 64 t, t < T (the generic kernels' ownership),
+// and a row gather is T dword loads, each coalesced on any alignment, with the lanes past the row's end reading the slice's first
+// column.  T <= 4 for F <= 33 and T <= 2 for F <= 65: at most 132 accumulator registers, as the V = 4 form.
+// The partition is bwd_plan's static one (W workgroups per XCD and slice, (cloud, part) items dealt to the XCDs, positions of
+// source_order interleaved over the waves): no work cursor, no hub launches, no atomics of any kind, so every slab is a function
+// of the shape, the graph and the order alone.
+// ------------------------------------------------------------------------------------------
+template <int T, int MAXF>
+__global__ __launch_bounds__(kBwdTWaves * 64, 3) void dwconv_bwd_t_odd(
+    int B, int N, int M, int F, int C, int W, int parts, int nslices,
+    const int* __restrict__ offsets, const int* __restrict__ entKey, const float* __restrict__ entScale,
+    const int* __restrict__ order,
+    const float* __restrict__ input, const float* __restrict__ filter, const float* __restrict__ gradOutput,
+    float* __restrict__ gradInput, float* __restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int SLW = 64 * T;                 // slice width in channels
+    const int xcd = (int)blockIdx.x & 7;
+    const int q = (int)blockIdx.x >> 3;
+    const int slice = q / W;
+    const int w = q - slice * W;
+    const int slice0 = slice * SLW;
+    const int SL = (C - slice0) < SLW ? (C - slice0) : SLW;
+    // [F][SLW], zeros past the slice's end: a compile-time row stride, so a lane reads row fi at ONE address + an immediate
+    // (with the stride SL the compiler kept MAXF x T hoisted addresses in registers and spilled the accumulators)
+    float* lfilt = lds;
+    for (int e = threadIdx.x; e < F * SLW; e += blockDim.x) {
+        const int f = e / SLW;
+        const int cl = e - f * SLW;
+        lfilt[e] = cl < SL ? filter[(size_t)f * C + slice0 + cl] : 0.f;
+    }
+    __syncthreads();
+
+    const int wave = uniform((int)threadIdx.x >> 6);
+    const int lane = lane_id();
+    const int stride = W * kBwdTWaves;
+    bool act[T];
+    unsigned cla[T];                            // the lane's columns inside the slice; past the row's end: column 0 (read, never stored)
+#pragma unroll
+    for (int t = 0; t < T; t++) {
+        act[t] = lane + 64 * t < SL;
+        cla[t] = act[t] ? (unsigned)(lane + 64 * t) : 0u;
+    }
+    float acc[MAXF][T];
+#pragma unroll
+    for (int i = 0; i < MAXF; i++)
+#pragma unroll
+        for (int t = 0; t < T; t++) acc[i][t] = 0.f;
+
+    for (int item = xcd; item < B * parts; item += 8) {
+    const int b = item / parts;
+    const int pi = item - b * parts;
+    const float* __restrict__ gou = gradOutput + (size_t)b * M * C + slice0;
+    const int* __restrict__ offb = offsets + (size_t)b * ((size_t)N * F + 1);
+    for (int p = pi + parts * (w * kBwdTWaves + wave); p < N; p += parts * stride) {
+        const int n = order ? uniform(order[(size_t)b * N + p]) : p;
+        // the source's F + 1 segment bounds: one coalesced read (two for 65 bins), consumed with v_readlane
+        const int* __restrict__ o = offb + (size_t)n * F;
+        const int ov0 = o[lane <= F ? lane : F];
+        const int ov1 = (MAXF >= 64) ? o[(64 + lane) <= F ? (64 + lane) : F] : 0;
+        const size_t xrow = ((size_t)b * N + n) * C + slice0;
+        float xv[T], gi[T];
+#pragma unroll
+        for (int t = 0; t < T; t++) {
+            xv[t] = input[xrow + cla[t]];
+            gi[t] = 0.f;
+        }
+        const int E0 = __builtin_amdgcn_readlane(ov0, 0);
+        const int E1 = uniform(o[F]);
+        for (int cb = E0; cb < E1; cb += 64) {
+        // keys and scales of 64 in-edges: one coalesced load each (lane = edge), handed to the gathers with v_readlane
+        const int cn = (E1 - cb) < 64 ? (E1 - cb) : 64;
+        const int li = lane < cn ? lane : 0;
+        const int wkey = entKey[cb + li];
+        const unsigned kel = (unsigned)tg_key(wkey, entScale == nullptr) * (unsigned)C;     // row offset in floats (M * C < 2^32: launcher)
+        const float sv = entScale == nullptr ? tg_packed_scale(wkey) : entScale[cb + li];
+#pragma unroll
+        for (int fi = 0; fi < MAXF; fi++) {
+            if (fi < F) {
+                const int a0 = __builtin_amdgcn_readlane(fi < 64 ? ov0 : ov1, fi & 63);
+                const int a1 = __builtin_amdgcn_readlane((fi + 1) < 64 ? ov0 : ov1, (fi + 1) & 63);
+                // the part of the segment inside this chunk, as lane numbers
+                const int e0 = (a0 > cb ? a0 : cb) - cb;
+                const int e1 = (a1 < cb + cn ? a1 : cb + cn) - cb;
+                if (e0 < e1) {                               // wave-uniform
+                    float sg[T], wr[T];
+#pragma unroll
+                    for (int t = 0; t < T; t++) {
+                        sg[t] = 0.f;
+                        wr[t] = lfilt[fi * SLW + 64 * t + lane];     // read under the gathers, not after them
+                    }
+                    // lanes e0 .. e1 - 1 only: no row outside the segment is gathered, no foreign row is multiplied by 0
+#define SPH3D_BWD_ODD_BATCH(NB)                                                                                      \
+    {                                                                                                                \
+        float sc[NB];                                                                                                \
+        float g[NB][T];                                                                                              \
+        _Pragma("unroll") for (int u = 0; u < NB; u++) {                                                             \
+            const unsigned ko = (unsigned)__builtin_amdgcn_readlane((int)kel, e + u);                                \
+            sc[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sv), e + u));                            \
+            const float* __restrict__ rp = gou + ko;                /* wave-uniform row address */                   \
+            _Pragma("unroll") for (int t = 0; t < T; t++) g[u][t] = rp[cla[t]];                                      \
+        }                                                                                                            \
+        _Pragma("unroll") for (int u = 0; u < NB; u++)                                                               \
+            _Pragma("unroll") for (int t = 0; t < T; t++) sg[t] = fmaf(g[u][t], sc[u], sg[t]);                       \
+    }
+                    int e = e0;
+                    for (; e + 4 <= e1; e += 4) SPH3D_BWD_ODD_BATCH(4)
+                    const int rem = e1 - e;
+                    if (rem == 3) SPH3D_BWD_ODD_BATCH(3)
+                    else if (rem == 2) SPH3D_BWD_ODD_BATCH(2)
+                    else if (rem == 1) SPH3D_BWD_ODD_BATCH(1)
+#undef SPH3D_BWD_ODD_BATCH
+#pragma unroll
+                    for (int t = 0; t < T; t++) {
+                        gi[t] = fmaf(sg[t], wr[t], gi[t]);
+                        acc[fi][t] = fmaf(sg[t], xv[t], acc[fi][t]);
+                    }
+                }
+            }
+        }
+        }   // chunks of 64 in-edges
+        // stored once per element; a source without in-edges gets its zero row
+#pragma unroll
+        for (int t = 0; t < T; t++)
+            if (act[t]) gradInput[xrow + cla[t]] = gi[t];
+    }
+    }   // items
+
+    // workgroup reduction of the per-wave tables: the waves take turns, in wave order, on one [F][SLW] LDS table (the columns
+    // past the slice's end hold what their idle lanes computed; they are not copied out)
+    __syncthreads();                 // everyone is done reading lfilt
+    float* tab = lds;
+    for (int tw = 0; tw < kBwdTWaves; tw++) {
+        if (wave == tw) {
+#pragma unroll
+            for (int i = 0; i < MAXF; i++) {
+                if (i < F) {
+#pragma unroll
+                    for (int t = 0; t < T; t++) {
+                        float* p = &tab[i * SLW + 64 * t + lane];
+                        *p = (tw == 0) ? acc[i][t] : (*p + acc[i][t]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float* out = partial + ((size_t)xcd * W + w) * ((size_t)F * C);
+    for (int e = threadIdx.x; e < F * SL; e += blockDim.x) {
+        const int f = e / SL;
+        const int cl = e - f * SL;
+        out[(size_t)f * C + slice0 + cl] = tab[f * SLW + cl];
+    }
+}
+
 static int conv_dims_ok(int B, int N, int M, int F, int C, int r, int K, const char* who)
 {
     SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && F > 0 && C > 0 && r > 0 && K > 0,
@@ -950,10 +1112,41 @@ static BwdLayout bwd_layout(int B, int N, int F, int C, int r)
     return L;
 }
 
-extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r) { return bwd_layout(B, N, F, C, r).bytes; }
+// The odd-width gradient's plan (dwconv_bwd_t_odd, deterministic mode only): r = 1 and odd C — with r in {1, 2} every other row
+// width is even and has a vec_plan.  T channels per lane: as many as the row needs, at most 4 (F <= 33) or 2 (F <= 65); wider
+// rows take several slices of 64 T channels.  The sweep is bwd_plan's at 3 workgroups per CU; the workspace is its slabs alone.
+struct OddLayout {
+    int T;             // 0: not an odd-width shape
+    int nslices;
+    BwdTable plan;
+    size_t bytes;
+};
+static OddLayout odd_layout(int B, int N, int F, int C, int r)
+{
+    OddLayout L = {};
+    if (r != 1 || C % 2 == 0 || F > 65) return L;
+    const int tmax = F <= 33 ? 4 : 2;
+    const int need = (C + 63) / 64;
+    L.T = need < tmax ? need : tmax;
+    L.nslices = (C + 64 * L.T - 1) / (64 * L.T);
+    L.plan = bwd_plan(B, N, L.nslices, 3);
+    L.bytes = sizeof(float) * (size_t)L.plan.slabs * F * C;
+    return L;
+}
+
+// bytes of the gradient's own workspace: the vector plan's; in deterministic mode the odd-width plan's for the shapes it serves;
+// 0 for what takes the generic kernel
+static size_t grad_t_bytes(int B, int N, int F, int C, int r)
+{
+    const BwdLayout L = bwd_layout(B, N, F, C, r);
+    if (L.V == 0 && deterministic_on()) return odd_layout(B, N, F, C, r).bytes;
+    return L.bytes;
+}
+
+extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r) { return grad_t_bytes(B, N, F, C, r); }
 extern "C" size_t sph3d_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K)
 {
-    return tg_layout(nullptr, B, N, M, K, F).bytes + bwd_layout(B, N, F, C, r).bytes;
+    return tg_layout(nullptr, B, N, M, K, F).bytes + grad_t_bytes(B, N, F, C, r);
 }
 
 constexpr int kCompactBins = 17;     // accumulator rows of the compact variant
@@ -1044,6 +1237,32 @@ static int run_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int C, 
     return r == 2 ? with_r(integral_constant<int, 2>{}) : with_r(integral_constant<int, 1>{});
 }
 
+// the odd-width gradient (deterministic mode): workspace check, the sweep of the instantiation for (T, bins), then the slabs' sum
+static int run_bwd_t_odd(const OddLayout& L, int B, int N, int M, int F, int C, const int* offsets, const int* ent_key,
+                         const float* ent_scale, const int* order, const float* input, const float* filter, const float* grad_output,
+                         float* grad_input, float* grad_filter, void* workspace, size_t workspace_bytes, hipStream_t st)
+{
+    if (workspace == nullptr || workspace_bytes < L.bytes) {
+        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, L.bytes);
+        return SPH3D_EWORKSPACE;
+    }
+    const size_t lds = (size_t)F * 64 * L.T * sizeof(float);      // [F][64 T]: at most 33 x 256 or 65 x 128 floats
+    float* partial = (float*)workspace;
+    auto go = [&](auto kern) {
+        return launch_lds(kern, dim3(L.plan.slabs * L.nslices), dim3(kBwdTWaves * 64), lds, st, "conv3d", B, N, M, F, C, L.plan.W,
+                          L.plan.parts, L.nslices, offsets, ent_key, ent_scale, order, input, filter, grad_output, grad_input, partial);
+    };
+    int rc;
+    if (F <= 33) rc = L.T == 1 ? go(dwconv_bwd_t_odd<1, 33>) : L.T == 2 ? go(dwconv_bwd_t_odd<2, 33>)
+                    : L.T == 3 ? go(dwconv_bwd_t_odd<3, 33>) : go(dwconv_bwd_t_odd<4, 33>);
+    else rc = L.T == 1 ? go(dwconv_bwd_t_odd<1, 65>) : go(dwconv_bwd_t_odd<2, 65>);
+    if (rc) return rc;
+    const int total = F * C;
+    hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, L.plan.slabs, total, C, partial, grad_filter,
+                       (const int*)nullptr, 0, 0);
+    return check_launch("sph3d_depthwise_conv3d_grad_t");
+}
+
 extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, int r,
                                              const int* offsets, const int* ent_key, const float* ent_scale,
                                              const int* source_order, const int* active_bins,
@@ -1063,8 +1282,13 @@ extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, 
                              grad_input, grad_filter, workspace, workspace_bytes, st);
     // generic path (odd channel counts, other multipliers, F > 64): LDS float atomics, slow but general
     if (deterministic_on()) {
+        // odd row widths (r = 1, odd C, F <= 65): the fixed-order gather of dwconv_bwd_t_odd instead
+        const OddLayout O = odd_layout(B, N, F, C, r);
+        if (O.T && (unsigned long long)M * CR + 256ull < (1ull << 32))
+            return run_bwd_t_odd(O, B, N, M, F, C, offsets, ent_key, ent_scale, source_order, input, filter, grad_output, grad_input,
+                                 grad_filter, workspace, workspace_bytes, st);
         set_error("DepthwiseConv3dGrad: deterministic mode is on and F=%d C=%d r=%d takes the generic kernel, which sums with float "
-                  "atomics (shapes with C*r %% 4 == 0, r in {1, 2} and F <= 33 or 65 run the fixed-order kernels)", F, C, r);
+                  "atomics (shapes with r in {1, 2} and F <= 65 run the fixed-order kernels)", F, C, r);
         return SPH3D_EUNSUPPORTED;
     }
     rc = check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
@@ -1091,7 +1315,7 @@ extern "C" int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, in
     int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3dGrad");
     if (rc) return rc;
     const TgLayout t = tg_layout(workspace, B, N, M, K, F);
-    const size_t need = t.bytes + bwd_layout(B, N, F, C, r).bytes;
+    const size_t need = t.bytes + grad_t_bytes(B, N, F, C, r);
     if (B > 0 && (workspace == nullptr || workspace_bytes < need)) {
         set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, need);
         return SPH3D_EWORKSPACE;

@@ -13,7 +13,9 @@ namespace sph3d {
 constexpr unsigned long long kFeedGold = 0x9e3779b97f4a7c15ull;
 constexpr int kFeedRounds = 6;
 enum : unsigned long long { kFeedPerm = 1, kFeedRepl = 2, kFeedTurn = 3, kFeedTilt = 4, kFeedJitter = 5, kFeedScale = 6,
-                            kFeedShift = 7, kFeedIds = 8 /* + level, 0 <= level < 8: idsample.hip */ };
+                            kFeedShift = 7, kFeedIds = 8 /* + level, 0 <= level < 8: idsample.hip */,
+                            kFeedDropout = 16 /* + layer, 0 <= layer < kFeedDropoutLayers: dropout.hip */ };
+constexpr int kFeedDropoutLayers = 16;
 
 __host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long long z)
 {

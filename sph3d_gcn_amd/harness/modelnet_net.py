@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import sph3gcn_util as s3g_util
+from .. import tf_dropout
 from .s3dis_net import GraphPlan, _separable_conv3d_block
 
 
@@ -60,11 +61,16 @@ def normalize_xyz(points):
     return points / scale
 
 
-def get_model(points, is_training, config=None, dropout_generator=None, points_ready=None, sample_key=(0, 0)):
+def get_model(points, is_training, config=None, dropout_generator=None, points_ready=None, sample_key=(0, 0), dropout_key=None,
+              dropout_row0=0):
     """models/SPH3D_modelnet.py:33-107: points [B, N, 3] -> logits [B, num_cls]
     points_ready: optional event after which `points` is valid (GraphPlan: the plan of this step then overlaps the previous
     step's backward pass instead of waiting for it); sample_key: (seed, step) of the keyed inverse-density sampler
-    (config.sample == 'IDS')"""
+    (config.sample == 'IDS'); dropout_key: (seed, step) of the keyed dropout (tf_dropout.dropout_keyed: fc1_dp is layer 0, fc2_dp
+    layer 1; dropout_row0: the number of cloud 0 in the global batch) — without it the masks come from torch's global generator
+    or from dropout_generator, as before; giving both is a ValueError"""
+    if dropout_key is not None and dropout_generator is not None:
+        raise ValueError("get_model: dropout_key and dropout_generator are two sources of one mask; give one")
     batch_size, num_point = points.shape[0], points.shape[1]
     end_points = {}
     assert num_point == config.num_input
@@ -136,19 +142,22 @@ def get_model(points, is_training, config=None, dropout_generator=None, points_r
     net = net.reshape(batch_size, -1)
     net = s3g_util.fully_connected(net, 512, scope='fc1', weight_decay=config.weight_decay, with_bn=config.with_bn,
                                    with_bias=config.with_bias, is_training=is_training)
-    net = _dropout(net, 0.5, training, dropout_generator)
+    net = _dropout(net, 0.5, training, dropout_generator, dropout_key, 0, dropout_row0)
     net = s3g_util.fully_connected(net, 256, scope='fc2', weight_decay=config.weight_decay, with_bn=config.with_bn,
                                    with_bias=config.with_bias, is_training=is_training)
-    net = _dropout(net, 0.5, training, dropout_generator)
+    net = _dropout(net, 0.5, training, dropout_generator, dropout_key, 1, dropout_row0)
     net = s3g_util.fully_connected(net, config.num_cls, scope='logits', with_bn=False, with_bias=config.with_bias,
                                    activation_fn=None, is_training=is_training)
     return net, end_points
 
 
-def _dropout(x, rate, training, generator):
-    """tf.layers.dropout(rate): inverted dropout; a generator makes the mask reproducible across devices"""
+def _dropout(x, rate, training, generator, key=None, layer=0, row0=0):
+    """tf.layers.dropout(rate): inverted dropout; a generator makes the mask reproducible across devices, a key = (seed, step)
+    makes it a pure function of (seed, step, row0 + cloud, layer, element) (csrc/dropout.hip)"""
     if not training or rate <= 0.0:
         return x
+    if key is not None:
+        return tf_dropout.dropout_keyed(x, rate, key, layer, row0)
     if generator is None:
         return F.dropout(x, rate, training=True)
     keep = (torch.rand(x.shape, generator=generator) >= rate).to(device=x.device, dtype=x.dtype)
@@ -168,10 +177,11 @@ class SPH3DModelNet(torch.nn.Module):
         self.config = copy.deepcopy(config) if config is not None else modelnet_config()
         self.store = s3g_util.VariableStore(device=device, seed=seed)
 
-    def forward(self, points, is_training=True, dropout_generator=None, points_ready=None, sample_key=(0, 0)):
+    def forward(self, points, is_training=True, dropout_generator=None, points_ready=None, sample_key=(0, 0), dropout_key=None,
+                dropout_row0=0):
         with s3g_util.variable_store(self.store):
             return get_model(points, is_training, self.config, dropout_generator=dropout_generator, points_ready=points_ready,
-                             sample_key=sample_key)
+                             sample_key=sample_key, dropout_key=dropout_key, dropout_row0=dropout_row0)
 
     def loss(self, pred, label):
         """train_modelnet.py:162-164: classification loss + the weight-decay 'losses' collection + the BN regularisers

@@ -22,6 +22,7 @@ copy brings the confusion matrix, the counters, the loss sum and the optimiser's
 """
 import collections
 import contextlib
+import inspect
 import os
 import re
 
@@ -272,10 +273,14 @@ class Trainer:
     rank must then run the same layer sequence with at least one row per layer (the ranks' row counts may differ: the count
     travels in the collective's buffer).  Evaluation is inference mode and issues no collective.  deterministic: train_step,
     eval_one_epoch and fit run under sph3d_gcn_amd.deterministic() — on one rank the same seed then gives the same bits, run after
-    run and across a resume; the mode is back at its previous value when they return."""
+    run and across a resume; the mode is back at its previous value when they return.  keyed_dropout: a model
+    whose forward takes `dropout_key` (the ModelNet net) is called with dropout_key = (seed, global_step) and dropout_row0 =
+    rank * B, so its dropout masks are draws of (seed, step) like the feed's — a checkpoint holds no generator state, and only
+    then does a resumed run drop what the uninterrupted one drops; None follows `deterministic`.  Other models are called as
+    before."""
 
     def __init__(self, model, loss_fn, optimizer_factory, schedule, num_cls, line=s3dis_line, prime=None, seed=0, log_every=50,
-                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False):
+                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False, keyed_dropout=None):
         if prime is None:
             raise ValueError("Trainer: `prime` (one batch of the training shapes) is needed to create the variables")
         self.model, self.loss_fn, self.schedule, self.line = model, loss_fn, schedule, line
@@ -284,6 +289,8 @@ class Trainer:
         self.log = log
         self.sync_bn = bool(sync_bn)
         self.deterministic = bool(deterministic)
+        self.keyed_dropout = (self.deterministic if keyed_dropout is None else bool(keyed_dropout)) and \
+            "dropout_key" in inspect.signature(model.forward).parameters
         self.global_step, self.epoch = 0, -1           # updates done; the last finished epoch
         self.rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
         batch = self.line(tuple(prime))
@@ -317,7 +324,10 @@ class Trainer:
     def _forward(self, item, is_training):
         ready = item[-1]
         batch = self.line(tuple(item[:-1]))
-        pred, _ = self.model(*batch.inputs, is_training=is_training, points_ready=ready, sample_key=(self.seed, self.global_step))
+        extra = {}
+        if self.keyed_dropout:
+            extra = dict(dropout_key=(self.seed, self.global_step), dropout_row0=self.rank * batch.inputs[0].shape[0])
+        pred, _ = self.model(*batch.inputs, is_training=is_training, points_ready=ready, sample_key=(self.seed, self.global_step), **extra)
         if ready is not None and pred.is_cuda:
             torch.cuda.current_stream().wait_event(ready)       # (the loss reads the labels on this stream)
         return batch, pred, self._total_loss(pred, batch), ready

@@ -73,6 +73,10 @@ def _depthwise_conv3d_grad_impl(input: torch.Tensor, filter: torch.Tensor, grad_
     F, _, r = filter.shape
     M, K = nn_index.shape[1], nn_index.shape[2]
     pad = _channel_pad(C, r)
+    if pad and r == 1 and C % 2 == 1 and F <= 65 and _tgraph.is_deterministic():
+        # deterministic mode has a gradient kernel for odd rows (dwconv_bwd_t_odd): no padded copies, no slices (measured on
+        # the ModelNet plan, 32 clouds: C=67 0.261 -> 0.234 ms, C=131 0.128 -> 0.110 ms; tools/exp_bwd_odd.py)
+        pad = 0
     if pad:
         gi, gf = _depthwise_conv3d_grad_impl(Fn.pad(input, (0, pad)), Fn.pad(filter, (0, 0, 0, pad)),
                                              Fn.pad(grad_output, (0, pad * r)), nn_index, nn_count, bin_index)
