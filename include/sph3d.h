@@ -627,6 +627,39 @@ int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int Ca, int Cb
                                       const float* input_b, const float* filter, const float* grad_output, float* grad_a,
                                       float* grad_b, float* grad_filter, void* workspace, size_t workspace_bytes,
                                       sph3d_stream_t stream);
+/* The launch a depthwise convolution or its gradient takes, answered on the host (no device is touched): csrc/conv_plan.hpp states
+ * the choice once (conv_plan) and every entry point above launches what it says; the two workspace queries and
+ * sph3d_depthwise_conv3d_cat_supported read it.
+ *   op: SPH3D_CONV_FWD (sph3d_depthwise_conv3d), _FWD_CAT (sph3d_depthwise_conv3d_cat), _GRAD_T (sph3d_depthwise_conv3d_grad_t, and
+ *       through it sph3d_depthwise_conv3d_grad), _GRAD_T_CAT (sph3d_depthwise_conv3d_grad_t_cat)
+ *   B, N, M, F, r as that entry point takes them; Ca, Cb: the channels (one input: C and 0); K: the forward ops' (the gradients
+ *   have none: ignored);  deterministic: 0 | 1, or -1 for the current mode;  active_given: 1 if the gradient's active_bins is
+ *   not NULL (forward: ignored).  The hub hooks SPH3D_BWD_HUB_MIN_N / SPH3D_BWD_HUB_T are read as a call reads them.
+ *   out[SPH3D_CONV_PLAN_FIELDS], in this order:
+ *     0 kernel: 0 none — nothing is launched (forward: B == 0 or M == 0; gradient: B == 0, grad_filter is zero-filled) and every
+ *       field but 21 is 0;  1 dwconv_fwd_multi  2 dwconv_fwd_row  3 dwconv_fwd_generic  4 dwconv_bwd_t_vec  5 dwconv_bwd_t_odd
+ *       6 dwconv_bwd_t_generic;  7 refused — the entry point answers SPH3D_EUNSUPPORTED (a two-input shape that is not covered;
+ *       deterministic mode and a shape only dwconv_bwd_t_generic's float atomics serve) and every other field is 0
+ *     1 R (depth multiplier)   2 LPE (fwd_multi: lanes per edge, 16 for C <= 64, else 32)   3 V (bwd_vec: channels per lane, 4 or 2;
+ *     bwd_odd: T, 1 .. 4)   4 MAXF (bwd_vec, bwd_odd: bin rows of the instantiation, 33 or 65)   5 PARTS (bwd_vec: 1 full, 2 half, 4
+ *     quarter waves take alternate in-edges; bwd_odd: 1)   6 nslices (channel slices)   7 compact_launch (bwd_vec: the compact
+ *     table's sweep is launched in front of the full one; the device chooses which of them works)   8 hub (bwd_vec: the sweeps
+ *     leave hub sources to a hub launch behind each)   9 hub_threshold (in-edges above which a source is a hub; 0 without hubs)
+ *     10 11 12 the full table: parts (position ranges per cloud), W (workgroups per XCD and slice), slabs (8 W)
+ *     13 14 15 the compact table (bwd_vec)   16 reduce_slabs, 17 reduce_slabs_compact (the slab counts reduce_filter_partials is told
+ *     for a full and for a compact run; 0: no reduce launch)   18 lds (dynamic LDS bytes of the main launch)   19 grid (its
+ *     workgroups: fwd_*, bwd_generic, the full table's sweep)   20 hub_list_offset (bwd_vec: bytes from the workspace's start)
+ *     21 workspace_bytes (gradient: sph3d_depthwise_conv3d_grad_t_workspace() for the shape, which asks with M = 0)
+ *   The forward takes the first of multi, row, generic whose shape conditions hold and whose filter table fits 160 KiB of LDS.
+ * -> SPH3D_OK (also for kernel 7), or SPH3D_EINVAL for an unknown op, a flag outside the above, Cb != 0 with a one-input op,
+ *    out == NULL, or dimensions the entry point itself rejects. */
+#define SPH3D_CONV_FWD 0
+#define SPH3D_CONV_FWD_CAT 1
+#define SPH3D_CONV_GRAD_T 2
+#define SPH3D_CONV_GRAD_T_CAT 3
+#define SPH3D_CONV_PLAN_FIELDS 22
+int sph3d_depthwise_conv3d_plan(int op, int B, int N, int M, int F, int Ca, int Cb, int r, int K, int deterministic, int active_given,
+                                long long* out);
 
 /* ---- the training loop's optimiser update (train_s3dis.py:224, tf.train.AdamOptimizer) over flat fp32 buffers: one streaming
  * pass, torch.optim.Adam's arithmetic (no amsgrad / weight decay); step = 1, 2, ... (bias corrections are computed on the host) */

@@ -62,6 +62,7 @@ SIGNATURES = {
     "sph3d_depthwise_conv3d_cat_supported": (_I, [_I] * 4),
     "sph3d_depthwise_conv3d_cat": (_I, [_I] * 8 + [_P] * 8),
     "sph3d_depthwise_conv3d_grad_t_cat": (_I, [_I] * 7 + [_P] * 12 + [_P, _S, _P]),
+    "sph3d_depthwise_conv3d_plan": (_I, [_I] * 11 + [_P]),
     "sph3d_spatial_order": (_I, [_I, _I, _P, _P, _P]),
     "sph3d_scatter_grad_t": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_scatter_grad_workspace": (_S, [_I] * 4),
@@ -204,7 +205,7 @@ def timing_stop():
 
 
 _PURE = ("_workspace", "_blocks", "_supported", "_parts", "_sample_chunk")
-_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_sample_chunk")
+_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_sample_chunk", "_plan")
 
 
 class _Proxy:

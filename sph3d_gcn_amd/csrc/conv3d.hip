@@ -23,16 +23,19 @@
 //     (N*C*4 B, 4 MiB at N=8192,C=128) stay in that XCD's 4 MiB L2.
 //   * Numerics: sum_k in*filt in fp32 FMA order k = 0..cnt-1, one division by cnt at the end (the
 //     reference divides every term); agreement with the oracle is ~1e-7 relative, bound 1e-5.
+//   * The host decides nothing here: which kernel, which instantiation, grid, LDS bytes, sweep tables, hub and compact launches
+//     and the workspace are conv_plan.hpp's conv_plan(), one pure function for the four ops (forward and transposed gradient,
+//     over one input or two).  The entry points at the end of this file launch what it says; sph3d_depthwise_conv3d_plan
+//     reports it.
+#include <stddef.h>
+#include <string.h>
 #include <type_traits>
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace sph3d {
 
-constexpr int kSlice = 256;       // output channels per wave pass (64 lanes x 4)
-constexpr int kFwdPointsPerWG = 32;
 constexpr int kFwdSB = 4;              // dwconv_fwd_multi: wave loads (each EPL neighbour rows) issued together
-constexpr int kMultiWaves = 4;                        // dwconv_fwd_multi: waves per workgroup (they share one LDS filter table)
-constexpr int kMultiPoints = 8 * kMultiWaves;         // output points per workgroup
 constexpr int kBatch = 8;               // dwconv_fwd_row: neighbours whose gathers are issued together
 
 // ------------------------------------------------------------------------------------------
@@ -371,8 +374,6 @@ __global__ __launch_bounds__(256) void dwconv_fwd_generic(
 // Edges are consumed four at a time: four scalar key loads and four independent row gathers are issued before
 // any is used (memory-level parallelism; the kernel is latency-bound at 2 waves/SIMD otherwise).
 // ------------------------------------------------------------------------------------------
-constexpr int kBwdTWaves = 4;
-constexpr int kBwdTPointsPerWG = 64;     // measured: 256 -> 1.90 ms, 128 -> 1.15, 64 -> 0.90, 32 -> 0.91, 16 -> 1.22 (tail / balance vs per-block setup)
 
 constexpr int kBwdNL2 = 3;     // wave loads per batch of the half-wave form (2 edges per load)
 constexpr int kBwdNL4 = 2;     // ... of the quarter-wave form (4 edges per load)
@@ -396,7 +397,6 @@ constexpr int kBwdNL4 = 2;     // ... of the quarter-wave form (4 edges per load
 //            entries already is not) and keep the filter gradient in their accumulators like every other wave: slabs
 //            slabBase .. slabBase + hubW - 1 of `partial`.
 //   HUB = 0 (every other launch, the headline's among them): neither — the instantiations of rounds 1-5, unchanged.
-constexpr int kHubGroup = 8;
 template <int R, int V, int MAXF, int PARTS, bool COMPACT, int HUB = 0>
 __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t_vec(
     int B, int N, int M, int F, int C, int W, int parts, int nslices,
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_t_generic(
 // no lane can load two or four channels at once; lane l owns channels slice0 + l + 64 t, t < T (the generic kernels' ownership),
 // and a row gather is T dword loads, each coalesced on any alignment, with the lanes past the row's end reading the slice's first
 // column.  T <= 4 for F <= 33 and T <= 2 for F <= 65: at most 132 accumulator registers, as the V = 4 form.
-// The partition is bwd_plan's static one (W workgroups per XCD and slice, (cloud, part) items dealt to the XCDs, positions of
+// The partition is conv_table's static one (conv_plan.hpp; W workgroups per XCD and slice, (cloud, part) items dealt to the XCDs, positions of
 // source_order interleaved over the waves): no work cursor, no hub launches, no atomics of any kind, so every slab is a function
 // of the shape, the graph and the order alone.
 // ------------------------------------------------------------------------------------------
@@ -971,46 +971,71 @@ __global__ __launch_bounds__(kBwdTWaves * 64, 3) void dwconv_bwd_t_odd(
     }
 }
 
-static int conv_dims_ok(int B, int N, int M, int F, int C, int r, int K, const char* who)
-{
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && F > 0 && C > 0 && r > 0 && K > 0,
-                  "%s: bad dims B=%d N=%d M=%d F=%d C=%d r=%d K=%d", who, B, N, M, F, C, r, K);
-    const size_t slice = (size_t)(C * r < kSlice ? C * r : kSlice);
-    SPH3D_REQUIRE((size_t)F * slice * sizeof(float) <= 160 * 1024,
-                  "%s: filter table slice F=%d does not fit LDS", who, F);
-    return SPH3D_OK;
-}
-
 }  // namespace sph3d
 
 using namespace sph3d;
 
-// dwconv_fwd_row over 256-output slices; input2 / Ca: the second tensor of a channel concatenation (sph3d_depthwise_conv3d_cat)
-static int launch_fwd_row(int B, int N, int M, int F, int C, int r, int K, const int* nn_index, const int* nn_count,
-                          const int* bin_index, const float* input, const float* filter, float* output, const float* input2, int Ca,
-                          hipStream_t st)
+// ---- the host side --------------------------------------------------------------------------------------------------------------
+// Every entry point asks conv_plan.hpp for the plan of its call and launches what the plan says; the checks they share (the
+// dimensions, the refusals, the workspace) are written once each.  The templates are chosen by switches on plan fields.
+struct ConvShape {
+    int op, B, N, M, F, Ca, Cb, r, K;       // K: the gradient entries have none and say 1
+};
+
+// Test hooks SPH3D_BWD_HUB_MIN_N / SPH3D_BWD_HUB_T: read per call
+static int hub_min_n() { return test_hook("SPH3D_BWD_HUB_MIN_N", 32768); }
+static int hub_threshold() { const int t = test_hook("SPH3D_BWD_HUB_T", 1024); return t < 1 ? 1 : t; }
+
+static ConvPlan plan_of(const ConvShape& s, bool active_given, bool deterministic = deterministic_on())
 {
-    const int CR = C * r;
-    const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
-    const int nslices = (CR + kSlice - 1) / kSlice;
-    const int SLmax = CR < kSlice ? CR : kSlice;
-    const size_t lds = (size_t)(F + 1) * SLmax * sizeof(float);      // + the zero row of the padding slots
-    return launch_lds(r == 2 ? dwconv_fwd_row<2> : dwconv_fwd_row<1>, dim3(xcd_grid(B, mblocks * nslices)), dim3(256), lds, st, "conv3d",
-                      B, N, M, F, C, K, mblocks, nslices, nn_index, nn_count, bin_index, input, filter, output, input2, Ca);
+    const bool grad = s.op == kConvGradT || s.op == kConvGradTCat;
+    return conv_plan(s.op, s.B, s.N, s.M, s.F, s.Ca, s.Cb, s.r, s.K, deterministic, active_given, grad ? hub_min_n() : 0,
+                     grad ? hub_threshold() : 0);
 }
 
-extern "C" int sph3d_depthwise_conv3d(int B, int N, int M, int F, int C, int r, int K,
-                                      const int* nn_index, const int* nn_count, const int* bin_index,
-                                      const float* input, const float* filter, float* output,
-                                      sph3d_stream_t stream)
+// the entry point's answer where the plan already is one: SPH3D_EINVAL, SPH3D_EUNSUPPORTED.  SPH3D_OK: launch (kernel none: nothing)
+static int plan_status(const ConvPlan& p, const ConvShape& s)
 {
-    int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3d");
-    if (rc) return rc;
-    if (B == 0 || M == 0) return SPH3D_OK;
+    const bool grad = s.op == kConvGradT || s.op == kConvGradTCat, cat = s.op == kConvFwdCat || s.op == kConvGradTCat;
+    const char* who = grad ? "DepthwiseConv3dGrad" : "DepthwiseConv3d";
+    const long long C = (long long)s.Ca + s.Cb;
+    SPH3D_REQUIRE(p.bad != kConvBadDims, "%s: bad dims B=%d N=%d M=%d F=%d C=%lld r=%d K=%d", who, s.B, s.N, s.M, s.F, C, s.r, s.K);
+    SPH3D_REQUIRE(p.bad != kConvBadLds, "%s: filter table slice F=%d does not fit LDS", who, s.F);
+    SPH3D_REQUIRE(p.bad != kConvBadMultiplier, "%s: depth multiplier %d > 256 unsupported", who, s.r);
+    SPH3D_REQUIRE(p.bad != kConvBadGrid, "%s: B=%d N=%d M=%d C=%lld r=%d is more than 2^31 - 1 workgroups", who, s.B, s.N, s.M, C, s.r);
+    if (p.kernel != kConvRefused) return SPH3D_OK;
+    if (cat)
+        set_error("%s (two inputs): Ca=%d Cb=%d r=%d not covered (Ca*r must be a multiple of 256)", who, s.Ca, s.Cb, s.r);
+    else
+        set_error("DepthwiseConv3dGrad: deterministic mode is on and F=%d C=%lld r=%d takes the generic kernel, which sums with float "
+                  "atomics (shapes with r in {1, 2} and F <= 65 run the fixed-order kernels)", s.F, C, s.r);
+    return SPH3D_EUNSUPPORTED;
+}
+
+static int workspace_status(const void* workspace, size_t have, size_t need)
+{
+    if (need == 0 || (workspace != nullptr && have >= need)) return SPH3D_OK;
+    set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", have, need);
+    return SPH3D_EWORKSPACE;
+}
+
+// ---- forward: one input, or (input2) the channel concatenation [input (Ca) | input2 (Cb)] that is never materialised ----------
+// (models/SPH3D_s3dis.py:100-104: tf.concat of the un-pooled features and the encoder's skip features feeds the next decoder
+// level's separable convolution).  Channel slices of the row kernel are 256 outputs = 256 / r inputs wide; Ca * r must be a
+// multiple of 256 so that every slice reads one tensor.  Other shapes: SPH3D_EUNSUPPORTED (concatenate and call the plain ops).
+static int run_fwd(const ConvShape& s, const int* nn_index, const int* nn_count, const int* bin_index, const float* input,
+                   const float* input2, const float* filter, float* output, sph3d_stream_t stream, const char* what)
+{
+    const ConvPlan p = plan_of(s, false);
+    int rc = plan_status(p, s);
+    if (rc || p.kernel == kConvNone) return rc;
     hipStream_t st = as_stream(stream);
-    const bool vec = (C % 4 == 0) && (r == 1 || r == 2);
-    const bool multi_ok = vec && N <= (1 << 24) && F <= 254 && (unsigned long long)N * C * 4ull + 1024ull < (1ull << 32);
-    if (multi_ok && C <= 128) {
+    const int B = s.B, N = s.N, M = s.M, F = s.F, C = s.Ca + s.Cb, r = s.r, K = s.K, nslices = (int)p.nslices;
+    static_assert(kMultiPoints == kFwdPointsPerWG, "one mblocks for the three kernels");
+    const int mblocks = (int)((M + (long long)kFwdPointsPerWG - 1) / kFwdPointsPerWG);
+    const dim3 grid((unsigned)p.grid);
+    const size_t lds = (size_t)p.lds;
+    if (p.kernel == kConvFwdMulti) {
         // 65..128 channels: 32 lanes per edge, TWO neighbour rows per wave load.  (Round 1 had measured this shape slower than one
         // row per load, 0.353 vs 0.297 ms at C = 128; with the zero-row padding and vector-side offsets of round 2 it is
         // 0.202 vs 0.240 ms = 16.6 % of the roofline, ahead of the LDS-tiled kernel and without a plan.  64 lanes per edge for
@@ -1018,177 +1043,78 @@ extern "C" int sph3d_depthwise_conv3d(int B, int N, int M, int F, int C, int r, 
         // stays behind the row kernel: 0.069 vs 0.060 ms at 2048 x 256.)
         // narrow layers (C <= 64): 16 lanes per edge, four neighbour rows per wave load (measured at C = 64, r = 2:
         // 0.254 -> 0.145 ms; at C >= 128 the one-edge-per-load kernel below is faster: 0.297 vs 0.353 ms with two edges per load)
-        const bool wide = C > 64;
-        auto kern = wide ? (r == 2 ? dwconv_fwd_multi<2, 32, kFwdSB> : dwconv_fwd_multi<1, 32, kFwdSB>)
-                         : (r == 2 ? dwconv_fwd_multi<2, 16, kFwdSB> : dwconv_fwd_multi<1, 16, kFwdSB>);
-        const int mmblocks = (M + kMultiPoints - 1) / kMultiPoints;
-        const size_t lds = (size_t)(F + 1) * (wide ? 128 : 64) * r * sizeof(float);   // + the zero row of the padding slots; rows of 128 * r or 64 * r
-        rc = launch_lds(kern, dim3(xcd_grid(B, mmblocks)), dim3(64 * kMultiWaves), lds, st, "conv3d", B, N, M, F, C, K, mmblocks,
-                        /*nslices=*/1, nn_index, nn_count, bin_index, input, filter, output);
-    } else if (vec && (unsigned long long)N * C + 256ull < (1ull << 32)) {       // (32-bit row offsets in the kernel)
-        rc = launch_fwd_row(B, N, M, F, C, r, K, nn_index, nn_count, bin_index, input, filter, output, nullptr, 0, st);
+        auto kern = p.LPE == 32 ? (p.R == 2 ? dwconv_fwd_multi<2, 32, kFwdSB> : dwconv_fwd_multi<1, 32, kFwdSB>)
+                                : (p.R == 2 ? dwconv_fwd_multi<2, 16, kFwdSB> : dwconv_fwd_multi<1, 16, kFwdSB>);
+        rc = launch_lds(kern, grid, dim3(64 * kMultiWaves), lds, st, "conv3d", B, N, M, F, C, K, mblocks, nslices, nn_index, nn_count,
+                        bin_index, input, filter, output);
+    } else if (p.kernel == kConvFwdRow) {
+        rc = launch_lds(p.R == 2 ? dwconv_fwd_row<2> : dwconv_fwd_row<1>, grid, dim3(256), lds, st, "conv3d", B, N, M, F, C, K, mblocks,
+                        nslices, nn_index, nn_count, bin_index, input, filter, output, input2, s.op == kConvFwdCat ? s.Ca : 0);
     } else {
-        const int CR = C * r;
-        const int mblocks = (M + kFwdPointsPerWG - 1) / kFwdPointsPerWG;
-        const int nslices = (CR + kSlice - 1) / kSlice;
-        const int SLmax = CR < kSlice ? CR : kSlice;
-        const size_t lds = (size_t)F * SLmax * sizeof(float);
-        rc = launch_lds(dwconv_fwd_generic, dim3(xcd_grid(B, mblocks * nslices)), dim3(256), lds, st, "conv3d", B, N, M, F, C, r, K,
-                        mblocks, nslices, nn_index, nn_count, bin_index, input, filter, output);
+        rc = launch_lds(dwconv_fwd_generic, grid, dim3(256), lds, st, "conv3d", B, N, M, F, C, r, K, mblocks, nslices, nn_index, nn_count,
+                        bin_index, input, filter, output);
     }
     if (rc) return rc;
-    return check_launch("sph3d_depthwise_conv3d");
+    return check_launch(what);
 }
 
-static int vec_plan(int F, int CR, int r, int& V)
+extern "C" int sph3d_depthwise_conv3d(int B, int N, int M, int F, int C, int r, int K,
+                                      const int* nn_index, const int* nn_count, const int* bin_index,
+                                      const float* input, const float* filter, float* output,
+                                      sph3d_stream_t stream)
 {
-    if (!(r == 1 || r == 2)) return 0;
-    if (F <= 33 && CR % 4 == 0) { V = 4; return 1; }
-    if (F <= 65 && CR % 2 == 0) { V = 2; return 1; }
-    return 0;
+    return run_fwd({kConvFwd, B, N, M, F, C, 0, r, K}, nn_index, nn_count, bin_index, input, nullptr, filter, output, stream,
+                   "sph3d_depthwise_conv3d");
 }
 
-// persistent-sweep plan of dwconv_bwd_t_vec: `parts` position ranges per cloud so that (cloud, part) items divide
-// evenly over the 8 XCDs, and W workgroups per XCD and channel slice:
-//   * large levels: ~64 sources per workgroup (per-workgroup cost: one F x CR partial table), at most 3 per CU;
-//   * small levels (N = 128..768: the whole launch is a few hundred sources per XCD): the kernel is a chain of
-//     dependent gathers per source, so the sources are spread over enough workgroups to put two on every CU
-//     (down to 2 sources per wave) instead of leaving most CUs idle.
-constexpr int kBwdFillWG = 128;   // workgroups per XCD that a small level is spread over (compact kernel: 4 fit a CU)
-struct BwdTable {
-    int parts, W;      // position ranges per cloud; workgroups per XCD and channel slice
-    int slabs;         // 8 * W partial tables, one per workgroup of a slice; the hub launch's kHubWG slabs follow them
+extern "C" int sph3d_depthwise_conv3d_cat(int B, int N, int M, int F, int Ca, int Cb, int r, int K, const int* nn_index,
+                                          const int* nn_count, const int* bin_index, const float* input_a, const float* input_b,
+                                          const float* filter, float* output, sph3d_stream_t stream)
+{
+    return run_fwd({kConvFwdCat, B, N, M, F, Ca, Cb, r, K}, nn_index, nn_count, bin_index, input_a, input_b, filter, output, stream,
+                   "sph3d_depthwise_conv3d_cat");
+}
+
+extern "C" int sph3d_depthwise_conv3d_cat_supported(int F, int Ca, int Cb, int r)
+{
+    return plan_of({kConvFwdCat, 1, 1, 1, F, Ca, Cb, r, 1}, false).kernel == kConvFwdRow;       // (a shape question: one point)
+}
+
+// ---- gradient over the transposed graph: one input, or (input2, grad_input2) two ---------------------------------------------------
+struct GradArgs {
+    const int *offsets, *ent_key;
+    const float* ent_scale;
+    const int *order, *active_bins;
+    const float *input, *input2, *filter, *grad_output;
+    float *grad_input, *grad_input2, *grad_filter;
+    void* workspace;
 };
-static BwdTable bwd_plan(int B, int N, int nslices, int wg_per_cu)
-{
-    BwdTable t;
-    int g = B & 7;                         // gcd(B, 8)
-    g = g == 0 ? 8 : (g & -g);
-    t.parts = 8 / g;
-    if (t.parts > N) t.parts = 1;
-    const long long items_per_xcd = ((long long)B * t.parts + 7) / 8;
-    const long long src = items_per_xcd * ((N + t.parts - 1) / t.parts);
-    const long long w_work = (src + kBwdTPointsPerWG - 1) / kBwdTPointsPerWG;
-    long long w_fill = (wg_per_cu >= 4 ? kBwdFillWG : 64) / (nslices < 1 ? 1 : nslices);
-    if (w_fill < 1) w_fill = 1;
-    const long long w_min = (src + 2 * kBwdTWaves - 1) / (2 * kBwdTWaves);
-    long long w = w_fill < w_min ? w_fill : w_min;
-    if (w < w_work) w = w_work;
-    const long long cap = 32LL * wg_per_cu;
-    t.W = (int)(w < 1 ? 1 : (w > cap ? cap : w));
-    t.slabs = 8 * t.W;
-    return t;
-}
 
-// hub sources (dwconv_bwd_t_vec<..., HUB>): clouds of at least 32 768 points (measured: at 16 384 the two extra launches cost more
-// than the few hubs of that level give back, profiles/r06_ab_conv_hub.log), sources with more than 1024 in-edges; kHubWG
-// workgroups per channel slice in the hub launch.  Test hooks SPH3D_BWD_HUB_MIN_N / SPH3D_BWD_HUB_T: read per call
-constexpr int kHubWG = 1024;       // workgroups of the hub launch (a multiple of kHubGroup) = slabs reserved for it
-static_assert(kHubWG % kHubGroup == 0, "hub workgroups come in groups of kHubGroup");
-static int hub_min_n() { return test_hook("SPH3D_BWD_HUB_MIN_N", 32768); }
-static int hub_threshold() { const int t = test_hook("SPH3D_BWD_HUB_T", 1024); return t < 1 ? 1 : t; }
-
-// The vector gradient's launch plan and workspace: the slabs of F x CR partial filter gradients, then the hub list.  A call
-// runs the full table's launches, the compact table's, or both (the device chooses, see the kernel); both write slabs 0 ..,
-// so the slab area holds the larger of the two plans and the hub launch's kHubWG slabs behind either.  Nothing here depends
-// on the per-call switches: a workspace sized once serves every call of the shape.
-struct BwdLayout {
-    int V;                     // channels per lane (vec_plan); 0: the shape takes the generic kernel, no workspace
-    int nslices;               // channel slices of 64 * V outputs
-    BwdTable full, compact;    // 3 and 4 workgroups per CU
-    size_t hub_list_offset;    // bytes from the workspace's start to the hub list [count, b * N + n ...]
-    size_t bytes;
-};
-static BwdLayout bwd_layout(int B, int N, int F, int C, int r)
-{
-    BwdLayout L = {};
-    if (!vec_plan(F, C * r, r, L.V)) return L;
-    L.nslices = (C * r + 64 * L.V - 1) / (64 * L.V);
-    L.full = bwd_plan(B, N, L.nslices, 3);
-    L.compact = bwd_plan(B, N, L.nslices, 4);
-    const size_t slabs = (size_t)(L.full.slabs > L.compact.slabs ? L.full.slabs : L.compact.slabs) + kHubWG;
-    L.hub_list_offset = sizeof(float) * slabs * F * C * r;
-    L.bytes = L.hub_list_offset + sizeof(int) * ((size_t)B * N + 4);
-    return L;
-}
-
-// The odd-width gradient's plan (dwconv_bwd_t_odd, deterministic mode only): r = 1 and odd C — with r in {1, 2} every other row
-// width is even and has a vec_plan.  T channels per lane: as many as the row needs, at most 4 (F <= 33) or 2 (F <= 65); wider
-// rows take several slices of 64 T channels.  The sweep is bwd_plan's at 3 workgroups per CU; the workspace is its slabs alone.
-struct OddLayout {
-    int T;             // 0: not an odd-width shape
-    int nslices;
-    BwdTable plan;
-    size_t bytes;
-};
-static OddLayout odd_layout(int B, int N, int F, int C, int r)
-{
-    OddLayout L = {};
-    if (r != 1 || C % 2 == 0 || F > 65) return L;
-    const int tmax = F <= 33 ? 4 : 2;
-    const int need = (C + 63) / 64;
-    L.T = need < tmax ? need : tmax;
-    L.nslices = (C + 64 * L.T - 1) / (64 * L.T);
-    L.plan = bwd_plan(B, N, L.nslices, 3);
-    L.bytes = sizeof(float) * (size_t)L.plan.slabs * F * C;
-    return L;
-}
-
-// bytes of the gradient's own workspace: the vector plan's; in deterministic mode the odd-width plan's for the shapes it serves;
-// 0 for what takes the generic kernel
-static size_t grad_t_bytes(int B, int N, int F, int C, int r)
-{
-    const BwdLayout L = bwd_layout(B, N, F, C, r);
-    if (L.V == 0 && deterministic_on()) return odd_layout(B, N, F, C, r).bytes;
-    return L.bytes;
-}
-
-extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r) { return grad_t_bytes(B, N, F, C, r); }
-extern "C" size_t sph3d_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K)
-{
-    return tg_layout(nullptr, B, N, M, K, F).bytes + grad_t_bytes(B, N, F, C, r);
-}
-
-constexpr int kCompactBins = 17;     // accumulator rows of the compact variant
-
+// the vector gradient's launches: the compact table's sweep (if the plan says so) and the full table's — the device chooses which
+// of the two does the work, see the kernel —, each with its hub launch behind it when hubs apply.  ab: active_bins for the kernels
 template <int R, int V, int MAXF, int PARTS>
-static int launch_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int C, const int* offsets, const int* ent_key,
-                            const float* ent_scale, const int* order, const int* active_bins, const float* input,
-                            const float* filter, const float* grad_output, float* grad_input, float* grad_filter,
-                            void* workspace, hipStream_t st, const float* input2, float* grad_input2, int Ca)
+static int launch_bwd_t_vec(const ConvPlan& p, const ConvShape& s, const GradArgs& a, const int* ab, hipStream_t st)
 {
-    const int CR = C * R;
-    const int SLmax = CR < 64 * V ? CR : 64 * V;
-    const size_t lds = (size_t)F * SLmax * sizeof(float);
-    const int total = F * CR;
-    float* partial = (float*)workspace;
-    // the compact launch exists for the 4-channels-per-lane plans with at most 63 bins (one register of segment bounds)
-    const bool compact = active_bins != nullptr && V == 4 && MAXF > kCompactBins && F <= 63;
-    const int* ab = compact ? active_bins : nullptr;
-    // big clouds: hub sources are left out of the sweep and shared among the waves of the hub launch (see the kernel)
-    // (deterministic mode: never — the hub list is appended with an atomic and the hub launch adds its grad_input sums with float
-    // atomics; the sweep alone takes every source, its static partition and reduce_filter_partials sum in a fixed order)
-    const bool hubs = V == 4 && !deterministic_on() && N >= hub_min_n();
+    const int C = s.Ca + s.Cb, nslices = (int)p.nslices, T = (int)p.hub_threshold;
     int* hub_list = nullptr;
-    int T = 0;
-    if (hubs) {
-        hub_list = reinterpret_cast<int*>((char*)workspace + L.hub_list_offset);
+    if (p.hub) {
+        hub_list = reinterpret_cast<int*>((char*)a.workspace + p.hub_list_offset);
         int rc = check_hip(hipMemsetAsync(hub_list, 0, sizeof(int), st), "conv3d grad: hub list");
         if (rc) return rc;
-        T = hub_threshold();
     }
     // one launch: `wgs` workgroups per slice, W of them per XCD (the hub launch: W = wgs in all)
-    auto launch = [&](auto kern, int wgs, int W, int parts, int slab_base) {
-        return launch_lds(kern, dim3(wgs * L.nslices), dim3(kBwdTWaves * 64), lds, st, "conv3d", B, N, M, F, C, W, parts, L.nslices,
-                          offsets, ent_key, ent_scale, order, ab, kCompactBins, input, filter, grad_output, grad_input, partial,
-                          input2, grad_input2, Ca, hub_list, T, slab_base);
+    auto launch = [&](auto kern, long long wgs, long long W, long long parts, long long slab_base) {
+        return launch_lds(kern, dim3((unsigned)(wgs * nslices)), dim3(kBwdTWaves * 64), (size_t)p.lds, st, "conv3d", s.B, s.N, s.M, s.F, C,
+                          (int)W, (int)parts, nslices, a.offsets, a.ent_key, a.ent_scale, a.order, ab, kCompactBins, a.input, a.filter,
+                          a.grad_output, a.grad_input, (float*)a.workspace, a.input2, a.grad_input2, s.op == kConvGradTCat ? s.Ca : 0,
+                          hub_list, T, (int)slab_base);
     };
     // one table's sweep over all sources and, when hubs apply, the hub launch behind it (HUB = 1, 2 exist for V == 4 only)
-    auto sweep = [&](auto compact_table, const BwdTable& t) {
+    auto sweep = [&](auto compact_table, const ConvTable& t) {
         constexpr bool CT = decltype(compact_table)::value;
         constexpr int MF = CT ? kCompactBins : MAXF;
         if constexpr (V == 4) {
-            if (hubs) {
+            if (p.hub) {
                 int rc = launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 1>, t.slabs, t.W, t.parts, 0);
                 if (rc) return rc;
                 return launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 2>, kHubWG, kHubWG, 1, t.slabs);
@@ -1196,70 +1122,74 @@ static int launch_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int 
         }
         return launch(dwconv_bwd_t_vec<R, V, MF, PARTS, CT, 0>, t.slabs, t.W, t.parts, 0);
     };
-    int rc = SPH3D_OK;
     if constexpr (V == 4) {
-        if (compact) rc = sweep(std::true_type{}, L.compact);
+        if (p.compact_launch) {
+            int rc = sweep(std::true_type{}, p.compact);
+            if (rc) return rc;
+        }
     }
-    if (rc == SPH3D_OK) rc = sweep(std::false_type{}, L.full);
-    if (rc) return rc;
-    const int hub_slabs = hubs ? kHubWG : 0;
-    hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, L.full.slabs + hub_slabs, total, CR, partial,
-                       grad_filter, ab, kCompactBins, (compact ? L.compact.slabs : 0) + hub_slabs);
-    return check_launch("sph3d_depthwise_conv3d_grad_t");
+    return sweep(std::false_type{}, p.full);
 }
 
-// the vector gradient of one or (input2: sph3d_depthwise_conv3d_grad_t_cat) two inputs: workspace check, then the instantiation
-// for the depth multiplier, the channels per lane and the row width
-static int run_bwd_t_vec(const BwdLayout& L, int B, int N, int M, int F, int C, int r, const int* offsets, const int* ent_key,
-                         const float* ent_scale, const int* order, const int* active_bins, const float* input, const float* filter,
-                         const float* grad_output, float* grad_input, float* grad_filter, void* workspace, size_t workspace_bytes,
-                         hipStream_t st, const float* input2 = nullptr, float* grad_input2 = nullptr, int Ca = 0)
+// the instantiation for the plan's depth multiplier, channels per lane (with them the row count) and wave parts
+static int run_bwd_t_vec(const ConvPlan& p, const ConvShape& s, const GradArgs& a, const int* ab, hipStream_t st)
 {
-    if (workspace == nullptr || workspace_bytes < L.bytes) {
-        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, L.bytes);
-        return SPH3D_EWORKSPACE;
-    }
-    auto go = [&](auto R, auto V, auto PARTS) {
-        return launch_bwd_t_vec<R(), V(), (V() == 4 ? 33 : 65), PARTS()>(L, B, N, M, F, C, offsets, ent_key, ent_scale, order, active_bins,
-                                                                       input, filter, grad_output, grad_input, grad_filter,
-                                                                       workspace, st, input2, grad_input2, Ca);
-    };
     using std::integral_constant;
+    auto go = [&](auto R, auto V, auto PARTS) { return launch_bwd_t_vec<R(), V(), (V() == 4 ? 33 : 65), PARTS()>(p, s, a, ab, st); };
     auto with_r = [&](auto R) {
-        const int CR = C * r;
-        if (L.V == 2) return go(R, integral_constant<int, 2>{}, integral_constant<int, 1>{});
-        // rows of at most 128 (64) outputs: two half (four quarter) waves take alternate edges; a narrower row leaves lanes of
-        // each part idle, but fewer than the full-wave form would (the ModelNet plan's 36-, 64- and 68-channel layers)
-        if (CR <= 64) return go(R, integral_constant<int, 4>{}, integral_constant<int, 4>{});
-        if (CR <= 128) return go(R, integral_constant<int, 4>{}, integral_constant<int, 2>{});
+        if (p.V == 2) return go(R, integral_constant<int, 2>{}, integral_constant<int, 1>{});
+        if (p.PARTS == 4) return go(R, integral_constant<int, 4>{}, integral_constant<int, 4>{});
+        if (p.PARTS == 2) return go(R, integral_constant<int, 4>{}, integral_constant<int, 2>{});
         return go(R, integral_constant<int, 4>{}, integral_constant<int, 1>{});
     };
-    return r == 2 ? with_r(integral_constant<int, 2>{}) : with_r(integral_constant<int, 1>{});
+    return p.R == 2 ? with_r(integral_constant<int, 2>{}) : with_r(integral_constant<int, 1>{});
 }
 
-// the odd-width gradient (deterministic mode): workspace check, the sweep of the instantiation for (T, bins), then the slabs' sum
-static int run_bwd_t_odd(const OddLayout& L, int B, int N, int M, int F, int C, const int* offsets, const int* ent_key,
-                         const float* ent_scale, const int* order, const float* input, const float* filter, const float* grad_output,
-                         float* grad_input, float* grad_filter, void* workspace, size_t workspace_bytes, hipStream_t st)
+// the odd-width gradient (deterministic mode): the sweep of the instantiation for (T, rows)
+static int run_bwd_t_odd(const ConvPlan& p, const ConvShape& s, const GradArgs& a, hipStream_t st)
 {
-    if (workspace == nullptr || workspace_bytes < L.bytes) {
-        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, L.bytes);
-        return SPH3D_EWORKSPACE;
-    }
-    const size_t lds = (size_t)F * 64 * L.T * sizeof(float);      // [F][64 T]: at most 33 x 256 or 65 x 128 floats
-    float* partial = (float*)workspace;
     auto go = [&](auto kern) {
-        return launch_lds(kern, dim3(L.plan.slabs * L.nslices), dim3(kBwdTWaves * 64), lds, st, "conv3d", B, N, M, F, C, L.plan.W,
-                          L.plan.parts, L.nslices, offsets, ent_key, ent_scale, order, input, filter, grad_output, grad_input, partial);
+        return launch_lds(kern, dim3((unsigned)p.grid), dim3(kBwdTWaves * 64), (size_t)p.lds, st, "conv3d", s.B, s.N, s.M, s.F, s.Ca,
+                          (int)p.full.W, (int)p.full.parts, (int)p.nslices, a.offsets, a.ent_key, a.ent_scale, a.order, a.input, a.filter,
+                          a.grad_output, a.grad_input, (float*)a.workspace);
     };
-    int rc;
-    if (F <= 33) rc = L.T == 1 ? go(dwconv_bwd_t_odd<1, 33>) : L.T == 2 ? go(dwconv_bwd_t_odd<2, 33>)
-                    : L.T == 3 ? go(dwconv_bwd_t_odd<3, 33>) : go(dwconv_bwd_t_odd<4, 33>);
-    else rc = L.T == 1 ? go(dwconv_bwd_t_odd<1, 65>) : go(dwconv_bwd_t_odd<2, 65>);
+    const int T = (int)p.V;
+    if (p.MAXF == 33) return T == 1 ? go(dwconv_bwd_t_odd<1, 33>) : T == 2 ? go(dwconv_bwd_t_odd<2, 33>)
+                           : T == 3 ? go(dwconv_bwd_t_odd<3, 33>) : go(dwconv_bwd_t_odd<4, 33>);
+    return T == 1 ? go(dwconv_bwd_t_odd<1, 65>) : go(dwconv_bwd_t_odd<2, 65>);
+}
+
+static int run_grad_t(const ConvShape& s, const GradArgs& a, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    const ConvPlan p = plan_of(s, a.active_bins != nullptr);
+    int rc = plan_status(p, s);
     if (rc) return rc;
-    const int total = F * C;
-    hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, L.plan.slabs, total, C, partial, grad_filter,
-                       (const int*)nullptr, 0, 0);
+    hipStream_t st = as_stream(stream);
+    const int C = s.Ca + s.Cb, CR = C * s.r, total = s.F * CR;
+    // no cloud: grad_filter is all there is to write; the generic kernel adds into it with atomics
+    if (p.kernel == kConvNone || p.kernel == kConvBwdGeneric) {
+        rc = check_hip(hipMemsetAsync(a.grad_filter, 0, sizeof(float) * (size_t)total, st), "conv3d grad: memset");
+        if (rc || p.kernel == kConvNone) return rc;
+    }
+    rc = workspace_status(a.workspace, workspace_bytes, (size_t)p.workspace_bytes);
+    if (rc) return rc;
+    const int* ab = p.compact_launch ? a.active_bins : nullptr;
+    if (p.kernel == kConvBwdVec) {
+        rc = run_bwd_t_vec(p, s, a, ab, st);
+    } else if (p.kernel == kConvBwdOdd) {
+        rc = run_bwd_t_odd(p, s, a, st);
+    } else {
+        const int sliceC = (int)(p.lds / ((long long)sizeof(float) * s.F * s.r));           // the table is [F][sliceC r] floats
+        rc = launch_lds(dwconv_bwd_t_generic, dim3((unsigned)p.grid), dim3(256), (size_t)p.lds, st, "conv3d", s.B, s.N, s.M, s.F, C, s.r,
+                        (int)((s.N + 63LL) / 64), (int)p.nslices, sliceC, a.offsets, a.ent_key, a.ent_scale, a.input, a.filter,
+                        a.grad_output, a.grad_input, a.grad_filter);
+    }
+    if (rc) return rc;
+    // the slabs' sum (after a compact run: that table's slab count, and only the rows of the bins that occur)
+    if (p.reduce_slabs)
+        hipLaunchKernelGGL(reduce_filter_partials, dim3((total + 31) / 32), dim3(1024), 0, st, (int)p.reduce_slabs, total, CR,
+                           (const float*)a.workspace, a.grad_filter, ab, p.kernel == kConvBwdVec ? kCompactBins : 0,
+                           (int)p.reduce_slabs_compact);
     return check_launch("sph3d_depthwise_conv3d_grad_t");
 }
 
@@ -1270,94 +1200,8 @@ extern "C" int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, 
                                              float* grad_input, float* grad_filter,
                                              void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    int rc = conv_dims_ok(B, N, M, F, C, r, 1, "DepthwiseConv3dGrad");
-    if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    const int CR = C * r;
-    if (B == 0) return check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
-    const BwdLayout L = bwd_layout(B, N, F, C, r);
-    // (the vector kernels address a cloud's grad_out rows with 32-bit element offsets)
-    if (L.V && (unsigned long long)M * CR + 256ull < (1ull << 32))
-        return run_bwd_t_vec(L, B, N, M, F, C, r, offsets, ent_key, ent_scale, source_order, active_bins, input, filter, grad_output,
-                             grad_input, grad_filter, workspace, workspace_bytes, st);
-    // generic path (odd channel counts, other multipliers, F > 64): LDS float atomics, slow but general
-    if (deterministic_on()) {
-        // odd row widths (r = 1, odd C, F <= 65): the fixed-order gather of dwconv_bwd_t_odd instead
-        const OddLayout O = odd_layout(B, N, F, C, r);
-        if (O.T && (unsigned long long)M * CR + 256ull < (1ull << 32))
-            return run_bwd_t_odd(O, B, N, M, F, C, offsets, ent_key, ent_scale, source_order, input, filter, grad_output, grad_input,
-                                 grad_filter, workspace, workspace_bytes, st);
-        set_error("DepthwiseConv3dGrad: deterministic mode is on and F=%d C=%d r=%d takes the generic kernel, which sums with float "
-                  "atomics (shapes with r in {1, 2} and F <= 65 run the fixed-order kernels)", F, C, r);
-        return SPH3D_EUNSUPPORTED;
-    }
-    rc = check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * CR, st), "conv3d grad: memset");
-    if (rc) return rc;
-    SPH3D_REQUIRE(r <= 256, "DepthwiseConv3dGrad: depth multiplier %d > 256 unsupported", r);
-    int sliceC = 256 / r;
-    if (sliceC < 1) sliceC = 1;
-    if (sliceC > C) sliceC = C;
-    const int nslices = (C + sliceC - 1) / sliceC;
-    const int nblocks = (N + 63) / 64;
-    const size_t lds = (size_t)F * sliceC * r * sizeof(float);
-    rc = launch_lds(dwconv_bwd_t_generic, dim3(xcd_grid(B, nblocks * nslices)), dim3(256), lds, st, "conv3d", B, N, M, F, C, r,
-                    nblocks, nslices, sliceC, offsets, ent_key, ent_scale, input, filter, grad_output, grad_input, grad_filter);
-    if (rc) return rc;
-    return check_launch("sph3d_depthwise_conv3d_grad_t");
-}
-
-extern "C" int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, int r, int K,
-                                           const int* nn_index, const int* nn_count, const int* bin_index,
-                                           const float* input, const float* filter, const float* grad_output,
-                                           float* grad_input, float* grad_filter,
-                                           void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
-{
-    int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3dGrad");
-    if (rc) return rc;
-    const TgLayout t = tg_layout(workspace, B, N, M, K, F);
-    const size_t need = t.bytes + grad_t_bytes(B, N, F, C, r);
-    if (B > 0 && (workspace == nullptr || workspace_bytes < need)) {
-        set_error("DepthwiseConv3dGrad: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
-    if (B == 0) return sph3d_depthwise_conv3d_grad_t(B, N, M, F, C, r, nullptr, nullptr, nullptr, nullptr, nullptr, input, filter,
-                                                     grad_output, grad_input, grad_filter, nullptr, 0, stream);
-    rc = sph3d_graph_transpose(B, N, M, K, F, nn_index, nn_count, bin_index, nullptr, t.offsets, t.key, t.scale, t.active,
-                               t.scratch, t.scratch_bytes, stream);
-    if (rc) return rc;
-    return sph3d_depthwise_conv3d_grad_t(B, N, M, F, C, r, t.offsets, t.key, t.scale, nullptr, t.active, input, filter, grad_output,
-                                         grad_input, grad_filter, (char*)workspace + t.bytes, workspace_bytes - t.bytes, stream);
-}
-
-
-// ---- the same two ops on a channel concatenation [input_a (Ca) | input_b (Cb)] that is never materialised ---------------------
-// (models/SPH3D_s3dis.py:100-104: tf.concat of the un-pooled features and the encoder's skip features feeds the next decoder
-// level's separable convolution).  Channel slices of the kernels are 256 outputs = 256 / r inputs wide; Ca * r must be a
-// multiple of 256 so that every slice reads one tensor.  Other shapes: SPH3D_EUNSUPPORTED (concatenate and call the plain ops).
-static bool cat_ok(int F, int Ca, int Cb, int r)
-{
-    int V = 0;
-    const int C = Ca + Cb;
-    return Ca > 0 && Cb > 0 && (r == 1 || r == 2) && C % 4 == 0 && C > 128 && (Ca * r) % kSlice == 0 && vec_plan(F, C * r, r, V) && V == 4;
-}
-
-extern "C" int sph3d_depthwise_conv3d_cat_supported(int F, int Ca, int Cb, int r) { return cat_ok(F, Ca, Cb, r) ? 1 : 0; }
-
-extern "C" int sph3d_depthwise_conv3d_cat(int B, int N, int M, int F, int Ca, int Cb, int r, int K, const int* nn_index,
-                                          const int* nn_count, const int* bin_index, const float* input_a, const float* input_b,
-                                          const float* filter, float* output, sph3d_stream_t stream)
-{
-    const int C = Ca + Cb;
-    int rc = conv_dims_ok(B, N, M, F, C, r, K, "DepthwiseConv3d");
-    if (rc) return rc;
-    if (!cat_ok(F, Ca, Cb, r) || (unsigned long long)N * C + 256ull >= (1ull << 32)) {
-        set_error("DepthwiseConv3d (two inputs): Ca=%d Cb=%d r=%d not covered (Ca*r must be a multiple of 256)", Ca, Cb, r);
-        return SPH3D_EUNSUPPORTED;
-    }
-    if (B == 0 || M == 0) return SPH3D_OK;
-    rc = launch_fwd_row(B, N, M, F, C, r, K, nn_index, nn_count, bin_index, input_a, filter, output, input_b, Ca, as_stream(stream));
-    if (rc) return rc;
-    return check_launch("sph3d_depthwise_conv3d_cat");
+    return run_grad_t({kConvGradT, B, N, M, F, C, 0, r, 1}, {offsets, ent_key, ent_scale, source_order, active_bins, input, nullptr, filter,
+                      grad_output, grad_input, nullptr, grad_filter, workspace}, workspace_bytes, stream);
 }
 
 extern "C" int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int Ca, int Cb, int r, const int* offsets, const int* ent_key,
@@ -1366,16 +1210,58 @@ extern "C" int sph3d_depthwise_conv3d_grad_t_cat(int B, int N, int M, int F, int
                                                  const float* grad_output, float* grad_a, float* grad_b, float* grad_filter,
                                                  void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    const int C = Ca + Cb;
-    int rc = conv_dims_ok(B, N, M, F, C, r, 1, "DepthwiseConv3dGrad");
+    return run_grad_t({kConvGradTCat, B, N, M, F, Ca, Cb, r, 1}, {offsets, ent_key, ent_scale, source_order, active_bins, input_a, input_b,
+                      filter, grad_output, grad_a, grad_b, grad_filter, workspace}, workspace_bytes, stream);
+}
+
+// bytes of the gradient's own workspace.  (M = 0: they do not depend on M — a call whose grad_output rows pass 32-bit offsets
+// takes a kernel that needs none)
+extern "C" size_t sph3d_depthwise_conv3d_grad_t_workspace(int B, int N, int F, int C, int r)
+{
+    return (size_t)plan_of({kConvGradT, B, N, 0, F, C, 0, r, 1}, false).workspace_bytes;
+}
+extern "C" size_t sph3d_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K)
+{
+    return tg_layout(nullptr, B, N, M, K, F).bytes + sph3d_depthwise_conv3d_grad_t_workspace(B, N, F, C, r);
+}
+
+// the one-call gradient: the transposed graph, built in front of the caller's workspace, then sph3d_depthwise_conv3d_grad_t
+extern "C" int sph3d_depthwise_conv3d_grad(int B, int N, int M, int F, int C, int r, int K,
+                                           const int* nn_index, const int* nn_count, const int* bin_index,
+                                           const float* input, const float* filter, const float* grad_output,
+                                           float* grad_input, float* grad_filter,
+                                           void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
+{
+    const ConvShape with_k = {kConvGradT, B, N, M, F, C, 0, r, K}, s = {kConvGradT, B, N, M, F, C, 0, r, 1};
+    int rc = plan_status(plan_of(with_k, true), with_k);           // (the dimensions, K among them, before they size the graph)
     if (rc) return rc;
-    if (!cat_ok(F, Ca, Cb, r) || (unsigned long long)M * C * r + 256ull >= (1ull << 32)) {
-        set_error("DepthwiseConv3dGrad (two inputs): Ca=%d Cb=%d r=%d not covered (Ca*r must be a multiple of 256)", Ca, Cb, r);
-        return SPH3D_EUNSUPPORTED;
-    }
-    hipStream_t st = as_stream(stream);
-    if (B == 0) return check_hip(hipMemsetAsync(grad_filter, 0, sizeof(float) * (size_t)F * C * r, st), "conv3d grad: memset");
-    // (cat_ok: four channels per lane and more than 128 outputs, so the full-wave form)
-    return run_bwd_t_vec(bwd_layout(B, N, F, C, r), B, N, M, F, C, r, offsets, ent_key, ent_scale, source_order, active_bins, input_a,
-                         filter, grad_output, grad_a, grad_filter, workspace, workspace_bytes, st, input_b, grad_b, Ca);
+    GradArgs a = {nullptr, nullptr, nullptr, nullptr, nullptr, input, nullptr, filter, grad_output, grad_input, nullptr, grad_filter, nullptr};
+    if (B == 0) return run_grad_t(s, a, 0, stream);
+    const TgLayout t = tg_layout(workspace, B, N, M, K, F);
+    rc = workspace_status(workspace, workspace_bytes, sph3d_depthwise_conv3d_grad_workspace(B, N, M, F, C, r, K));
+    if (rc) return rc;
+    rc = sph3d_graph_transpose(B, N, M, K, F, nn_index, nn_count, bin_index, nullptr, t.offsets, t.key, t.scale, t.active,
+                               t.scratch, t.scratch_bytes, stream);
+    if (rc) return rc;
+    a.offsets = t.offsets, a.ent_key = t.key, a.ent_scale = t.scale, a.active_bins = t.active, a.workspace = (char*)workspace + t.bytes;
+    return run_grad_t(s, a, workspace_bytes - t.bytes, stream);
+}
+
+// ---- the plan, reported (include/sph3d.h) ---------------------------------------------------------------------------------------------
+extern "C" int sph3d_depthwise_conv3d_plan(int op, int B, int N, int M, int F, int Ca, int Cb, int r, int K, int deterministic,
+                                           int active_given, long long* out)
+{
+    const bool grad = op == kConvGradT || op == kConvGradTCat, cat = op == kConvFwdCat || op == kConvGradTCat;
+    SPH3D_REQUIRE(out != nullptr && op >= kConvFwd && op <= kConvGradTCat && deterministic >= -1 && deterministic <= 1 &&
+                      (active_given == 0 || active_given == 1) && (cat || Cb == 0),
+                  "sph3d_depthwise_conv3d_plan: bad argument (op=%d deterministic=%d active_given=%d Cb=%d out=%p)", op, deterministic,
+                  active_given, Cb, (void*)out);
+    const ConvShape s = {op, B, N, M, F, Ca, Cb, r, grad ? 1 : K};
+    const ConvPlan p = plan_of(s, active_given != 0, deterministic < 0 ? deterministic_on() : deterministic != 0);
+    if (p.bad) return plan_status(p, s);
+    static_assert(offsetof(ConvPlan, bad) == SPH3D_CONV_PLAN_FIELDS * sizeof(long long), "the plan starts with the documented fields, in their order");
+    static_assert(kConvFwd == SPH3D_CONV_FWD && kConvFwdCat == SPH3D_CONV_FWD_CAT && kConvGradT == SPH3D_CONV_GRAD_T && kConvGradTCat == SPH3D_CONV_GRAD_T_CAT,
+                  "the ops as the header numbers them");
+    memcpy(out, &p, SPH3D_CONV_PLAN_FIELDS * sizeof(long long));
+    return SPH3D_OK;
 }

@@ -4,6 +4,7 @@ PyTorch custom ops ``sph3d::depthwise_conv3d`` and ``sph3d::depthwise_conv3d_gra
 gradient wiring is the reference's @RegisterGradient("DepthwiseConv3d") (:23-32):
 [grad_input, grad_filter, None, None, None].
 """
+import ctypes
 from typing import Tuple
 
 import torch
@@ -16,6 +17,17 @@ def _channel_pad(C, r):
     """channels to add so that the 4-channels-per-lane kernels apply (they need C % 4 == 0 and r in {1, 2}); measured on
     the ModelNet level-0 shapes: C=67 r=1 gradient 7.5 -> 1.5 ms, C=35 r=2 forward 0.88 -> 0.39 ms"""
     return (-C) % 4 if r in (1, 2) else 0
+
+
+_BWD_ODD = 5                    # include/sph3d.h, sph3d_depthwise_conv3d_plan: out[0] for dwconv_bwd_t_odd
+
+
+def _grad_plan_kernel(B, N, M, F, C, r):
+    """the kernel the library's own plan names for the gradient of this shape in the current mode (a host-side question, asked
+    for the few shapes _channel_pad would pad: no layer with C % 4 == 0 comes here); an invalid shape: None, the call reports it"""
+    out = (ctypes.c_longlong * 22)()                # SPH3D_CONV_PLAN_FIELDS
+    rc = _lib.lib().sph3d_depthwise_conv3d_plan(2, B, N, M, F, C, 0, r, 1, -1, 1, ctypes.addressof(out))       # 2: SPH3D_CONV_GRAD_T
+    return out[0] if rc == 0 else None
 
 
 def _check_conv(input, filter, nn_index, nn_count, bin_index):
@@ -73,7 +85,7 @@ def _depthwise_conv3d_grad_impl(input: torch.Tensor, filter: torch.Tensor, grad_
     F, _, r = filter.shape
     M, K = nn_index.shape[1], nn_index.shape[2]
     pad = _channel_pad(C, r)
-    if pad and r == 1 and C % 2 == 1 and F <= 65 and _tgraph.is_deterministic():
+    if pad and _grad_plan_kernel(B, N, M, F, C, r) == _BWD_ODD:
         # deterministic mode has a gradient kernel for odd rows (dwconv_bwd_t_odd): no padded copies, no slices (measured on
         # the ModelNet plan, 32 clouds: C=67 0.261 -> 0.234 ms, C=131 0.128 -> 0.110 ms; tools/exp_bwd_odd.py)
         pad = 0

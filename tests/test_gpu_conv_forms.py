@@ -2,14 +2,15 @@
 form, through the C ABI.
 
 The launchers pick kernels from the dimensions (and, on the device, from the active-bin count); every case restates the rule
-that selects its form as an assertion — the functions of tests/_conv_forms.py are copied from conv3d.hip, and the two the
-library can be asked about (the gradient's workspace size, which is bwd_plan's and vec_plan's result, and the two-input
-predicate) are compared with its answer.  Outputs are pre-filled with NaN (grad_input and grad_filter are promised "fully
+that selects its form as an assertion — the functions of tests/_conv_forms.py are copied from the launchers conv3d.hip had before
+csrc/conv_plan.hpp stated the choice once; tests/test_conv_forms.py holds the library's own plan to them on the host, and here
+the gradient's workspace size and the two-input predicate are compared with the library's answer.  Outputs are pre-filled with NaN (grad_input and grad_filter are promised "fully
 written"), the gradient's workspace — slabs and hub list — with 0xFF bytes (NaN as floats: a slab that is read but was not
 written this call shows), transposed graphs are built with sph3d_graph_transpose itself.  assert_conv prints the used fraction
 of each derived bound behind a [form] tag: DESIGN.md §2 quotes the maxima.
 
-Left out on purpose: the 32-bit-offset fall-backs (N C or M C r near 2^32, N above 2^24) and neighbour ids outside [0, N).  The
+Left out on purpose: neighbour ids outside [0, N), and launches at the 32-bit-offset fall-backs (N C or M C r near 2^32, N above
+2^24: no small device input reaches them; tests/test_conv_forms.py holds the plan's choice there on the host).  The
 separable kernels (sepconv.hip, sepring.hip) are held the same way in tests/test_gpu_sep_forms.py."""
 import os
 

@@ -1,7 +1,7 @@
 """The conv gradient for odd row widths (r = 1, odd C: dwconv_bwd_t_odd of csrc/conv3d.hip), the fixed-order kernel that
 deterministic mode runs where dwconv_bwd_t_generic would add with float atomics — per element against float64
 (tests/_conv_ref.py: the project's derived bounds, nothing new), through the C ABI like tests/test_gpu_conv_forms.py, whose host
-graph makers and device helpers it uses.  tests/_conv_odd_forms.py restates the launch plan; the workspace bytes it gives are
+graph makers and device helpers it uses.  tests/_conv_forms.py restates the launch plan; the workspace bytes it gives are
 compared with the library's answer in the mode, and outside it the same shapes must still ask for no workspace and run.
 
 Outputs are pre-filled with NaN, the workspace with 0xFF bytes.  Every comparison of bit patterns is exact.  The switch is off
@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from _conv_forms import dims_ok, vec_plan
-from _conv_odd_forms import odd_form, odd_layout
+from _conv_forms import ODD_CHANNELS as CHANNELS, dims_ok, odd_form, odd_layout, vec_plan
 from _conv_ref import assert_conv, bits, conv_grad_ref, make_bins, make_graph, make_values
 from test_gpu_conv_forms import Graph, _ff, _graph_from_segments, _n, _nan, _random_graph, _t
 import sph3d_gcn_amd as pkg
@@ -21,7 +20,6 @@ pytestmark = pytest.mark.gpu
 P, S = _lib.ptr, _lib.stream_ptr
 EUNSUPPORTED = -4
 B, N, M = 3, 300, 77                     # three clouds: a ragged deal of (cloud, part) items to the 8 XCDs; N != M
-CHANNELS = [1, 3, 35, 63, 65, 67, 131, 255, 257]          # T = 1, 1, 1, 1, 2, 2, 3, 4 and 4 with a second slice of one channel
 
 
 @pytest.fixture(autouse=True)
