@@ -434,6 +434,23 @@ int sph3d_pointwise_gemm(int R, int Cin, int Cout,
  * Ragged shapes and misaligned operands take the same kernels with element-wise bounds, in either mode; only the very narrow ones
  * (NN / NT: Cin < 16 or Cout < 32; TN: Cin < 32 or Cout < 32) take the fp32 kernels in mode 1 too. */
 int sph3d_pointwise_gemm_mode(int mode);
+/* float32 matmul precision of the products on the bf16 matrix pipe — the three levels of torch.set_float32_matmul_precision, as the
+ * number of bf16 pieces every fp32 operand is cut into.  Process-wide; 1, 2 or 3 sets the piece count and returns the previous one,
+ * any other value only queries.  With rn(x) = fp32 -> bf16 by round-to-nearest-even, widened back to fp32 (on the bit pattern u of a
+ * finite x: ((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16):
+ *   3 (default, "highest"): truncation pieces h, m, l, x = h + m + l exactly, six products — as described at sph3d_pointwise_gemm_mode;
+ *   2 ("high")  : h = rn(x), m = rn(x - h) (the subtraction is exact in fp32); per product  m h' + h m' + h h'  is kept.
+ *                 Per output element |error| <= c_high * sum_k |x_k| |w_k|,  c_high = 3 * 2^-16 * (1 + 2^-7);
+ *   1 ("medium"): h = rn(x); per product  h h'.   |error| <= c_medium * sum_k |x_k| |w_k|,  c_medium = 2^-7 + 2^-16.
+ * Piece products are exact in the fp32 accumulator; the accumulation (fp32, small terms first, in the order the launch form already
+ * uses) adds its usual share (the tests allow 1e-5 of the same sum).  Non-finite operands never give a finite output; rn rounds the
+ * largest finite values to infinity.  A level is a permission: it has effect only where the plan's `pipe` is 1 — products on the fp32
+ * pipe (mode 0, and the very narrow ragged shapes above) stay there and are merely more accurate than asked.  It covers
+ * sph3d_pointwise_gemm (both trans_w), sph3d_pointwise_gemm_bnstats and sph3d_pointwise_gemm_tn; sph3d_pointwise_gemm_plan,
+ * sph3d_pointwise_gemm_mode and every workspace size answer the same at every piece count.  The products inside
+ * sph3d_separable_conv3d_fused / _train, sph3d_pointwise_gemm_skinny* and sph3d_pointwise_gemm_cond* keep the default accuracy.
+ * Like the mode, this is a process-global read at every launch: do not change it while another thread issues products. */
+int sph3d_pointwise_gemm_pieces(int pieces);
 /* The launch a product takes, answered on the host (no device is touched): csrc/gemm.hip states the choice once (gemm_plan) and
  * every entry point below launches what it says.
  *   product: SPH3D_GEMM_NN / _NT (sph3d_pointwise_gemm with trans_w = 0 / 1), _NN_STATS (sph3d_pointwise_gemm_bnstats), _TN

@@ -15,6 +15,8 @@ from . import _lib  # noqa: F401
 from . import tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm, tf_surface, tf_dropout  # noqa: F401
 from . import sph3gcn_util  # noqa: F401
 from ._tgraph import set_deterministic, is_deterministic, deterministic  # noqa: F401
+from .tf_gemm import set_float32_matmul_precision, get_float32_matmul_precision, float32_matmul_precision  # noqa: F401
 
 __all__ = ["tf_nnquery", "tf_buildkernel", "tf_conv3d", "tf_pool3d", "tf_unpool3d", "tf_sample", "tf_gemm", "tf_surface", "tf_dropout",
-           "sph3gcn_util", "set_deterministic", "is_deterministic", "deterministic"]
+           "sph3gcn_util", "set_deterministic", "is_deterministic", "deterministic", "set_float32_matmul_precision",
+           "get_float32_matmul_precision", "float32_matmul_precision"]

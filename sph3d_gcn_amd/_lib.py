@@ -80,6 +80,7 @@ SIGNATURES = {
     "sph3d_ids_sample": (_I, [_I] * 4 + [_P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I, _P, _P, _S, _P]),
     "sph3d_pointwise_gemm": (_I, [_I] * 3 + [_P, _P, _P, _I, _I, _P, _P]),
     "sph3d_pointwise_gemm_mode": (_I, [_I]),
+    "sph3d_pointwise_gemm_pieces": (_I, [_I]),
     "sph3d_pointwise_gemm_plan": (_I, [_I] * 7 + [_P]),
     "sph3d_pointwise_gemm_tn_workspace": (_S, [_I] * 3),
     "sph3d_pointwise_gemm_tn": (_I, [_I] * 3 + [_P, _P, _P, _P, _S, _P]),
@@ -205,7 +206,7 @@ def timing_stop():
 
 
 _PURE = ("_workspace", "_blocks", "_supported", "_parts", "_sample_chunk")
-_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_sample_chunk", "_plan")
+_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_pieces", "_sample_chunk", "_plan")
 
 
 class _Proxy:

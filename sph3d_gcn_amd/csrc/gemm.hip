@@ -531,16 +531,36 @@ __device__ __forceinline__ Split3 split_pair(float a, float b)
     return r;
 }
 
-// Operand tile of the split kernel: global -> registers -> three bf16 piece planes in LDS.
+// The lower float32 matmul precision levels (sph3d_pointwise_gemm_pieces): NP = 2 ("high") or 1 ("medium") pieces, cut
+// by ROUND-TO-NEAREST-EVEN — rn(x) = fp32 -> bf16 -> fp32 — so that the last kept piece carries no bias towards zero:
+//     NP = 2: h = rn(x), m = rn(x - h) (the subtraction is exact), kept  m h' + h m' + h h'   — error <= 3 * 2^-16 * (1 + 2^-7) |x y|
+//     NP = 1: h = rn(x),                                           kept  h h'                 — error <= (2^-7 + 2^-16) |x y|
+// The plain __bf16 cast is the hardware's round-to-nearest-even conversion (two operands per v_cvt_pk_bf16_f32); on finite values it
+// is the integer formula (u + 0x7fff + ((u >> 16) & 1)) >> 16 of the tests, bit for bit (tests/test_gpu_gemm_precision.py: known
+// answers).  Inf stays Inf and NaN stays NaN in h, Inf - Inf makes m NaN: non-finite operands never give a finite output.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned rne_pair(float a, float b)      // the bf16 of a in the low half, of b in the high half
+{
+    return __builtin_bit_cast(unsigned, bf16x2{(__bf16)a, (__bf16)b});
+}
+template <int NP>
+__device__ __forceinline__ void split_pair_rne(float a, float b, unsigned (&pc)[NP])
+{
+    pc[0] = rne_pair(a, b);
+    if constexpr (NP == 2) pc[1] = rne_pair(a - __uint_as_float(pc[0] << 16), b - __uint_as_float(pc[0] & 0xffff0000u));
+}
+
+// Operand tile of the split kernel: global -> registers -> NP (three, unless a lower precision level is set) bf16 piece planes in LDS.
 // KMAJ (memory [row][k]): a unit = one float4 (4 consecutive k of a row) -> one 8-byte store per piece.
 // !KMAJ (memory [k][row]): a unit = 2 (k) x 4 (rows): two float4 loads along the rows (the lanes of a k cover contiguous bytes) ->
 // per row the k pair is ONE packed dword per piece (no transposing shuffles: split_pair packs its two arguments).  Always pairs —
 // with 4 x 4 blocks half of the threads have no unit at 64-row tiles and the busy half carries twice the conversion work.
-template <bool KMAJ, int BT, int BK>
+template <bool KMAJ, int BT, int BK, int NP>
 struct SplitStage {
+    static_assert(NP >= 1 && NP <= 3, "one, two or three pieces");
     static constexpr int KG = BK / 8;                       // k-groups of 8
     static constexpr int PLANE = KG * BT * 16;              // bytes of one piece's plane
-    static constexpr int BYTES = 3 * PLANE;
+    static constexpr int BYTES = NP * PLANE;
     // 16-byte slot of (k-group g, row): the row index XOR-ed with a few bits of (g, row bit 4), constant over the 16 consecutive rows
     // a fragment read covers (it stays a permutation of one 256-byte bank group: conflict-free), different for the writers that
     // would otherwise meet in a bank — the two k-groups of a k-contiguous unit's store (same row) and, for the row-contiguous
@@ -595,6 +615,13 @@ struct SplitStage {
     }
     __device__ __forceinline__ void store(char* img) const
     {
+        if constexpr (NP == 3) store_exact(img);
+        else store_rounded(img);
+    }
+    // three truncation pieces (split_pair): the default level.  Kept as it was, statement for statement: its kernels assemble to the text
+    // they had before the other levels existed
+    __device__ __forceinline__ void store_exact(char* img) const
+    {
         if (UNITS < 256 && (int)threadIdx.x >= UNITS) return;
 #pragma unroll
         for (int i = 0; i < NCH; i++) {
@@ -622,6 +649,37 @@ struct SplitStage {
             }
         }
     }
+    // one or two round-to-nearest pieces (split_pair_rne): the same units and slots, NP planes
+    __device__ __forceinline__ void store_rounded(char* img) const
+    {
+        if (UNITS < 256 && (int)threadIdx.x >= UNITS) return;
+#pragma unroll
+        for (int i = 0; i < NCH; i++) {
+            const int u = (int)threadIdx.x + i * 256;
+            if (KMAJ) {
+                const int row = u / KUN, kq = u % KUN;
+                const f32x4 v = r[i];
+                unsigned p0[NP], p1[NP];
+                split_pair_rne<NP>(v.x, v.y, p0);
+                split_pair_rne<NP>(v.z, v.w, p1);
+                char* q = img + (slot(kq >> 1, row) << 4) + ((kq & 1) << 3);
+#pragma unroll
+                for (int pc = 0; pc < NP; pc++) *reinterpret_cast<u32x2v*>(q + pc * PLANE) = u32x2v{p0[pc], p1[pc]};
+            } else {
+                const int kq = u % KUN, rq = u / KUN;
+                const int k0 = kq * 2;
+                const f32x4 a = r[2 * i], b = r[2 * i + 1];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    unsigned sp[NP];
+                    split_pair_rne<NP>(a[j], b[j], sp);
+                    char* q = img + (slot(k0 >> 3, rq * 4 + j) << 4) + ((k0 & 7) << 1);
+#pragma unroll
+                    for (int pc = 0; pc < NP; pc++) *reinterpret_cast<unsigned*>(q + pc * PLANE) = sp[pc];
+                }
+            }
+        }
+    }
     // piece `pc` of the lane's operand: tile row `row`, k-group g
     __device__ __forceinline__ static bf16x8 frag(const char* img, int pc, int row, int g)
     {
@@ -637,7 +695,9 @@ __device__ int g_xs_fail = 0;      // exchange launches that gave up waiting (ne
 // and count themselves in at xflag[tile]; split 0 (dispatched last) waits for the count, adds the slabs in split order
 // (deterministic), clears the counter and runs the ordinary epilogue (bias / ELU / BN statistics / float4 rows).  No slab-sum
 // launch, no float atomics.
-template <bool AK, bool BKM, int BMT, int BN, int BK, bool SPLITK, bool STATS, bool GUARD = false, bool XS = false>
+// NP: pieces per operand (3: the default, fp32-sized error; 2 / 1: the lower precision levels, see split_pair_rne) — NP planes per operand
+// in LDS, NP fragments per MFMA tile, and the 6, 3 or 1 leading piece products.
+template <int NP, bool AK, bool BKM, int BMT, int BN, int BK, bool SPLITK, bool STATS, bool GUARD = false, bool XS = false>
 __global__ __launch_bounds__(256, 4) void gemm_split_mfma(int M, int N, int Kd, const float* __restrict__ A, int lda,
                                                           const float* __restrict__ B, int ldb, float* __restrict__ Cmat, int ldc,
                                                           const float* __restrict__ bias, int act, int kchunk,
@@ -645,8 +705,8 @@ __global__ __launch_bounds__(256, 4) void gemm_split_mfma(int M, int N, int Kd, 
                                                           float* __restrict__ xslab = nullptr, int* __restrict__ xflag = nullptr)
 {
     static_assert(!(XS && SPLITK) && !(XS && GUARD), "the exchange variant is an unguarded, non-slab kernel");
-    using PA = SplitStage<AK, BMT, BK>;
-    using PB = SplitStage<BKM, BN, BK>;
+    using PA = SplitStage<AK, BMT, BK, NP>;
+    using PB = SplitStage<BKM, BN, BK, NP>;
     constexpr int WM = BMT / 2, WN = BN / 2;     // wave sub-tile
     constexpr int TM = WM / 32, TN = WN / 32;    // MFMA tiles per wave
     constexpr int BUFB = PA::BYTES + PB::BYTES;  // bytes of one plane image (A pieces, then B pieces)
@@ -737,25 +797,38 @@ __global__ __launch_bounds__(256, 4) void gemm_split_mfma(int M, int N, int Kd, 
 #pragma unroll
         for (int s16 = 0; s16 < BK / 16; s16++) {
             const int g = 2 * s16 + lk;
-            bf16x8 af[TM][3], bf[TN][3];
+            bf16x8 af[TM][NP], bf[TN][NP];
 #pragma unroll
             for (int i = 0; i < TM; i++)
 #pragma unroll
-                for (int pc = 0; pc < 3; pc++) af[i][pc] = PA::frag(ca, pc, wm + i * 32 + li, g);
+                for (int pc = 0; pc < NP; pc++) af[i][pc] = PA::frag(ca, pc, wm + i * 32 + li, g);
 #pragma unroll
             for (int j = 0; j < TN; j++)
 #pragma unroll
-                for (int pc = 0; pc < 3; pc++) bf[j][pc] = PB::frag(cb, pc, wn + j * 32 + li, g);
+                for (int pc = 0; pc < NP; pc++) bf[j][pc] = PB::frag(cb, pc, wn + j * 32 + li, g);
             // small terms first; consecutive MFMAs write different accumulators where there is more than one
+            if constexpr (NP == 3) {
 #pragma unroll
-            for (int t = 0; t < 6; t++) {
-                const int pa = t == 0 ? 0 : (t == 1 ? 2 : (t == 2 ? 1 : (t == 3 ? 0 : (t == 4 ? 1 : 0))));      // A piece: h l m h m h
-                const int pb = t == 0 ? 2 : (t == 1 ? 0 : (t == 2 ? 1 : (t == 3 ? 1 : (t == 4 ? 0 : 0))));      // B piece: l h m m h h
+                for (int t = 0; t < 6; t++) {
+                    const int pa = t == 0 ? 0 : (t == 1 ? 2 : (t == 2 ? 1 : (t == 3 ? 0 : (t == 4 ? 1 : 0))));      // A piece: h l m h m h
+                    const int pb = t == 0 ? 2 : (t == 1 ? 0 : (t == 2 ? 1 : (t == 3 ? 1 : (t == 4 ? 0 : 0))));      // B piece: l h m m h h
 #pragma unroll
-                for (int i = 0; i < TM; i++)
+                    for (int i = 0; i < TM; i++)
 #pragma unroll
-                    for (int j = 0; j < TN; j++)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][pa], bf[j][pb], acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < TN; j++)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][pa], bf[j][pb], acc[i][j], 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int t = NP == 2 ? 0 : 2; t < 3; t++) {
+                    const int pa = t == 0 ? 1 : 0;      // A piece: m h h
+                    const int pb = t == 1 ? 1 : 0;      // B piece: h m h   (one piece: the last product alone)
+#pragma unroll
+                    for (int i = 0; i < TM; i++)
+#pragma unroll
+                        for (int j = 0; j < TN; j++)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][pa], bf[j][pb], acc[i][j], 0, 0, 0);
+                }
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -862,6 +935,10 @@ static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15)
 // instead.  Ragged or misaligned products take the guarded variants of either; the very narrow ones always the fp32 ones (gemm_plan)
 static std::atomic<int> g_split_mode{1};
 static bool split_on() { return g_split_mode.load(std::memory_order_relaxed) != 0; }
+// pieces per operand on the bf16 pipe (sph3d_pointwise_gemm_pieces): 3 "highest" (the default), 2 "high", 1 "medium".  Read once per
+// launch, beside the plan; the plan itself does not depend on it, and products the plan sends to the fp32 pipe ignore it
+static std::atomic<int> g_split_pieces{3};
+static int split_pieces() { return g_split_pieces.load(std::memory_order_relaxed); }
 
 // tile choice: the largest tile that still gives every CU TWO workgroups (measured: with >= 256 tiles as the rule the
 // mid-size levels ran 50 TF, with >= 512 they run 80-90 TF: one partial wave of workgroups leaves half the CUs idle)
@@ -999,6 +1076,8 @@ static GemmPlan gemm_plan(int product, int R, int Cin, int Cout, bool aligned, b
 }
 
 // ---- the launcher: the kernel a plan names.  Only the instantiations some plan reaches are compiled ------------------------------
+// (bf16 pipe: each reached form in the three piece counts — the plan does not depend on the precision level, so every split form is
+// reached at every level: 24 forms x 3 beside the 17 of the fp32 pipe)
 constexpr bool plan_reaches(int product, bool bf16, int bm, int bn, int bk, bool guard, bool xs)
 {
     // 64 x 64 x 32 on the bf16 pipe: every product's exchange, and NN / NT / NNS without it
@@ -1016,13 +1095,23 @@ static int launch_plan(const GemmPlan& p, const GemmOperands& o, char* xb, hipSt
 {
     constexpr bool AK = PRODUCT != kTN, BKM = PRODUCT == kNT, STATS = PRODUCT == kNNS;
     const int ns = p.xs > 1 ? p.xs : p.nsplit;
+    const int pieces = split_pieces();
     auto go = [&](auto BF16, auto BMT, auto BN, auto BK, auto GUARD, auto XS) {
         if constexpr (plan_reaches(PRODUCT, BF16(), BMT(), BN(), BK(), GUARD(), XS())) {
             constexpr bool SPLITK = PRODUCT == kTN && !XS();
-            if constexpr (BF16())
-                hipLaunchKernelGGL((gemm_split_mfma<AK, BKM, BMT(), BN(), BK(), SPLITK, STATS, GUARD(), XS()>), dim3(p.grid), dim3(256), 0, st,
-                                   o.M, o.N, o.Kd, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.act, p.kchunk, o.stats, ns,
-                                   XS() ? (float*)(xb + kXsFlagBytes) : nullptr, XS() ? (int*)xb : nullptr);
+            if constexpr (BF16()) {
+                // the piece count beside the plan: the same tile, k-step, guard, exchange and slabs at every precision level
+                constexpr int bmt = BMT(), bn = BN(), bk = BK();
+                constexpr bool guard = GUARD(), xs = XS();
+                auto split = [&](auto NP) {
+                    hipLaunchKernelGGL((gemm_split_mfma<decltype(NP)::value, AK, BKM, bmt, bn, bk, SPLITK, STATS, guard, xs>), dim3(p.grid),
+                                       dim3(256), 0, st, o.M, o.N, o.Kd, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.act, p.kchunk, o.stats, ns,
+                                       xs ? (float*)(xb + kXsFlagBytes) : nullptr, xs ? (int*)xb : nullptr);
+                };
+                if (pieces == 3) split(std::integral_constant<int, 3>{});
+                else if (pieces == 2) split(std::integral_constant<int, 2>{});
+                else split(std::integral_constant<int, 1>{});
+            }
             else
                 hipLaunchKernelGGL((gemm_f32_mfma<AK, BKM, BMT(), BN(), BK(), SPLITK, GUARD(), STATS>), dim3(p.grid), dim3(256), 0, st, o.M,
                                    o.N, o.Kd, o.A, o.lda, o.B, o.ldb, o.C, o.ldc, o.bias, o.act, p.kchunk, o.stats, ns);
@@ -1081,6 +1170,12 @@ extern "C" int sph3d_pointwise_gemm_mode(int mode)
 {
     if (mode == 0 || mode == 1) return g_split_mode.exchange(mode);
     return g_split_mode.load();
+}
+
+extern "C" int sph3d_pointwise_gemm_pieces(int pieces)
+{
+    if (pieces >= 1 && pieces <= 3) return g_split_pieces.exchange(pieces);
+    return g_split_pieces.load();
 }
 
 // deterministic mode (include/sph3d.h): read by graph.hip, conv3d.hip and pool3d.hip on every call

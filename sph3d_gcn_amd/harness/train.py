@@ -29,7 +29,7 @@ import re
 import numpy as np
 import torch
 
-from .. import _lib, _tgraph, tf_norm
+from .. import _lib, _tgraph, tf_gemm, tf_norm
 from . import dist as hdist
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -277,10 +277,13 @@ class Trainer:
     whose forward takes `dropout_key` (the ModelNet net) is called with dropout_key = (seed, global_step) and dropout_row0 =
     rank * B, so its dropout masks are draws of (seed, step) like the feed's — a checkpoint holds no generator state, and only
     then does a resumed run drop what the uninterrupted one drops; None follows `deterministic`.  Other models are called as
-    before."""
+    before.  matmul_precision: "highest" | "high" | "medium" — train_step, eval_one_epoch and fit run under
+    sph3d_gcn_amd.float32_matmul_precision(level) and the process setting is back at its previous value when they
+    return; None leaves the process setting alone."""
 
     def __init__(self, model, loss_fn, optimizer_factory, schedule, num_cls, line=s3dis_line, prime=None, seed=0, log_every=50,
-                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False, keyed_dropout=None):
+                 max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False, keyed_dropout=None,
+                 matmul_precision=None):
         if prime is None:
             raise ValueError("Trainer: `prime` (one batch of the training shapes) is needed to create the variables")
         self.model, self.loss_fn, self.schedule, self.line = model, loss_fn, schedule, line
@@ -289,6 +292,9 @@ class Trainer:
         self.log = log
         self.sync_bn = bool(sync_bn)
         self.deterministic = bool(deterministic)
+        if matmul_precision is not None and matmul_precision not in ("highest", "high", "medium"):
+            raise ValueError("Trainer: matmul_precision should be None, 'highest', 'high' or 'medium', got %r" % (matmul_precision,))
+        self.matmul_precision = matmul_precision
         self.keyed_dropout = (self.deterministic if keyed_dropout is None else bool(keyed_dropout)) and \
             "dropout_key" in inspect.signature(model.forward).parameters
         self.global_step, self.epoch = 0, -1           # updates done; the last finished epoch
@@ -333,7 +339,13 @@ class Trainer:
         return batch, pred, self._total_loss(pred, batch), ready
 
     def _mode(self):
-        return _tgraph.deterministic(True) if self.deterministic else contextlib.nullcontext()
+        if self.matmul_precision is None:
+            return _tgraph.deterministic(True) if self.deterministic else contextlib.nullcontext()
+        stack = contextlib.ExitStack()          # (entered here, left by the caller's `with`)
+        stack.enter_context(tf_gemm.float32_matmul_precision(self.matmul_precision))
+        if self.deterministic:
+            stack.enter_context(_tgraph.deterministic(True))
+        return stack
 
     def train_step(self, item, feed=None):
         """plan / forward, loss, backward, all-reduce, update, metrics; nothing is read from the device"""

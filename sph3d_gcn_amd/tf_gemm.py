@@ -5,9 +5,41 @@ fully_connected (utils/sph3gcn_util.py:146-150, 204-206, 260; cuBLAS SGEMM in th
 (sph3d_pointwise_gemm*): custom op ``sph3d::pointwise_gemm`` with its two backward products.  (The library yardstick,
 torch.matmul on rocBLAS / hipBLASLt, lives in tools/exp_gemm.py, not here.)
 """
+import contextlib
+
 import torch
 
 from . import _lib
+
+# ---- float32 matmul precision of the products on the bf16 matrix pipe (include/sph3d.h: sph3d_pointwise_gemm_pieces; DESIGN.md 4.22) ----
+# The names and meanings of torch.set_float32_matmul_precision; torch's own global is NOT read: the default path cannot change
+# behind a user who set torch's flag for other reasons.
+_PIECES = {"highest": 3, "high": 2, "medium": 1}
+_LEVELS = {v: k for k, v in _PIECES.items()}
+
+
+def get_float32_matmul_precision():
+    return _LEVELS[_lib.lib().sph3d_pointwise_gemm_pieces(0)]
+
+
+def set_float32_matmul_precision(level):
+    """process-wide (not to be flipped while another thread issues products): "highest" — every fp32 operand as three bf16 pieces,
+    fp32-sized error, the default; "high" — two round-to-nearest pieces, error <= 3 * 2^-16 * (1 + 2^-7) of an element's summed term
+    magnitudes; "medium" — one, error <= 2^-7 + 2^-16 of them.  A permission: products that run on the fp32 pipe stay there, and
+    the products inside the one-kernel separable layers, the few-output logits layers and their gradients keep "highest".
+    -> the previous level"""
+    if level not in _PIECES:
+        raise ValueError("float32 matmul precision should be 'highest', 'high' or 'medium', got %r" % (level,))
+    return _LEVELS[_lib.lib().sph3d_pointwise_gemm_pieces(_PIECES[level])]
+
+
+@contextlib.contextmanager
+def float32_matmul_precision(level):
+    prev = set_float32_matmul_precision(level)
+    try:
+        yield
+    finally:
+        set_float32_matmul_precision(prev)
 
 
 def _pointwise_gemm_impl(x: torch.Tensor, w: torch.Tensor, trans_w: bool) -> torch.Tensor:
