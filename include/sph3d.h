@@ -111,6 +111,42 @@ int sph3d_build_sphere_neighbor_fixed_ws(int B, int N, int M, int nn_sample, flo
 int sph3d_release_stream_scratch(sph3d_stream_t stream);
 int sph3d_release_all_scratch(void);
 
+/* What a range search launches, answered on the host (no device is touched): csrc/nn_plan.hpp states the choice once (nn_plan),
+ * every search entry point above and sph3d_build_sphere_graph* below launch what it says, and
+ * sph3d_build_sphere_neighbor_workspace reads it.
+ *   fixed: 0 the reference's search, 1 the `_fixed` entries;  B, N, M, K (nn_sample), radius as the entry point takes them;
+ *   fuse_wanted: 1 for sph3d_build_sphere_graph*;  memory: the front's device memory — SPH3D_NN_MEMORY_CALLER (a `_ws` entry
+ *   with a workspace), _LIBRARY (an entry with the reference's signature), _NONE (a `_ws` entry with workspace == NULL; a call
+ *   the library finds no buffer for, e.g. under stream capture, is launched as this)
+ *   out[SPH3D_NN_PLAN_FIELDS], in this order:
+ *     0 front: 0 none, 1 the cell grid (+ the early-stopping scan of the later positions), 2 small clouds: that scan alone.
+ *       Counted by sph3d_nngrid_launches() when not 0; fields 1 .. 22 are 0 without a front
+ *     1 npos (grid: chain positions it takes; fixed: 1, all queries)   2 nq (queries per cloud in its visiting order)
+ *     3 nslices (their slices of 1024)   4 parts (waves of four queries)   5 W (32-bit words of a query's bitmap)
+ *     6 build_lds (LDS bytes of nngrid_build_kernel and nngrid_qorder_kernel)   7 search_lds (of nngrid_search_kernel)
+ *     8 9 10 workgroups of the build (B), the query order (B nslices), the search (parts of B clouds dealt to the XCDs)
+ *     11 j0 (first query of a cloud that nndense_kernel takes: M if none, 0 for small clouds)
+ *     12 dparts, 13 dense_lds, 14 dense_grid (nndense_kernel: waves-of-four-queries groups per cloud, LDS bytes, workgroups;
+ *     0 when j0 == M)   15 prepare_block (small: threads of nnsmall_prepare_kernel)
+ *     16 workspace_bytes, and the byte offsets into it: 17 flag  18 radii and thresholds  19 per-cloud headers  20 cell starts
+ *     21 the cloud in cell order  22 the query order (20 .. 22: grid)
+ *     23 CPW, 24 MULTI, 25 DEFER: the chain kernel nnquery_sphere_kernel<CPW, MULTI, DEFER, fused> behind the front (CPW 1 with
+ *     MULTI)   26 chunkN (points per LDS chunk)   27 groups (workgroups per reference block)   28 chain_grid (workgroups; 0: B or
+ *     M is 0, nothing is launched)   29 chain_lds (bytes)   30 grid_done (chain positions the front has finished unless its
+ *     flag is up: 0 or 1 << 20)   31 fused (the output passes write bins and segment counts; 0 with fuse_wanted:
+ *     sph3d_build_sphere_graph* runs sph3d_spherical_kernel and sph3d_graph_transpose_count behind the search)
+ *     32 clear_counts (segments of F counters, B N + 1, that are cleared again in front of the chain kernel when the front's
+ *     flag is up; 0: no such launch)
+ *   sph3d_build_sphere_neighbor_workspace(B, N, M) is field 16 of (fixed = 1, K = 1, memory = CALLER): at least field 16 for every
+ *   K and mode, and equal to it whenever front != 0.
+ * -> SPH3D_OK, or SPH3D_EINVAL for a flag outside the above, out == NULL, or arguments the entry point itself rejects (radius,
+ *    nn_sample, dimensions, in that order). */
+#define SPH3D_NN_MEMORY_NONE 0
+#define SPH3D_NN_MEMORY_CALLER 1
+#define SPH3D_NN_MEMORY_LIBRARY 2
+#define SPH3D_NN_PLAN_FIELDS 33
+int sph3d_build_sphere_neighbor_plan(int fixed, int B, int N, int M, int K, float radius, int fuse_wanted, int memory, long long* out);
+
 /* replaces buildCubeNeighborLauncher (tf_nnquery_gpu.cu:123-127; kernel
  * cal_nn_binidx_cube :72-113; op BuildCubeNeighbor tf_nnquery.cpp:116-168).
  * -> nn_index[B,M,K,2] i32 = (database index, cubic bin id), nn_count[B,M]. */

@@ -27,6 +27,7 @@ SIGNATURES = {
     "sph3d_build_sphere_neighbor": (_I, [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "sph3d_build_sphere_neighbor_fixed": (_I, [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "sph3d_build_sphere_neighbor_workspace": (_S, [_I, _I, _I]),
+    "sph3d_build_sphere_neighbor_plan": (_I, [_I] * 5 + [_F, _I, _I, _P]),
     "sph3d_build_sphere_neighbor_ws": (_I, [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _S, _P]),
     "sph3d_build_sphere_neighbor_fixed_ws": (_I, [_I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _S, _P]),
     "sph3d_release_stream_scratch": (_I, [_P]),

@@ -38,7 +38,6 @@
 // positions, all from the grid): 84 -> 60 us.  In the training step (graph stream, beside the feature kernels) the fused graph
 // construction drops from 1.69 to 1.23 ms per step: 1767 -> 1788 blocks/s.
 #include <atomic>
-#include <cstdlib>
 #include "common.hpp"
 #include "sphere_bin.hpp"
 #include "nnquery.hpp"
@@ -47,17 +46,12 @@ namespace sph3d {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kGridMaxCells = 8192;      // LDS histogram of the build kernels (32 KB: they must fit beside the step's other kernels)
 constexpr int kGridMinCells = 512;       // below this 27 cells are too large a share of the cloud
-constexpr int kGridMaxK = 256;           // sorted hit lists of a wave's four queries: 4 * K * 2 B
-constexpr int kGridMaxPos = 8;           // chain positions the grid may take (r_k <= kGridReach * r_0 bounds it further)
-constexpr int kGridReach = 3;            // ... in units of r_0 = cells a query looks in every direction: (2 * 3 + 1)^2 = 49 columns
 
 struct GridHdr {
     float minx, miny, minz, invh;
     int nx, ny, nz, nq;                  // nx == 0: cloud not indexed (the flag is raised); nq: queries in the visiting order
 };
-constexpr int kMaxPositions = 64;        // positions of a chain at M <= 65536 queries
 struct GridRadii {
     float thr[kMaxPositions], rk[kMaxPositions];      // exact threshold T(r_k) and radius of chain position k
 };
@@ -406,7 +400,6 @@ __global__ __launch_bounds__(64) void nngrid_search_kernel(
 // nn_sample hits after a fraction of the cloud — a WAVE per query walks the cloud 128 points per trip in index order and stops
 // there.  No chain state (the radius of position k is tabulated), every query independent: 49 152 waves at S3DIS level 0
 // where the chain kernel walks 1024 chains per cloud one query after the other.  K <= 256 slots in LDS per wave.
-constexpr int kDenseQ = 4;              // queries per wave: they share every trip's points
 template <bool FUSE>
 __global__ __launch_bounds__(256) void nndense_kernel(
     int B, int N, int M, int K, int j0, int parts, int fixed, GraphFuse fx, int* __restrict__ flag, const GridRadii* __restrict__ radii,
@@ -530,7 +523,7 @@ __global__ __launch_bounds__(256) void nndense_kernel(
     }
 }
 
-// Clouds of at most 1024 points (nnsmall_search): no cell grid pays there, and the scan above needs none — what it reads of the
+// Clouds of at most 1024 points (nn_plan.hpp: the front `small`): no cell grid pays there, and the scan above needs none — what it reads of the
 // build kernel's output is the table of thresholds and, per cloud, a header that says "valid, nothing taken by the grid"
 // (nx != 0, nq = 0).  ONE workgroup, a wave per cloud (B <= 32 clouds over 16 waves), writes exactly that and the flag itself: 0, or
 // 1 for non-finite coordinates as the build raises it — so the call needs no memset in front.
@@ -564,174 +557,60 @@ __global__ __launch_bounds__(1024) void nnsmall_prepare_kernel(int B, int N, int
     if (threadIdx.x == 0) *flag = anybad;
 }
 
+static_assert(kNnRefGrid == kRefGrid && kNnRefBlock == kRefBlock, "nn_plan.hpp restates the reference's launch shape");
+static_assert(sizeof(GridHdr) == kNnHdrBytes && sizeof(GridRadii) == kNnRadiiBytes && kNnRadiiOffset + kNnRadiiBytes <= kNnHdrOffset,
+              "nn_plan.hpp lays these out in the search's memory");
+
 static std::atomic<long long> g_grid_launches{0};
 
-// the shapes nnsmall_search takes (minus what depends on K): where the grid declines, every query of a small cloud as an
-// independent wave.  Beyond 32 clouds (two clouds per reference block) the chain kernel keeps the call — and so do batches of
-// one or two clouds: there its launch holds two CUs at most, so a step has nothing to win back from it, and the suite pins
-// those batches to "no workspace, no launch counted" (test_abi, test_gpu_nngrid)
-constexpr int kSmallMinClouds = 3;
-static bool small_shape(int B, int N, int M)
+// The front of a search (nnquery.hpp): the grid's build, query order and search and the scan of the positions behind them, or —
+// small clouds — the prepare launch and the scan of every query.  Sizes, LDS bytes and the layout of `ws` are the plan's.
+int nn_front(NnPlan& p, int fixed, int B, int N, int M, int K, float radius, const float* database, const float* query,
+             int* nn_index, int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t st, void* workspace,
+             size_t workspace_bytes, const int** gate)
 {
-    return B >= kSmallMinClouds && B <= kRefGrid && N >= 1 && N <= 1024 && M >= 1 && M <= kMaxPositions * kRefBlock;
-}
-// ... and their memory: flag, thresholds, one header per cloud
-static size_t small_bytes(int B) { return (1024 + sizeof(GridHdr) * (size_t)B + 15) & ~(size_t)15; }
-
-// The search's device memory (`total` bytes): the caller's workspace (the `_ws` entry points: no allocation, legal under stream
-// capture), or — the convenience entry points with the reference's signature — the library's buffer of this (device, stream);
-// *ws == nullptr afterwards: none.  0, or the error status of a workspace that is too small or misaligned
-static int search_memory(void* workspace, size_t workspace_bytes, bool library_scratch, hipStream_t st, size_t total,
-                         unsigned char** ws)
-{
-    *ws = (unsigned char*)workspace;
-    if (*ws != nullptr) {
-        if (workspace_bytes < total || (reinterpret_cast<size_t>(*ws) & 15) != 0) {
-            set_error("BuildSphereNeighbor: workspace %zu B < required %zu B (or not 16-byte aligned)", workspace_bytes, total);
+    if (p.front == kNnFrontNone) return SPH3D_OK;
+    unsigned char* ws = (unsigned char*)workspace;
+    if (ws != nullptr) {
+        if (workspace_bytes < (size_t)p.workspace_bytes || (reinterpret_cast<size_t>(ws) & 15) != 0) {
+            set_error("BuildSphereNeighbor: workspace %zu B < required %zu B (or not 16-byte aligned)", workspace_bytes,
+                      (size_t)p.workspace_bytes);
             return SPH3D_EWORKSPACE;
         }
-    } else if (library_scratch) {
-        *ws = (unsigned char*)stream_scratch(st, total);
+    } else if ((ws = (unsigned char*)stream_scratch(st, (size_t)p.workspace_bytes)) == nullptr) {
+        p = nn_plan(fixed, B, N, M, K, radius, fuse != nullptr, kNnMemNone);
+        return SPH3D_OK;
     }
+    int* flag = (int*)(ws + p.off_flag);
+    GridRadii* radii = (GridRadii*)(ws + p.off_radii);
+    GridHdr* hdr = (GridHdr*)(ws + p.off_hdr);
+    const GraphFuse fx = p.fused ? *fuse : GraphFuse{};
+    if (p.front == kNnFrontGrid) {
+        int* cellStart = (int*)(ws + p.off_cells);
+        float4* pts = (float4*)(ws + p.off_points);
+        int* qorder = (int*)(ws + p.off_order);
+        int rc = check_hip(hipMemsetAsync(flag, 0, 16, st), "nngrid: memset");
+        if (rc) return rc;
+        hipLaunchKernelGGL(nngrid_build_kernel, dim3((unsigned)p.build_grid), dim3(1024), (size_t)p.build_lds, st, N, M, (int)p.npos,
+                           fixed, radius, database, flag, radii, hdr, cellStart, pts);
+        hipLaunchKernelGGL(nngrid_qorder_kernel, dim3((unsigned)p.order_grid), dim3(1024), (size_t)p.build_lds, st, M, (int)p.nslices,
+                           query, hdr, qorder);
+        hipLaunchKernelGGL(p.fused ? nngrid_search_kernel<true> : nngrid_search_kernel<false>, dim3((unsigned)p.search_grid), dim3(64),
+                           (size_t)p.search_lds, st, B, N, M, K, (int)p.W, (int)p.parts, fixed, fx, flag, radii, hdr, cellStart, pts,
+                           qorder, database, query, nn_index, nn_count, nn_dist);
+    } else {
+        hipLaunchKernelGGL(nnsmall_prepare_kernel, dim3(1), dim3((unsigned)p.prepare_block), 0, st, B, N, M, fixed, radius, database,
+                           flag, radii, hdr);
+    }
+    if (p.dense_grid != 0)          // the queries j >= j0 of every cloud
+        hipLaunchKernelGGL(p.fused ? nndense_kernel<true> : nndense_kernel<false>, dim3((unsigned)p.dense_grid), dim3(256),
+                           (size_t)p.dense_lds, st, B, N, M, K, (int)p.j0, (int)p.dparts, fixed, fx, flag, radii, hdr, database, query,
+                           nn_index, nn_count, nn_dist);
+    int rc = check_launch(p.front == kNnFrontGrid ? "nngrid_search" : "nnsmall_search");
+    if (rc) return rc;
+    g_grid_launches.fetch_add(1, std::memory_order_relaxed);
+    *gate = flag;
     return SPH3D_OK;
-}
-
-// the queries j >= j0 of every cloud
-static void launch_dense(int B, int N, int M, int K, int j0, int fixed, const GraphFuse* fuse, int* flag, const GridRadii* radii,
-                         const GridHdr* hdr, const float* database, const float* query, int* nn_index, int* nn_count,
-                         float* nn_dist, hipStream_t st)
-{
-    const int dparts = (M - j0 + 4 * kDenseQ - 1) / (4 * kDenseQ);
-    const size_t dlds = sizeof(int) * 4 * kDenseQ * (size_t)K;
-    if (fuse != nullptr)
-        hipLaunchKernelGGL(nndense_kernel<true>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fixed,
-                           *fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist);
-    else
-        hipLaunchKernelGGL(nndense_kernel<false>, dim3(xcd_grid(B, dparts)), dim3(256), dlds, st, B, N, M, K, j0, dparts, fixed,
-                           GraphFuse{}, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist);
-}
-
-// bytes of the search's memory of one call.  The cell grid: header + flag, cell starts, the cloud in cell order, the query orders
-size_t nngrid_workspace_bytes(int B, int N, int M)
-{
-    if (B <= 0 || N <= 0 || M <= 0) return 0;
-    // shapes the grid never takes (the same test as nngrid_search, minus what depends on K and the radius mode)
-    if (N < 1024 || N > 65536 || M < 64 || M > kMaxPositions * kRefBlock || (long long)N * M < (1LL << 22))
-        return small_shape(B, N, M) ? small_bytes(B) : 0;
-    const size_t hdrBytes = 1024 + sizeof(GridHdr) * (size_t)B;
-    const size_t csBytes = sizeof(int) * (size_t)B * (kGridMaxCells + 1);
-    const size_t ptBytes = sizeof(float4) * (size_t)B * N;
-    const size_t qoBytes = sizeof(int) * (size_t)B * M;
-    const size_t a16 = 15;
-    return ((hdrBytes + a16) & ~a16) + ((csBytes + a16) & ~a16) + ptBytes + qoBytes;
-}
-
-int nngrid_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
-                  int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t st, const int** gate, int* grid_done,
-                  void* workspace, size_t workspace_bytes, bool library_scratch)
-{
-    // worth it from ~4 M point pairs per cloud (below, the chain kernel's scan of the whole cloud from LDS is as fast as the
-    // grid's build + search: 2048 x 512 measured 60 vs 68 us); the sorted hit lists hold 16-bit indices; with more than 32 clouds
-    // (two clouds per reference block: its chains go on from one to the next) every thread must visit the same number of
-    // queries per cloud, so that a query's position is a function of (cloud, j) alone
-    if (N < 1024 || N > 65536 || M < 64 || M > kMaxPositions * kRefBlock || (long long)N * M < (1LL << 22) || K > kGridMaxK ||
-        (!fixed && B > kRefGrid && ((M >= kRefBlock && M % kRefBlock != 0) ||
-                                    ((B + kRefGrid - 1) / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock) > kMaxPositions)))
-        return 0;
-    // chain positions whose radius stays <= 3 r_0 go through the grid; the later ones find nn_sample hits early in an ascending
-    // scan (nndense_kernel)
-    int npos = 1;
-    if (!fixed) {
-        float rk = radius;
-        while (npos < kGridMaxPos) {
-            rk = (float)((double)rk + 0.05);
-            if (!(rk <= kGridReach * radius)) break;
-            npos++;
-        }
-        const int have = ((B + kRefGrid - 1) / kRefGrid) * ((M + kRefBlock - 1) / kRefBlock);      // positions in use
-        if (npos > have) npos = have;
-    }
-    const size_t hdrBytes = 1024 + sizeof(GridHdr) * (size_t)B;
-    const size_t csBytes = sizeof(int) * (size_t)B * (kGridMaxCells + 1);
-    const size_t ptBytes = sizeof(float4) * (size_t)B * N;
-    const size_t qoBytes = sizeof(int) * (size_t)B * M;
-    const size_t a16 = 15;
-    const size_t total = ((hdrBytes + a16) & ~a16) + ((csBytes + a16) & ~a16) + ptBytes + qoBytes;
-    unsigned char* ws;
-    int rc = search_memory(workspace, workspace_bytes, library_scratch, st, total, &ws);
-    if (rc) return rc;
-    if (ws == nullptr) return 0;          // no memory: no grid
-    int* flag = (int*)ws;
-    GridRadii* radii = (GridRadii*)(ws + 64);
-    GridHdr* hdr = (GridHdr*)(ws + 1024);
-    int* cellStart = (int*)(ws + ((hdrBytes + a16) & ~a16));
-    float4* pts = (float4*)((unsigned char*)cellStart + ((csBytes + a16) & ~a16));
-    int* qorder = (int*)((unsigned char*)pts + ptBytes);
-    rc = check_hip(hipMemsetAsync(flag, 0, 16, st), "nngrid: memset");
-    if (rc) return rc;
-    const size_t ldsBuild = sizeof(int) * (size_t)kGridMaxCells;
-    hipLaunchKernelGGL(nngrid_build_kernel, dim3(B), dim3(1024), ldsBuild, st, N, M, npos, fixed, radius, database, flag,
-                       radii, hdr, cellStart, pts);
-    const int nq = fixed ? M : (M < npos * kRefBlock ? M : npos * kRefBlock);
-    const int nslices = (nq + kRefBlock - 1) / kRefBlock;
-    hipLaunchKernelGGL(nngrid_qorder_kernel, dim3(B * nslices), dim3(1024), ldsBuild, st, M, nslices, query, hdr, qorder);
-    const int parts = (nq + 3) / 4;
-    const int W = ((N + 31) / 32 + 15) & ~15;
-    const size_t lds = (size_t)4 * W * 4 + 4 * 64 * 8 + (size_t)4 * K * 2;
-    GraphFuse fx{};
-    if (fuse != nullptr) fx = *fuse;
-#define SPH3D_GRID(FU)                                                                                                      \
-    do {                                                                                                                    \
-        auto kern = nngrid_search_kernel<FU>;                                                                               \
-        hipLaunchKernelGGL(kern, dim3(xcd_grid(B, parts)), dim3(64), lds, st, B, N, M, K, W, parts, fixed, fx, flag, radii, \
-                           hdr, cellStart, pts, qorder, database, query, nn_index, nn_count, nn_dist);                      \
-    } while (0)
-    if (fuse != nullptr) SPH3D_GRID(true); else SPH3D_GRID(false);
-#undef SPH3D_GRID
-    // the later positions: early-stopping scans.  The first query any cloud leaves to them (the clouds of the last block round
-    // start at the highest positions): the kernel skips the part of a cloud that its grid share covers
-    int j0 = M;
-    if (!fixed) {
-        const int S = (M + kRefBlock - 1) / kRefBlock;
-        int sl = npos - ((B - 1) / kRefGrid) * S;
-        sl = sl < 0 ? 0 : (sl > S ? S : sl);
-        j0 = sl * kRefBlock < M ? sl * kRefBlock : M;
-    }
-    if (j0 < M) launch_dense(B, N, M, K, j0, fixed, fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist, st);
-    rc = check_launch("nngrid_search");
-    if (rc) return rc;
-    g_grid_launches.fetch_add(1, std::memory_order_relaxed);
-    *gate = flag;
-    *grid_done = 1 << 20;          // every query is done unless the flag is up
-    return 1;
-}
-
-// Clouds of at most 1024 points, where the grid declines: the chain kernel would put one 16-wave workgroup per cloud on the
-// device and walk ~48 queries per wave one after the other.  Under the grid's own condition — no empty pass, verified on the
-// device — every query is independent here too (M <= 1024: all at position 0; beyond: the tabulated radii), so the
-// early-stopping scan takes ALL of them, j0 = 0, behind a prepare launch instead of a grid build.  Same contract as
-// nngrid_search: same memory rules, same flag, same counter; the gated chain kernel behind it is the fallback.
-int nnsmall_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
-                   int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t st, const int** gate, int* grid_done,
-                   void* workspace, size_t workspace_bytes, bool library_scratch)
-{
-    if (!small_shape(B, N, M) || K > kGridMaxK) return 0;
-    unsigned char* ws;
-    int rc = search_memory(workspace, workspace_bytes, library_scratch, st, small_bytes(B), &ws);
-    if (rc) return rc;
-    if (ws == nullptr) return 0;
-    int* flag = (int*)ws;
-    GridRadii* radii = (GridRadii*)(ws + 64);
-    GridHdr* hdr = (GridHdr*)(ws + 1024);
-    hipLaunchKernelGGL(nnsmall_prepare_kernel, dim3(1), dim3(64 * (B < 16 ? B : 16)), 0, st, B, N, M, fixed, radius, database, flag,
-                       radii, hdr);
-    launch_dense(B, N, M, K, 0, fixed, fuse, flag, radii, hdr, database, query, nn_index, nn_count, nn_dist, st);
-    rc = check_launch("nnsmall_search");
-    if (rc) return rc;
-    g_grid_launches.fetch_add(1, std::memory_order_relaxed);
-    *gate = flag;
-    *grid_done = 1 << 20;          // every query is done unless the flag is up
-    return 1;
 }
 
 }  // namespace sph3d

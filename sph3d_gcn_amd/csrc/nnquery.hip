@@ -17,6 +17,8 @@
 //     bit patterns (6 rounds) and the inner loop is sub/mul/add/compare only: no sqrt per pair,
 //     bit-identical decisions.
 //   * -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz must round exactly like the oracle.
+#include <stddef.h>
+#include <string.h>
 #include "common.hpp"
 #include "sphere_bin.hpp"
 #include "nnquery.hpp"
@@ -24,10 +26,6 @@
 namespace sph3d {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kWavesPerWG = 16;
-constexpr int kMaxChunk = 12288;   // points per LDS chunk (3 * 12288 * 4 B = 144 KB)
-constexpr int kThrTable = 64;      // positions of the radius sequence with a precomputed threshold
 
 // LDS image of a cloud chunk: blocks of 128 points (one trip of the scan = two strips of 64), each block
 // x[strip 0][64] x[strip 1][64] y[0][64] y[1][64] z[0][64] z[1][64] (384 floats).  A lane's operands for the two strips of
@@ -422,92 +420,72 @@ __global__ void gated_zero_kernel(const int* __restrict__ gate, int* __restrict_
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = 0;
 }
 
-// bytes of LDS for the deferred hit lists (0 = write hits from inside the scan: K too large for LDS lists)
-static size_t hits_bytes(int CPW, int K)
+// the chain kernel of a plan (FUSE only with DEFER: the bins come from the deferred output pass)
+using ChainKernel = decltype(&nnquery_sphere_kernel<1, false, true, false>);
+template <int CPW, bool MULTI>
+static ChainKernel chain_kernel(const NnPlan& p)
 {
-    const size_t b = sizeof(int) * (size_t)kWavesPerWG * CPW * K;
-    return b <= 40 * 1024 ? b : 0;
-}
-
-template <int CPW, bool MULTI, bool DEFER>
-static int launch_sphere(int B, int N, int M, int K, float radius, int chunkN,
-                         const float* database, const float* query,
-                         int* nn_index, int* nn_count, float* nn_dist, hipStream_t stream, int fixed,
-                         const GraphFuse* fuse = nullptr, const int* gate = nullptr, int grid_done = 0)
-{
-    const int nb = B < kRefGrid ? B : kRefGrid;
-    const int nt = M < kRefBlock ? M : kRefBlock;
-    const int groups = (nt + kWavesPerWG * CPW - 1) / (kWavesPerWG * CPW);
-    const size_t lds = (size_t)3 * ((chunkN + 127) & ~127) * sizeof(float) + (DEFER ? hits_bytes(CPW, K) : 0) + kThrTable * sizeof(float);
-    if constexpr (DEFER) {
-        if (fuse != nullptr) {
-            int rc = launch_lds(nnquery_sphere_kernel<CPW, MULTI, DEFER, true>, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream, "nnquery",
-                                B, N, M, K, radius, chunkN, groups, fixed, *fuse, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
-            if (rc) return rc;
-            return check_launch("sph3d_build_sphere_graph");
-        }
-    }
-    int rc = launch_lds(nnquery_sphere_kernel<CPW, MULTI, DEFER, false>, dim3(nb * groups), dim3(kWavesPerWG * 64), lds, stream, "nnquery",
-                        B, N, M, K, radius, chunkN, groups, fixed, GraphFuse{}, database, query, nn_index, nn_count, nn_dist, gate, grid_done);
-    if (rc) return rc;
-    return check_launch("sph3d_build_sphere_neighbor");
+    if (p.fused) return nnquery_sphere_kernel<CPW, MULTI, true, true>;
+    return p.DEFER ? nnquery_sphere_kernel<CPW, MULTI, true, false> : nnquery_sphere_kernel<CPW, MULTI, false, false>;
 }
 
 }  // namespace sph3d
 
 using namespace sph3d;
 
-static int sphere_neighbor(int fixed, int B, int N, int M, int nn_sample, float radius,
-                           const float* database, const float* query,
-                           int* nn_index, int* nn_count, float* nn_dist,
-                           sph3d_stream_t stream, const GraphFuse* fuse = nullptr, bool* fused = nullptr,
-                           void* search_ws = nullptr, size_t search_ws_bytes = 0, bool library_scratch = true)
+// The front's device memory as an entry point has it: the caller's workspace (the `_ws` entries: nothing is allocated, so they are
+// legal under stream capture and independent of any library state — SURVEY 8b: kernels never allocate), else the library's buffer
+// of the stream (the entries with the reference's signature), else none: the chain kernel computes the call (same rows)
+struct SearchMem {
+    void* ws;
+    size_t bytes;
+    bool library;
+    int state() const { return ws != nullptr ? kNnMemCaller : (library ? kNnMemLibrary : kNnMemNone); }      // nn_plan's `memory`
+};
+
+// the plan of a search (nn_plan.hpp) -> SPH3D_EINVAL for arguments it calls bad
+static int search_plan(NnPlan* p, int fixed, int B, int N, int M, int nn_sample, float radius, bool fuse_wanted, int memory)
 {
-    if (fused) *fused = false;
-    SPH3D_REQUIRE(radius > 0, "Range search requires radius>0, got %g", (double)radius);          // tf_nnquery.cpp:60
-    SPH3D_REQUIRE(nn_sample > 0, "BuildSphereNeighbor requires nn_sample>0, got %d", nn_sample);  // :63
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0, "BuildSphereNeighbor: bad dims B=%d N=%d M=%d", B, N, M);
-    if (B == 0 || M == 0) return SPH3D_OK;
+    *p = nn_plan(fixed, B, N, M, nn_sample, radius, fuse_wanted, memory);
+    SPH3D_REQUIRE(p->bad != kNnBadRadius, "Range search requires radius>0, got %g", (double)radius);                // tf_nnquery.cpp:60
+    SPH3D_REQUIRE(p->bad != kNnBadSample, "BuildSphereNeighbor requires nn_sample>0, got %d", nn_sample);          // :63
+    SPH3D_REQUIRE(p->bad != kNnBadDims, "BuildSphereNeighbor: bad dims B=%d N=%d M=%d", B, N, M);
+    return SPH3D_OK;
+}
+
+// ... and its launches: the front, if the plan has one, and the chain kernel behind it.  `fuse`: what sph3d_build_sphere_graph*
+// adds to the output passes (read when p.fused)
+static int search_launch(NnPlan p, int fixed, int B, int N, int M, int nn_sample, float radius, const float* database,
+                         const float* query, int* nn_index, int* nn_count, float* nn_dist, sph3d_stream_t stream,
+                         const SearchMem& mem, const GraphFuse* fuse = nullptr)
+{
+    if (p.chain_grid == 0) return SPH3D_OK;
     hipStream_t st = as_stream(stream);
-    const long long chains = (long long)(B < kRefGrid ? B : kRefGrid) * (M < kRefBlock ? M : kRefBlock);
-    const int cpw = chains >= 256LL * kWavesPerWG * 4 ? 4 : (chains >= 256LL * kWavesPerWG * 2 ? 2 : 1);
-    // LDS: the cloud chunk (12 B per point) next to the deferred hit lists
-    size_t hb = hits_bytes(cpw, nn_sample);
-    int maxChunk = (int)((160 * 1024 - kThrTable * 4 - hb) / 12) & ~127;      // whole trips of 128 points
-    if (maxChunk > kMaxChunk) maxChunk = kMaxChunk;
-    int chunkN = N < maxChunk ? N : maxChunk;
-    const bool multi = N > chunkN;
-    if (multi) {
-        hb = hits_bytes(1, nn_sample);
-        maxChunk = (int)((160 * 1024 - kThrTable * 4 - hb) / 12) & ~127;
-        if (maxChunk > kMaxChunk) maxChunk = kMaxChunk;
-        chunkN = maxChunk;
-    }
-    if (fused) *fused = (fuse != nullptr) && hb != 0;       // the bins come from the deferred output pass
-    if (hb == 0) fuse = nullptr;
-    // The cell-grid search first (nngrid.hip): complete unless some query has no neighbour inside the nominal radius — then
-    // (device flag `gate`) the chain kernel below recomputes the call, after the fused counters have been cleared again.
+    if (!p.fused) fuse = nullptr;
+    // The front first: complete unless some query has no neighbour inside the nominal radius — then (device flag `gate`) the chain
+    // kernel below recomputes the call, after the fused counters have been cleared again.
     const int* gate = nullptr;
-    int grid_done = 0;
-    int g = nngrid_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
-                          &grid_done, search_ws, search_ws_bytes, library_scratch);
-    // ... and where it declines, clouds of at most 1024 points through its early-stopping scan alone (same flag, same fallback)
-    if (g == 0)
-        g = nnsmall_search(B, N, M, nn_sample, radius, fixed, database, query, nn_index, nn_count, nn_dist, fuse, st, &gate,
-                           &grid_done, search_ws, search_ws_bytes, library_scratch);
-    if (g < 0) return g;
-    if (g > 0 && fuse != nullptr && fuse->deg != nullptr) {
-        const long long cnt = (long long)B * N * fuse->F + fuse->F;
-        hipLaunchKernelGGL(gated_zero_kernel, dim3(256), dim3(256), 0, st, gate, fuse->deg, cnt);
-    }
-#define SPH3D_NN(CP, MU)                                                                                          \
-    return hb ? launch_sphere<CP, MU, true>(B, N, M, nn_sample, radius, chunkN, database, query, nn_index, nn_count, nn_dist, st, fixed, fuse, gate, grid_done) \
-              : launch_sphere<CP, MU, false>(B, N, M, nn_sample, radius, chunkN, database, query, nn_index, nn_count, nn_dist, st, fixed, nullptr, gate, grid_done)
-    if (multi) { SPH3D_NN(1, true); }
-    if (cpw == 4) { SPH3D_NN(4, false); }
-    if (cpw == 2) { SPH3D_NN(2, false); }
-    SPH3D_NN(1, false);
-#undef SPH3D_NN
+    int rc = nn_front(p, fixed, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, fuse, st, mem.ws, mem.bytes,
+                      &gate);
+    if (rc) return rc;
+    if (p.clear_counts != 0 && fuse->deg != nullptr)
+        hipLaunchKernelGGL(gated_zero_kernel, dim3(256), dim3(256), 0, st, gate, fuse->deg, p.clear_counts * fuse->F);
+    const ChainKernel kern = p.MULTI ? chain_kernel<1, true>(p)
+                                     : (p.CPW == 4 ? chain_kernel<4, false>(p) : (p.CPW == 2 ? chain_kernel<2, false>(p) : chain_kernel<1, false>(p)));
+    rc = launch_lds(kern, dim3((unsigned)p.chain_grid), dim3(kWavesPerWG * 64), (size_t)p.chain_lds, st, "nnquery", B, N, M, nn_sample,
+                    radius, (int)p.chunkN, (int)p.groups, fixed, fuse ? *fuse : GraphFuse{}, database, query, nn_index, nn_count, nn_dist,
+                    gate, (int)p.grid_done);
+    if (rc) return rc;
+    return check_launch(fuse ? "sph3d_build_sphere_graph" : "sph3d_build_sphere_neighbor");
+}
+
+static int sphere_neighbor(int fixed, int B, int N, int M, int nn_sample, float radius, const float* database, const float* query,
+                           int* nn_index, int* nn_count, float* nn_dist, sph3d_stream_t stream, const SearchMem& mem)
+{
+    NnPlan p;
+    int rc = search_plan(&p, fixed, B, N, M, nn_sample, radius, false, mem.state());
+    if (rc) return rc;
+    return search_launch(p, fixed, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, mem);
 }
 
 extern "C" int sph3d_build_sphere_neighbor(int B, int N, int M, int nn_sample, float radius,
@@ -515,7 +493,7 @@ extern "C" int sph3d_build_sphere_neighbor(int B, int N, int M, int nn_sample, f
                                            int* nn_index, int* nn_count, float* nn_dist,
                                            sph3d_stream_t stream)
 {
-    return sphere_neighbor(0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream);
+    return sphere_neighbor(0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, {nullptr, 0, true});
 }
 
 extern "C" int sph3d_build_sphere_neighbor_fixed(int B, int N, int M, int nn_sample, float radius,
@@ -523,21 +501,39 @@ extern "C" int sph3d_build_sphere_neighbor_fixed(int B, int N, int M, int nn_sam
                                                  int* nn_index, int* nn_count, float* nn_dist,
                                                  sph3d_stream_t stream)
 {
-    return sphere_neighbor(1, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream);
+    return sphere_neighbor(1, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, {nullptr, 0, true});
 }
 
-// ---- the same searches with the cell grid's memory from the caller: nothing is allocated, so the calls are legal under stream
-// capture and independent of any library state (kernels never allocate).  workspace == NULL: no grid, the chain
-// kernel computes the call (same rows).
-extern "C" size_t sph3d_build_sphere_neighbor_workspace(int B, int N, int M) { return nngrid_workspace_bytes(B, N, M); }
+// the bytes of the front that some K <= kGridMaxK and radius mode give the shape (0: none takes it)
+extern "C" size_t sph3d_build_sphere_neighbor_workspace(int B, int N, int M)
+{
+    return (size_t)nn_plan(1, B, N, M, 1, 1.0f, false, kNnMemCaller).workspace_bytes;
+}
+
+extern "C" int sph3d_build_sphere_neighbor_plan(int fixed, int B, int N, int M, int K, float radius, int fuse_wanted, int memory,
+                                                long long* out)
+{
+    SPH3D_REQUIRE(out != nullptr && (fixed == 0 || fixed == 1) && (fuse_wanted == 0 || fuse_wanted == 1) && memory >= kNnMemNone &&
+                      memory <= kNnMemLibrary,
+                  "sph3d_build_sphere_neighbor_plan: bad argument (fixed=%d fuse_wanted=%d memory=%d out=%p)", fixed, fuse_wanted, memory,
+                  (void*)out);
+    NnPlan p;
+    int rc = search_plan(&p, fixed, B, N, M, K, radius, fuse_wanted != 0, memory);
+    if (rc) return rc;
+    static_assert(offsetof(NnPlan, bad) == SPH3D_NN_PLAN_FIELDS * sizeof(long long), "the plan starts with the documented fields, in their order");
+    static_assert(kNnMemNone == SPH3D_NN_MEMORY_NONE && kNnMemCaller == SPH3D_NN_MEMORY_CALLER && kNnMemLibrary == SPH3D_NN_MEMORY_LIBRARY,
+                  "the memory states as the header numbers them");
+    memcpy(out, &p, SPH3D_NN_PLAN_FIELDS * sizeof(long long));
+    return SPH3D_OK;
+}
 
 extern "C" int sph3d_build_sphere_neighbor_ws(int B, int N, int M, int nn_sample, float radius,
                                               const float* database, const float* query,
                                               int* nn_index, int* nn_count, float* nn_dist,
                                               void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    return sphere_neighbor(0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, nullptr, nullptr,
-                           workspace, workspace_bytes, false);
+    return sphere_neighbor(0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream,
+                           {workspace, workspace_bytes, false});
 }
 
 extern "C" int sph3d_build_sphere_neighbor_fixed_ws(int B, int N, int M, int nn_sample, float radius,
@@ -545,26 +541,18 @@ extern "C" int sph3d_build_sphere_neighbor_fixed_ws(int B, int N, int M, int nn_
                                                     int* nn_index, int* nn_count, float* nn_dist,
                                                     void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    return sphere_neighbor(1, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, nullptr, nullptr,
-                           workspace, workspace_bytes, false);
+    return sphere_neighbor(1, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream,
+                           {workspace, workspace_bytes, false});
 }
 
 // Fused graph construction of one level: neighbour search + spherical-kernel bins (+ the segment counts of
 // the transposed graph) in ONE kernel.  Same outputs, bit for bit, as sph3d_build_sphere_neighbor followed by
 // sph3d_spherical_kernel with the same database / query (and sph3d_graph_transpose's counting pass).
-extern "C" int sph3d_spherical_kernel(int B, int N, int M, int K, int n, int p, int q, float radius,
-                                      const float* database, const float* query,
-                                      const int* nn_index, const int* nn_count, const float* nn_dist,
-                                      int* filt_index, sph3d_stream_t stream);
-extern "C" int sph3d_graph_transpose_count(int B, int N, int M, int K, int F, const int* nn_index, const int* nn_count,
-                                           const int* bin_index, int want_active, void* workspace, size_t workspace_bytes,
-                                           sph3d_stream_t stream);
-
 static int build_sphere_graph_impl(bool ocml, int B, int N, int M, int nn_sample, float radius, int n, int p, int q,
                                    const float* database, const float* query,
                                    int* nn_index, int* nn_count, float* nn_dist, int* filt_index,
                                    void* transpose_workspace, size_t transpose_workspace_bytes, sph3d_stream_t stream,
-                                   void* search_ws = nullptr, size_t search_ws_bytes = 0, bool library_scratch = true)
+                                   const SearchMem& mem = {nullptr, 0, true})
 {
     // filt_index == NULL: no bins (an inter-level graph: one segment per source point), only the search and the counts
     const bool binned = filt_index != nullptr;
@@ -595,10 +583,10 @@ static int build_sphere_graph_impl(bool ocml, int B, int N, int M, int nn_sample
         int rc = zero_async(w.deg, sizeof(int) * w.zero_words, as_stream(stream), "build_sphere_graph: memset");
         if (rc) return rc;
     }
-    bool fused = false;
-    int rc = sphere_neighbor(0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, &fx, &fused,
-                             search_ws, search_ws_bytes, library_scratch);
-    if (rc || fused) return rc;
+    NnPlan plan;
+    int rc = search_plan(&plan, 0, B, N, M, nn_sample, radius, true, mem.state());
+    if (rc == SPH3D_OK) rc = search_launch(plan, 0, B, N, M, nn_sample, radius, database, query, nn_index, nn_count, nn_dist, stream, mem, &fx);
+    if (rc || plan.fused) return rc;
     // shapes whose hit lists do not fit LDS: the same results from the separate kernels
     if (binned)
         rc = ocml ? sph3d_spherical_kernel_ocml(B, N, M, nn_sample, n, p, q, radius, database, query, nn_index, nn_count, nn_dist, filt_index, stream)
@@ -633,8 +621,8 @@ extern "C" int sph3d_build_sphere_graph_ws(int B, int N, int M, int nn_sample, f
                                            void* search_workspace, size_t search_workspace_bytes, sph3d_stream_t stream)
 {
     return build_sphere_graph_impl(ocml != 0, B, N, M, nn_sample, radius, n, p, q, database, query, nn_index, nn_count, nn_dist,
-                                   filt_index, transpose_workspace, transpose_workspace_bytes, stream, search_workspace,
-                                   search_workspace_bytes, false);
+                                   filt_index, transpose_workspace, transpose_workspace_bytes, stream,
+                                   {search_workspace, search_workspace_bytes, false});
 }
 
 extern "C" int sph3d_build_cube_neighbor(int B, int N, int M, int grid_size, int nn_sample, float length,

@@ -2,6 +2,7 @@
 // nngrid.hip: the cell-grid search that replaces it whenever no query needs the reference's radius growth).
 #pragma once
 #include "common.hpp"
+#include "nn_plan.hpp"
 
 namespace sph3d {
 
@@ -58,24 +59,16 @@ struct GraphFuse {
     int ocml;                // 1: the device library's atan2f (the reference as it builds here), 0: the shared correctly rounded one
 };
 
-// nngrid.hip.  Tries the cell-grid search: 0 = not applicable (nothing launched, *gate untouched); 1 = launched; < 0 = error
-// status.  Launched, it has produced the rows of the queries at the first *grid_done positions of every chain (reference
-// thread t visits queries t, t + 1024, ...: position = j / 1024; in `fixed` mode: of all queries) UNLESS the device flag *gate
-// reads non-zero afterwards: a query without a neighbour inside its radius (the reference grows the radius there, and every
-// later position of the chain with it), a grid too coarse to pay, non-finite coordinates.  The chain kernel runs behind it
-// and reads the flag: it starts at position *grid_done, or at 0 when the flag is up.
-// The grid's device memory (nngrid_workspace_bytes) is `workspace` when the caller gave one (too small: SPH3D_EWORKSPACE), else the
-// library's per-(device, stream) buffer when library_scratch is set, else the grid is not used (0).
-int nngrid_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
-                  int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t stream, const int** gate, int* grid_done,
-                  void* workspace, size_t workspace_bytes, bool library_scratch);
-// Where the grid declines and the cloud has at most 1024 points (3 <= B <= 32, K <= 256): every query through the grid's
-// early-stopping scan, no grid.  Same arguments, same return values, same flag and memory rules as nngrid_search.
-int nnsmall_search(int B, int N, int M, int K, float radius, int fixed, const float* database, const float* query, int* nn_index,
-                   int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t stream, const int** gate, int* grid_done,
-                   void* workspace, size_t workspace_bytes, bool library_scratch);
-// bytes of `workspace` for either of them (0: the shape is the chain kernel's)
-size_t nngrid_workspace_bytes(int B, int N, int M);
-
+// nngrid.hip.  Launches the front of plan `p` (nn_plan.hpp), if it has one: the cell-grid search and / or the early-stopping scans.
+// They have produced the rows of the queries at the first p.grid_done positions of every chain (reference thread t visits queries
+// t, t + 1024, ...: position = j / 1024) UNLESS the device flag *gate reads non-zero afterwards: a query without a neighbour
+// inside its radius (the reference grows the radius there, and every later position of the chain with it), a grid too coarse to
+// pay, non-finite coordinates.  The chain kernel runs behind it and reads the flag: it starts at position p.grid_done, or at 0 when
+// the flag is up.  The front's device memory (p.workspace_bytes) is `workspace` when the caller gave one (too small or misaligned:
+// SPH3D_EWORKSPACE), else the library's per-(device, stream) buffer; where the library has none, `p` becomes the plan without a
+// front and nothing is launched.  -> status; *gate is set when a front was launched.
+int nn_front(NnPlan& p, int fixed, int B, int N, int M, int K, float radius, const float* database, const float* query,
+             int* nn_index, int* nn_count, float* nn_dist, const GraphFuse* fuse, hipStream_t stream, void* workspace,
+             size_t workspace_bytes, const int** gate);
 
 }  // namespace sph3d
