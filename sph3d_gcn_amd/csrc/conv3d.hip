@@ -396,7 +396,7 @@ constexpr int kBwdNL4 = 2;     // ... of the quarter-wave form (4 edges per load
 //            chunk anyway), add their grad_input partial sums with float atomics (order not fixed — as the order of a segment's
 //            entries already is not) and keep the filter gradient in their accumulators like every other wave: slabs
 //            slabBase .. slabBase + hubW - 1 of `partial`.
-//   HUB = 0 (every other launch, the headline's among them): neither — the instantiations of rounds 1-5, unchanged.
+//   HUB = 0 (every other launch, the headline's among them): neither.
 template <int R, int V, int MAXF, int PARTS, bool COMPACT, int HUB = 0>
 __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t_vec(
     int B, int N, int M, int F, int C, int W, int parts, int nslices,
@@ -482,16 +482,71 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
     const float* __restrict__ gou = gradOutput + (size_t)b * M * CR + slice0;
     const unsigned cla = (unsigned)(act ? cl0 : 0);
     const int* __restrict__ offb = offsets + (size_t)b * ((size_t)N * F + 1);
-    for (int p = HUB == 2 ? 0 : pi + parts * (w * kBwdTWaves + wave); HUB == 2 ? p < 1 : p < N; p += HUB == 2 ? 1 : parts * stride) {
-        const int n = HUB == 2 ? hubSrc - b * N : (order ? uniform(order[(size_t)b * N + p]) : p);
-        // the source's F+1 segment bounds: ONE coalesced read (lane f holds bound f), consumed with v_readlane at
-        // compile-time lanes — not 33 dependent scalar loads (measured: they dominated the sparse levels)
-        const int* __restrict__ o = offb + (size_t)n * F;
-        const int ov0 = o[lane <= F ? lane : F];
-        const int ov1 = (MAXF >= 64) ? o[(64 + lane) <= F ? (64 + lane) : F] : 0;
+    // The index chain of a source — position -> order[] -> n -> bounds row and [E0, E1) -> the first 64 keys -> gathers — is three
+    // dependent round trips that move no payload, and everything in it is known before the source in front has begun.  So
+    // (HUB < 2) it runs ahead of the walk: at the top of the body for position p the wave issues order[] for p + 3 steps, E0 / E1
+    // for p + 2 steps (scalar loads: SGPRs only), and the bounds row and the first key chunk for p + 1 step (one VGPR each, two
+    // for the bounds where MAXF >= 64); the walk of p hides them.  Which wave takes which source and the order of every sum are
+    // untouched.  A position past the cloud's end stands for position N - 1, whose index data is in range and read for nothing.
+    const int pstep = HUB == 2 ? 1 : parts * stride;
+    const int pfirst = HUB == 2 ? 0 : pi + parts * (w * kBwdTWaves + wave);
+    if (HUB != 2 && pfirst >= N) continue;
+    auto src_at = [&](int q) {
+        const int qc = q < N ? q : N - 1;
+        return order ? uniform(order[(size_t)b * N + qc]) : qc;
+    };
+    // the source's F+1 segment bounds: ONE coalesced read (lane f holds bound f), consumed with v_readlane at
+    // compile-time lanes — not 33 dependent scalar loads (measured: they dominated the sparse levels)
+    // (here and below: a wave-uniform row pointer indexed with an unsigned lane offset — an SGPR pair + one 32-bit VGPR per load.
+    // lane_offset() hides the offset from loop-invariant code motion, which otherwise adds it to the cloud's base pointer once
+    // per item and keeps that 64-bit per-lane address in two VGPRs through the whole walk: there is no room for them)
+    auto lane_offset = [](int i) {
+        unsigned u = (unsigned)i;
+        asm volatile("" : "+v"(u));
+        return u;
+    };
+    auto bounds0 = [&](int nn) { return (offb + (size_t)nn * F)[lane_offset(lane <= F ? lane : F)]; };
+    auto bounds1 = [&](int nn) { return (MAXF >= 64) ? (offb + (size_t)nn * F)[lane_offset((64 + lane) <= F ? (64 + lane) : F)] : 0; };
+    // the first min(64, E1 - E0) keys of a source, lanes past them clamped to the first; a source without in-edges reads nothing
+    auto keys0 = [&](int e0, int e1) {
+        const int c = (e1 - e0) < 64 ? (e1 - e0) : 64;
+        return e1 > e0 ? (entKey + e0)[(unsigned)(lane < c ? lane : 0)] : 0;
+    };
+    int n1 = 0, n2 = 0, n3 = 0, E0n = 0, E1n = 0, E0nn = 0, E1nn = 0, ovn0 = 0, ovn1 = 0, wkn = 0;
+    if (HUB != 2) {
+        n1 = src_at(pfirst);
+        n2 = src_at(pfirst + pstep);
+        n3 = src_at(pfirst + 2 * pstep);
+        E0n = uniform(offb[(size_t)n1 * F]);
+        E1n = uniform(offb[(size_t)n1 * F + F]);
+        E0nn = uniform(offb[(size_t)n2 * F]);
+        E1nn = uniform(offb[(size_t)n2 * F + F]);
+        ovn0 = bounds0(n1);
+        ovn1 = bounds1(n1);
+        wkn = keys0(E0n, E1n);
+    }
+    for (int p = pfirst; HUB == 2 ? p < 1 : p < N; p += pstep) {
+        int n, ov0, ov1, E0, E1, wkey0 = 0;
+        if (HUB == 2) {
+            n = hubSrc - b * N;
+            ov0 = bounds0(n);
+            ov1 = bounds1(n);
+            E0 = __builtin_amdgcn_readlane(ov0, 0);
+            E1 = uniform(offb[(size_t)n * F + F]);
+        } else {
+            // this source's index data arrived under the walk of the one before; the next ones' loads go out now
+            n = n1, ov0 = ovn0, ov1 = ovn1, E0 = E0n, E1 = E1n, wkey0 = wkn;
+            n1 = n2, n2 = n3, E0n = E0nn, E1n = E1nn;
+            n3 = src_at(p + 3 * pstep);
+            E0nn = uniform(offb[(size_t)n2 * F]);
+            E1nn = uniform(offb[(size_t)n2 * F + F]);
+            ovn0 = bounds0(n1);
+            ovn1 = bounds1(n1);
+            wkn = keys0(E0n, E1n);
+        }
         float xi[VI], xv[V];
 #pragma unroll
-        for (int u = 0; u < VI; u++) xi[u] = xin[((size_t)b * N + n) * Cs + (act ? cin0 : slice0 / R) + u];
+        for (int u = 0; u < VI; u++) xi[u] = (xin + ((size_t)b * N + n) * Cs)[lane_offset(act ? cin0 : slice0 / R) + u];
 #pragma unroll
         for (int v = 0; v < V; v++) xv[v] = xi[(V >= R) ? v / R : 0];
         float gi[V];
@@ -503,8 +558,6 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
         // edge, 64-bit scalar address arithmetic, clamps): 16.8 scalar-ALU + 2.7 scalar-memory instructions per edge =
         // half of the CU's one-per-cycle scalar issue for the whole kernel, and a dependent s_load -> gather round
         // trip per batch of four edges.
-        const int E0 = __builtin_amdgcn_readlane(ov0, 0);
-        const int E1 = uniform(o[F]);
         // COMPACT: which accumulator rows have a non-empty segment at this source (about half of the 17 do not): one mask per
         // source instead of two v_readlane + clamps + compare per empty segment
         unsigned long long nonempty = ~0ull;
@@ -512,7 +565,8 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
             const int fl = lane < MAXF ? abv : 0;
             const int s0 = __builtin_amdgcn_ds_bpermute(fl << 2, ov0);
             const int s1 = __builtin_amdgcn_ds_bpermute((fl + 1) << 2, ov0);
-            nonempty = __ballot(s1 > s0);
+            // (rows past the A-th folded in here: `fi < A` per row kept 17 hoisted wave masks alive through the whole walk)
+            nonempty = __ballot(s1 > s0 && lane < A);
         }
         if (HUB == 1 && (E1 - E0) > hubT) {
             // a hub: left to the hub kernel (every slice's wave decides the same from the degree alone; the list holds each source once)
@@ -526,19 +580,27 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
         }
         const int cfirst = HUB == 2 ? E0 + 64 * ((w % kHubGroup) * kBwdTWaves + wave) : E0;
         const int cstep = HUB == 2 ? 64 * kHubGroup * kBwdTWaves : 64;
-        for (int cb = cfirst; cb < E1; cb += cstep) {
-        const int cn = (E1 - cb) < 64 ? (E1 - cb) : 64;
-        const int li = lane < cn ? lane : 0;
-        // (entScale == NULL: packed entries, common.hpp: row and count in one word, 1 / count divided here: once per lane and chunk)
-        const int wkey = entKey[cb + li];
-        const unsigned kel = (unsigned)tg_key(wkey, entScale == nullptr) * (unsigned)CR;     // row offset in floats (M * CR < 2^32, checked by the launcher)
-        const float svl = entScale == nullptr ? tg_packed_scale(wkey) : entScale[cb + li];
-        const float sv = lane < cn ? svl : 0.f;
+        // the chunk at cb: its edge count, row offsets and scales; the first chunk's keys came with the prefetch (HUB < 2), a later
+        // chunk's are loaded at the foot of the loop
+        int cb = cfirst, cn = 0;
+        unsigned kel = 0u;
+        float sv = 0.f;
+        auto take_chunk = [&](bool prefetched) {
+            cn = (E1 - cb) < 64 ? (E1 - cb) : 64;
+            const int li = lane < cn ? lane : 0;
+            // (entScale == NULL: packed entries, common.hpp: row and count in one word, 1 / count divided here: once per lane and chunk)
+            const int wkey = prefetched ? wkey0 : (entKey + cb)[(unsigned)li];
+            kel = (unsigned)tg_key(wkey, entScale == nullptr) * (unsigned)CR;     // row offset in floats (M * CR < 2^32, checked by the launcher)
+            const float svl = entScale == nullptr ? tg_packed_scale(wkey) : (entScale + cb)[(unsigned)li];
+            sv = lane < cn ? svl : 0.f;
+        };
+        if (cb < E1) take_chunk(HUB != 2);
+        while (cb < E1) {
 #pragma unroll
         for (int fi = 0; fi < MAXF; fi++) {
             // the mask exists for the compact table only (MAXF <= 64 there); the full table of the V = 2 plan has MAXF = 65 and a
             // shift by 64 would be undefined — and let the compiler drop bin 64 altogether
-            if (fi < (COMPACT ? A : F) && (!COMPACT || ((nonempty >> (fi & 63)) & 1ull))) {
+            if (COMPACT ? ((nonempty >> (fi & 63)) & 1ull) != 0ull : fi < F) {
                 // COMPACT: row fi of the accumulators belongs to bin activeBins[1 + fi] (wave-uniform, F <= 63)
                 const int f = COMPACT ? __builtin_amdgcn_readlane(abv, fi) : fi;
                 const int a0 = COMPACT ? __builtin_amdgcn_readlane(ov0, f)
@@ -638,6 +700,8 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
                 }
             }
         }
+        cb += cstep;
+        if (cb < E1) take_chunk(false);
         }   // chunks of 64 in-edges
         if (HALF) {
 #pragma unroll
@@ -647,7 +711,7 @@ __global__ __launch_bounds__(kBwdTWaves * 64, COMPACT ? 4 : 3) void dwconv_bwd_t
             }
         }
         if (act && half == 0) {
-            float* gp = &gin[((size_t)b * N + n) * Cs + cin0];
+            float* gp = &(gin + ((size_t)b * N + n) * Cs)[lane_offset(cin0)];
             if (V >= R) {
 #pragma unroll
                 for (int u = 0; u < VI; u++) {

@@ -25,3 +25,14 @@ for C, r in ((32, 1), (32, 2), (64, 1), (64, 2), (128, 1), (128, 2), (256, 1), (
     tf = timeit(lambda: tf_conv3d.depthwise_conv3d(x, w, nidx, cnt, filt))
     print("C %4d r %d row %5d B cloud %5.1f MB | grad %7.1f us  %5.1f TB/s gathered | fwd %7.1f us %5.1f TB/s (row %4d B)" % (
         C, r, C * r * 4, N * C * r * 4 / 1e6, tb, edges * C * r * 4 / tb / 1e6, tf, edges * C * 4 / tf / 1e6, C * 4))
+# one deep-level call (16 x 768 farthest points of the same clouds, radius 0.4, C = 256, r = 2): the launches that are all per-source floor
+from sph3d_gcn_amd import tf_sample
+Nd, C, r = 768, 256, 2
+sel = tf_sample.farthest_point_sample(Nd, xyz).long()
+xd = torch.gather(xyz, 1, sel.unsqueeze(-1).expand(B, Nd, 3)).contiguous()
+nidx, cnt, dst = tf_nnquery.build_sphere_neighbor(xd, xd, 0.4, None, K)
+filt = tf_buildkernel.spherical_kernel(xd, xd, nidx, cnt, dst, 0.4, [8, 2, 2])
+x = torch.randn(B, Nd, C, device=dev); w = torch.randn(33, C, r, device=dev); go = torch.randn(B, Nd, C * r, device=dev)
+tb = timeit(lambda: tf_conv3d.depthwise_conv3d_grad(x, w, go, nidx, cnt, filt), n=50)
+print("deep level: %d x %d, %d edges, C %d r %d | grad %7.1f us = %.2f us of wave time per source" % (
+    B, Nd, int(cnt.sum()), C, r, tb, tb * 256 * 16 / (B * Nd * 2)))
