@@ -816,6 +816,23 @@ int sph3d_objfeed_assemble(int B, int num_point, int num_blocks, long long total
                            const int* shape_ids, unsigned long long seed, unsigned long long step, const int* recipe,
                            float* points, int* label, int* index, sph3d_stream_t stream);
 
+/* ---- the input side of the ScanNet line (scannet_seg/train_scannet.py:112-127, evaluate_scannet_withoverlap.py:94-116,282-286)
+ * on the device: one launch assembles ALL views of one draw from a resident pool of blocks.  The pool is sph3d_feed_assemble's
+ * (rows [T,8]: xyz, rgb, label, inner; offsets [P+1]; block_ids [B] int32, device), and so are the sample draws: index, label and
+ * inner are the same pure function of (seed, step, b, n, num_point), whatever the recipes, and equal what
+ * sph3d_feed_assemble(..., augment = 0) writes bit for bit.  recipe [views,B] int32 (device): the bit masks, purposes and
+ * counters of sph3d_objfeed_assemble.  View v's xyz is recipe[v][b] applied to the fp32 xyz of view v - 1 (view -1: the pool
+ * row) — the reference augments its float32 batch in place, view after view — with its transform draws taken from
+ * feed_view_key(ck, v) (csrc/feed_draws.hpp): view 0's key is the cloud's own, so a one-view launch draws exactly what
+ * sph3d_objfeed_assemble draws; view v >= 1 uses one more splitmix round over (ck, v).  A mask of 0 copies the previous view bit
+ * for bit; rgb is copied into every view (csrc/scanfeed.hip; harness/scannet.py states it in numpy).
+ * -> points [views,B,num_point,6] fp32 (8-byte aligned); label, inner [B,num_point] int32; index [B,num_point] int32 (nullable).
+ * A block id outside [0, P) or an offset pair outside [0, T] reads nothing: zeros in every view, label 0, inner 0, index -1.
+ * 1 <= views <= 4, B <= 65535, views * B * num_point <= 2^31 - 1. */
+int sph3d_blockfeed_assemble(int B, int num_point, int num_blocks, long long total_rows, const float* rows, const long long* offsets,
+                             const int* block_ids, unsigned long long seed, unsigned long long step, int views, const int* recipe,
+                             float* points, int* label, int* inner, int* index, sph3d_stream_t stream);
+
 /* ---- the input side of the RueMonge2014 facade line (ruemonge2014_seg/train_ruemonge2014.py:98-138,159,
  * ruemonge2014_seg/evaluate_ruemonge2014.py:180-305, utils/data_util.py:64-105; records: io/make_tfrecord_ruemonge2014.py:45-57) on
  * the device: one launch assembles a batch of 9-channel clouds from a resident pool of facade splits.  The pool is

@@ -97,7 +97,8 @@ SIGNATURES = {
     "sph3d_dropout_keyed": (_I, [_I, _L, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _L, _I, ctypes.c_uint, _F, _P]),
     "sph3d_feed_assemble": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I] + [_P] * 5),
     "sph3d_objfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
-    "sph3d_facadefeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
+    "sph3d_blockfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I, _P] + [_P] * 4 + [_P]),
+    "sph3d_facadefeed_assemble": (_I,[_I, _I, _I, _L, _P, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
     "sph3d_shape_iou": (_I, [_I, _I, _I, _L, _P, _P, _P, _L, _L, _P, _P, _P] + [_P] * 6 + [_P]),
     "sph3d_clsfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P, _I, _I, _P, _P, _P]),
     "sph3d_cls_vote_accumulate": (_I, [_I, _I, _P, _I, _I, _P, _P, _P, _I, _P]),

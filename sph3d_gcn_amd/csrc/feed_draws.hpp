@@ -1,6 +1,8 @@
-// feed_draws.hpp — the counter-based draws the feed kernels share (feed.hip, objfeed.hip); harness/feed.py states them in numpy.
+// feed_draws.hpp — the counter-based draws the feed kernels share (feed.hip, objfeed.hip, scanfeed.hip); harness/feed.py states
+// them in numpy.
 //
 //   cloud key   ck = mix(mix(mix(seed + G) + step + G) + b + G)           mix = the splitmix64 finaliser, G = 0x9e3779b97f4a7c15
+//   view key    vk(ck, 0) = ck,  vk(ck, v) = mix(ck + v + G) for v >= 1   (harness/scannet.py: view_key)
 //   a draw      w(purpose, counter) = mix(ck ^ (purpose << 56 | counter))    64 bits; "bits" = its high word
 //   n >= N      slot j takes pi(j): a 6-round balanced Feistel network over 2 * ceil(k / 2) bits (2^k >= n > 2^(k-1)), walked
 //               until it lands below n;  n < N: slot j takes mulhi(bits, n)
@@ -26,6 +28,13 @@ __host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long lo
 __host__ __device__ __forceinline__ unsigned long long feed_cloud_key(unsigned long long seed, unsigned long long step, unsigned b)
 {
     return feed_mix(feed_mix(feed_mix(seed + kFeedGold) + step + kFeedGold) + b + kFeedGold);
+}
+// the key view v of a cloud takes its TRANSFORM draws from (scanfeed.hip: several views of one sample): view 0 is the cloud's own
+// key, so a one-view launch draws what objfeed.hip draws; a later view is one more round over (ck, v).  The sample draws
+// (kFeedPerm, kFeedRepl) always use ck itself.
+__host__ __device__ __forceinline__ unsigned long long feed_view_key(unsigned long long ck, unsigned v)
+{
+    return v == 0u ? ck : feed_mix(ck + v + kFeedGold);
 }
 __device__ __forceinline__ unsigned long long feed_draw(unsigned long long ck, unsigned long long purpose, unsigned counter)
 {

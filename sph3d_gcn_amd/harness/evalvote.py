@@ -3,7 +3,8 @@ sph3d_vote_begin / _accumulate / _finalize) — what s3dis_seg/evaluate_s3dis_wi
 numpy on the host after copying every pass's logits back.
 
 Every test block is sampled to `num_point` points again and again until each of its INNER rows (column 7 of the pool's rows
-== 1) has been drawn `min_votes` times (1 for S3DIS, 2 for ScanNet); the logits of all passes are summed per block row, the
+== 1) has been drawn `min_votes` times (1 for S3DIS; 2 is ScanNet's coverage rule, but its script evaluates three views per draw:
+harness/scannet.py); the logits of all passes are summed per block row, the
 first maximum of the sums is the row's prediction, and the inner rows' (label, prediction) pairs fill a confusion matrix from
 which overall accuracy, class accuracy and IoU follow in float64.  Passes repeat for the whole batch while any of its blocks is
 uncovered; blocks that are covered already keep voting.
@@ -377,7 +378,7 @@ def evaluate(model_fn, pool, batch_size, num_point, seed, num_cls=13, min_votes=
     under torch.no_grad() on the current stream, and the tensors it gets are overwritten by the next pass (when it returns,
     everything that reads them must be ordered before later work on the current stream — the project's nets are).
     Batch i is blocks [i * batch_size, (i + 1) * batch_size) of the pool; rank r of `world` takes batches r, r + world, ... and
-    EvalResult.merge of the ranks' results equals the world = 1 result.  min_votes: 1 for S3DIS, 2 for ScanNet.
+    EvalResult.merge of the ranks' results equals the world = 1 result.  min_votes: 1 for S3DIS (ScanNet: scannet.evaluate).
     on_pass(batch_index, pass, index, logits): a hook that sees each pass's device tensors before they are voted.
     keep_votes: the finished batches' sums, counts and predictions are copied to the host (result.votes)."""
     _check_loop_args(num_point, num_cls, min_votes, max_passes)

@@ -259,10 +259,12 @@ def _check_scene_args(scenes, batch_size, rank, world):
 
 def evaluate_scenes_reference(logits_fn, sizes, rows_label, rows_inner, index, scene_of_block, scenes, batch_size, num_point, seed,
                               num_cls=13, min_votes=1, max_passes=evalvote.MAX_PASSES, rank=0, world=1, label_map=None,
-                              keep_pred=False):
+                              keep_pred=False, vote_fn=None):
     """`evaluate_scenes` stated in numpy.  sizes [P], rows_label / rows_inner / index [T]: the pool on the host;
-    logits_fn(batch_index, pass, index [b, N]) -> [b, N, C] float32"""
+    logits_fn(batch_index, pass, index [b, N]) -> [b, N, C] float32.  vote_fn: the pass loop of one batch, called with
+    evalvote.vote_reference's positional arguments (the default) — the statement's side of `voter_factory`"""
     _check_scene_args(scenes, batch_size, rank, world)
+    vote_fn = evalvote.vote_reference if vote_fn is None else vote_fn
     C = int(num_cls)
     first_block, first_batch = scene_plan(scene_of_block, len(scenes), batch_size)
     offsets = np.concatenate(([0], np.cumsum(np.asarray(sizes, dtype=np.int64))))
@@ -278,8 +280,8 @@ def evaluate_scenes_reference(logits_fn, sizes, rows_label, rows_inner, index, s
         ok = True
         for j, ids in enumerate(scene_batches(first_block, s, batch_size)):
             i = int(first_batch[s]) + j
-            d = evalvote.vote_reference(sizes, rows_label, rows_inner, ids, num_point, seed, i,
-                                        lambda p, idx, _i=i: logits_fn(_i, p, idx), C, min_votes, max_passes)
+            d = vote_fn(sizes, rows_label, rows_inner, ids, num_point, seed, i, lambda p, idx, _i=i: logits_fn(_i, p, idx), C,
+                        min_votes, max_passes)
             done.append(d)
             numbers.append(i)
             ok = ok and d.complete
@@ -327,7 +329,7 @@ def nearest(ref_xyz, query_xyz, mode=NN1_GRID):
 
 
 def evaluate_scenes(model_fn, pool, scenes, batch_size, num_point, seed, num_cls=13, min_votes=1, max_passes=evalvote.MAX_PASSES,
-                    rank=0, world=1, label_map=None, keep_pred=False, on_pass=None):
+                    rank=0, world=1, label_map=None, keep_pred=False, on_pass=None, voter_factory=None):
     """Evaluate a network scene by scene -> SceneResult.
 
         pool = feed.BlockPool.from_records(scene_files, with_index=True)         # one record file per scene
@@ -342,7 +344,9 @@ def evaluate_scenes(model_fn, pool, scenes, batch_size, num_point, seed, num_cls
     After every batch sph3d_scene_merge reads the vote sums while they are in the voter's buffer; after a scene's last batch
     come sph3d_scene_finalize, sph3d_nn1 (skipped without a full cloud) and sph3d_scene_lift.  A scene's clouds are uploaded
     for the scene and released after it.  label_map [C]: ScanNet's labelid_set, applied to pred_full only.
-    model_fn, min_votes, max_passes, on_pass: as evalvote.evaluate."""
+    model_fn, min_votes, max_passes, on_pass: as evalvote.evaluate.
+    voter_factory(pool, batch_size, num_point, num_cls, capacity_rows, min_votes) -> the evalvote.Voter whose run_batch votes the
+    batches (default: evalvote.Voter itself; harness/scannet.py hands in its three-view voter)."""
     import torch
     from .. import _lib
     _check_scene_args(scenes, batch_size, rank, world)
@@ -356,7 +360,7 @@ def evaluate_scenes(model_fn, pool, scenes, batch_size, num_point, seed, num_cls
     spans = [ids for s in mine for ids in plans[s]]
     dev, l = pool.device, _lib.lib()
     cap = max([int(pool.host_offsets[ids[-1] + 1] - pool.host_offsets[ids[0]]) for ids in spans] or [1])
-    voter = evalvote.Voter(pool, batch_size, num_point, C, cap, min_votes)
+    voter = (evalvote.Voter if voter_factory is None else voter_factory)(pool, batch_size, num_point, C, cap, min_votes)
     P, T = len(pool), int(pool.rows.shape[0])
     conf = torch.zeros((2, C * C), dtype=torch.int64, device=dev)          # full | voxel
     map_dev = None

@@ -199,7 +199,7 @@ Batch = collections.namedtuple("Batch", "inputs loss_args label inner")
 
 
 def s3dis_line(item):
-    """S3DIS / ScanNet (feed.DeviceFeed): points [B, N, 6], label, inner [B, N]"""
+    """S3DIS (feed.DeviceFeed) / ScanNet (scannet.ScanNetFeed): points [B, N, 6], label, inner [B, N]"""
     points, label, inner = item
     return Batch((points,), (label, inner), label, inner)
 
