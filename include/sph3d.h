@@ -417,11 +417,34 @@ int sph3d_interpolate_narrow_grad_t(int B, int Nin, int Mout, int C,
  * points whose distance update is skipped when the new sample provably cannot
  * lower any of their running distances; same samples bit for bit.
  * workspace: sph3d_farthest_point_sample_workspace(b,n,m) bytes (0 when the
- * cloud fits the register-resident kernels, n <= 24576). */
+ * cloud fits the register-resident kernels, n <= 24576, and for arguments the
+ * entry rejects). */
 size_t sph3d_farthest_point_sample_workspace(int b, int n, int m);
 int sph3d_farthest_point_sample(int b, int n, int m, const float* inp, int* out,
                                 void* workspace, size_t workspace_bytes,
                                 sph3d_stream_t stream);
+
+/* What sph3d_farthest_point_sample(b, n, m, ...) will launch (csrc/fps_plan.hpp: fps_plan, which the entry launches from and the
+ * workspace query sizes from), answered on the host; nothing is launched.  out[SPH3D_FPS_PLAN_FIELDS], in this order:
+ *     0 kernel: SPH3D_FPS_NONE (b == 0), _PLAIN fps_reg_kernel<P> (n <= 24576, outside the pruned kernel's range or m == 1),
+ *       _PRUNED fps_prune_kernel<P, 16> (2049 <= n <= 16384 and m > 1), _COOP fps_coop_kernel (n > 24576 and b G <= 128, G = ceil(n / 4096)),
+ *       _BIG fps_big_kernel alone (n > 24576 otherwise)
+ *     1 P (the template's points per thread or lane; 0 for _COOP and _BIG)   2 block (threads per workgroup: 1024, or n rounded up
+ *     to 64 below 1024 points)   3 grid (workgroups of the first launch)   4 G (workgroups per cloud: 1 but for _COOP)
+ *     5 xcd_local (_COOP: 1 when ceil(b / 8) G <= 16: a cloud's workgroups share an XCD, grid = 8 ceil(b / 8) G and the surplus
+ *     workgroups leave; which XCD cloud 0 starts on rotates per launch and is not part of the plan)
+ *     6 repair (_COOP: 1, fps_big_kernel is queued behind it and runs only if the co-operative pass raised its error word)
+ *     7 big_grid (workgroups of fps_big_kernel, min(b, 64); 0 where it is not launched)
+ *     8 workspace_bytes, and the byte offsets into it: 9 the error word   10 the granules [b][2][G] of 8 bytes (_COOP)
+ *     11 fps_big_kernel's running distances [big_grid][n] fp32
+ * -> SPH3D_OK, or SPH3D_EINVAL with the entry's own message for m <= 0, then n <= 0 or b < 0, then n > 262144, then out == NULL. */
+#define SPH3D_FPS_NONE 0
+#define SPH3D_FPS_PLAIN 1
+#define SPH3D_FPS_PRUNED 2
+#define SPH3D_FPS_COOP 3
+#define SPH3D_FPS_BIG 4
+#define SPH3D_FPS_PLAN_FIELDS 12
+int sph3d_farthest_point_sample_plan(int b, int n, int m, long long* out);
 
 /* Keyed inverse-density sampling (csrc/idsample.hip): what inverse_density_sample (tf_ops/sampling/tf_sample.py:27-41, stock TF
  * ops on the global generator in the reference) draws, as a pure function of (nn_dist, nn_count, seed, step, level).

@@ -76,6 +76,7 @@ SIGNATURES = {
     "sph3d_interpolate_narrow_grad_t": (_I, [_I] * 4 + [_P] * 6),
     "sph3d_farthest_point_sample_workspace": (_S, [_I] * 3),
     "sph3d_farthest_point_sample": (_I, [_I] * 3 + [_P, _P, _P, _S, _P]),
+    "sph3d_farthest_point_sample_plan": (_I, [_I] * 3 + [_P]),
     "sph3d_ids_sample_workspace": (_S, [_I] * 2),
     "sph3d_ids_sample_chunk": (_I, []),
     "sph3d_ids_sample": (_I, [_I] * 4 + [_P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I, _P, _P, _S, _P]),

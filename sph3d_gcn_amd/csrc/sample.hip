@@ -19,7 +19,10 @@
 // caller-provided workspace (the reference's `temp`) and re-reads xyz from L2.
 // -ffp-contract=off: d = (dx*dx + dy*dy) + dz*dz must round like the oracle.
 #include <atomic>
+#include <stddef.h>
+#include <string.h>
 #include "common.hpp"
+#include "fps_plan.hpp"
 
 namespace sph3d {
 
@@ -666,21 +669,11 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int b, int xcd_local, in
     }
 }
 
-constexpr int kFpsMaxRegPoints = 24;   // points per thread held in registers
-constexpr int kFpsBigGrid = 64;
+static_assert(kFpsRefBlock == kRefBlock && kFpsCoopPts == kCoopPts && kFpsMaxPoints == kRefBlock * 256, "fps_plan.hpp restates the kernels' constants");
 
 }  // namespace sph3d
 
 using namespace sph3d;
-
-// co-operative kernel: G workgroups per cloud, all B * G resident at once (<= 128 of the 256 CUs)
-static int coop_groups(int b, int n)
-{
-    const int G = (n + kCoopPts - 1) / kCoopPts;
-    return (G <= 64 && (long long)b * G <= 128) ? G : 0;
-}
-
-static size_t coop_slot_bytes(int b, int G) { return (256 + sizeof(unsigned long long) * (size_t)b * 2 * G + 255) & ~(size_t)255; }
 
 // test hook: SPH3D_FPS_FORCE_TIMEOUT=1 starts the co-operative kernel with its error word already set, so the repair pass runs
 // (read once)
@@ -690,85 +683,94 @@ static bool fps_force_timeout()
     return v;
 }
 
-// cloud size from which the pruned kernel is used
-constexpr int kFpsPruneMin = 2049;
+// The plan of a call, or the status and message of the arguments it rejects (the entry and the plan query answer alike)
+static int fps_checked_plan(FpsPlan* p, int b, int n, int m)
+{
+    *p = fps_plan(b, n, m);
+    SPH3D_REQUIRE(p->bad != kFpsBadSamples, "FarthestPointSample expects positive npoint");                     // tf_sample.cpp:35
+    SPH3D_REQUIRE(p->bad != kFpsBadShape, "FarthestPointSample expects (batch_size,num_points,3) inp shape");
+    SPH3D_REQUIRE(p->bad != kFpsBadPoints, "FarthestPointSample: n=%d exceeds the supported 262144 points", n);
+    return SPH3D_OK;
+}
 
+// 0 for arguments the entry rejects
 extern "C" size_t sph3d_farthest_point_sample_workspace(int b, int n, int m)
 {
-    (void)m;
-    if (n <= kRefBlock * kFpsMaxRegPoints) return 0;
-    const int G = coop_groups(b, n);
-    const int g = b < kFpsBigGrid ? b : kFpsBigGrid;
-    const size_t big = sizeof(float) * (size_t)g * n;                            // fps_big_kernel's running distances
-    if (G) return coop_slot_bytes(b, G) + big;                                   // error word + granule slots, then the repair pass's
-    return big;
+    return (size_t)fps_plan(b, n, m).workspace_bytes;
+}
+
+extern "C" int sph3d_farthest_point_sample_plan(int b, int n, int m, long long* out)
+{
+    FpsPlan p;
+    int rc = fps_checked_plan(&p, b, n, m);
+    if (rc) return rc;
+    SPH3D_REQUIRE(out != nullptr, "sph3d_farthest_point_sample_plan: out is NULL");
+    static_assert(offsetof(FpsPlan, bad) == SPH3D_FPS_PLAN_FIELDS * sizeof(long long), "the plan starts with the documented fields, in their order");
+    static_assert(kFpsNone == SPH3D_FPS_NONE && kFpsPlain == SPH3D_FPS_PLAIN && kFpsPruned == SPH3D_FPS_PRUNED && kFpsCoop == SPH3D_FPS_COOP &&
+                      kFpsBig == SPH3D_FPS_BIG, "the kernels as the header numbers them");
+    memcpy(out, &p, SPH3D_FPS_PLAN_FIELDS * sizeof(long long));
+    return SPH3D_OK;
 }
 
 extern "C" int sph3d_farthest_point_sample(int b, int n, int m, const float* inp, int* out,
                                            void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(m > 0, "FarthestPointSample expects positive npoint");                     // tf_sample.cpp:35
-    SPH3D_REQUIRE(b >= 0 && n > 0, "FarthestPointSample expects (batch_size,num_points,3) inp shape");
-    SPH3D_REQUIRE(n <= kRefBlock * 256, "FarthestPointSample: n=%d exceeds the supported 262144 points", n);
-    if (b == 0) return SPH3D_OK;
+    FpsPlan p;
+    int rc = fps_checked_plan(&p, b, n, m);
+    if (rc) return rc;
+    if (p.kernel == kFpsNone) return SPH3D_OK;
     hipStream_t st = as_stream(stream);
-    const int P = (n + kRefBlock - 1) / kRefBlock;
-    int bs = n < kRefBlock ? ((n + 63) / 64) * 64 : kRefBlock;
-    const dim3 grid(b), block(bs);
-#define SPH3D_FPS(PP) hipLaunchKernelGGL(fps_reg_kernel<PP>, grid, block, 0, st, b, n, m, inp, out)
-    // clouds of 2049 .. 16384 points: the pruned kernel (same samples bit for bit; at 2048 points it only ties with the plain
-    // kernel: 0.620 vs 0.614 us per round)
-    if (n >= kFpsPruneMin && n > kRefBlock && n <= 16384 && m > 1) {
-        const int need = (n + kRefBlock - 1) / kRefBlock;
-        const dim3 pblock(kRefBlock);
-#define SPH3D_FPSP(PP) hipLaunchKernelGGL((fps_prune_kernel<PP, 16>), grid, pblock, 0, st, b, n, m, inp, out)
-        if (need <= 4) SPH3D_FPSP(4);
-        else if (need <= 8) SPH3D_FPSP(8);
-        else SPH3D_FPSP(16);
+    const dim3 grid((unsigned)p.grid), block((unsigned)p.block), big_grid((unsigned)p.big_grid);
+    if (p.workspace_bytes != 0 && (workspace == nullptr || workspace_bytes < (size_t)p.workspace_bytes)) {
+        set_error("FarthestPointSample: workspace %zu B < required %zu B", workspace_bytes, (size_t)p.workspace_bytes);
+        return SPH3D_EWORKSPACE;
+    }
+    float* temp = (float*)((char*)workspace + p.off_temp);
+#define SPH3D_FPS(PP) case PP: hipLaunchKernelGGL(fps_reg_kernel<PP>, grid, block, 0, st, b, n, m, inp, out); break
+#define SPH3D_FPSP(PP) case PP: hipLaunchKernelGGL((fps_prune_kernel<PP, 16>), grid, block, 0, st, b, n, m, inp, out); break
+    switch (p.kernel) {
+    case kFpsPruned:        // (same samples as the plain kernel, bit for bit)
+        switch (p.P) {
+            SPH3D_FPSP(4);
+            SPH3D_FPSP(8);
+            SPH3D_FPSP(16);
+        }
+        break;
+    case kFpsPlain:
+        switch (p.P) {
+            SPH3D_FPS(1);
+            SPH3D_FPS(2);
+            SPH3D_FPS(4);
+            SPH3D_FPS(8);
+            SPH3D_FPS(12);
+            SPH3D_FPS(16);
+            SPH3D_FPS(24);
+        }
+        break;
+    case kFpsCoop: {
+        rc = check_hip(hipMemsetAsync(workspace, 0, (size_t)p.off_temp, st), "FarthestPointSample: memset");
+        if (rc) return rc;
+        int* err = (int*)((char*)workspace + p.off_err);
+        if (fps_force_timeout()) {
+            rc = check_hip(hipMemsetAsync(err, 1, 1, st), "FarthestPointSample: memset");
+            if (rc) return rc;
+        }
+        unsigned long long* slots = (unsigned long long*)((char*)workspace + p.off_slots);
+        // (launches rotate over the XCDs: two sampling streams' kernels of one-cloud batches would share XCD 0 otherwise)
+        static std::atomic<unsigned> rotate{0};
+        const int xcd_local = p.xcd_local ? 1 + (int)(rotate.fetch_add(1, std::memory_order_relaxed) & 7u) : 0;
+        hipLaunchKernelGGL(fps_coop_kernel, grid, block, 0, st, b, xcd_local, n, m, (int)p.G, inp, slots, err, out);
+        rc = check_launch("sph3d_farthest_point_sample (co-operative pass)");
+        if (rc) return rc;
+        // repair pass: returns at once unless the co-operative pass timed out (then every cloud is resampled, bit-exactly)
+        hipLaunchKernelGGL(fps_big_kernel, big_grid, block, 0, st, b, n, m, inp, temp, out, (const int*)err);
+        break;
+    }
+    case kFpsBig:
+        hipLaunchKernelGGL(fps_big_kernel, big_grid, block, 0, st, b, n, m, inp, temp, out, (const int*)nullptr);
+        break;
+    }
 #undef SPH3D_FPSP
-    }
-    else if (P <= 1) SPH3D_FPS(1);
-    else if (P <= 2) SPH3D_FPS(2);
-    else if (P <= 4) SPH3D_FPS(4);
-    else if (P <= 8) SPH3D_FPS(8);
-    else if (P <= 12) SPH3D_FPS(12);
-    else if (P <= 16) SPH3D_FPS(16);
-    else if (P <= kFpsMaxRegPoints) SPH3D_FPS(24);
-    else {
-        const size_t need = sph3d_farthest_point_sample_workspace(b, n, m);
-        if (workspace == nullptr || workspace_bytes < need) {
-            set_error("FarthestPointSample: workspace %zu B < required %zu B", workspace_bytes, need);
-            return SPH3D_EWORKSPACE;
-        }
-        const int G = coop_groups(b, n);
-        if (G) {
-            const size_t head = coop_slot_bytes(b, G);
-            int rc = check_hip(hipMemsetAsync(workspace, 0, head, st), "FarthestPointSample: memset");
-            if (rc) return rc;
-            int* err = (int*)workspace;
-            if (fps_force_timeout()) {
-                rc = check_hip(hipMemsetAsync(err, 1, 1, st), "FarthestPointSample: memset");
-                if (rc) return rc;
-            }
-            unsigned long long* slots = (unsigned long long*)((char*)workspace + 256);
-            // all workgroups of a cloud on one XCD while they take at most half of its 32 CUs (one 1024-thread workgroup per CU)
-            const int rounds8 = (b + 7) / 8;
-            // (launches rotate over the XCDs: two sampling streams' kernels of one-cloud batches would share XCD 0 otherwise)
-            static std::atomic<unsigned> rotate{0};
-            const int xcd_local = rounds8 * G <= 16 ? 1 + (int)(rotate.fetch_add(1, std::memory_order_relaxed) & 7u) : 0;      // (32 per XCD measured slower than spread: 2.88 vs 2.46 us per round at 131 072 points)
-            const unsigned nblk = xcd_local ? (unsigned)(8 * rounds8 * G) : (unsigned)(b * G);
-            hipLaunchKernelGGL(fps_coop_kernel, dim3(nblk), dim3(kRefBlock), 0, st, b, xcd_local, n, m, G, inp, slots, err, out);
-            rc = check_launch("sph3d_farthest_point_sample (co-operative pass)");
-            if (rc) return rc;
-            // repair pass: returns at once unless the co-operative pass timed out (then every cloud is resampled, bit-exactly)
-            const int g = b < kFpsBigGrid ? b : kFpsBigGrid;
-            hipLaunchKernelGGL(fps_big_kernel, dim3(g), dim3(kRefBlock), 0, st, b, n, m, inp, (float*)((char*)workspace + head), out,
-                               (const int*)err);
-        } else {
-            const int g = b < kFpsBigGrid ? b : kFpsBigGrid;
-            hipLaunchKernelGGL(fps_big_kernel, dim3(g), dim3(kRefBlock), 0, st, b, n, m, inp, (float*)workspace, out, (const int*)nullptr);
-        }
-    }
 #undef SPH3D_FPS
     return check_launch("sph3d_farthest_point_sample");
 }

@@ -1,13 +1,16 @@
-"""The pruned farthest-point sampling kernel (csrc/sample.hip: fps_prune_kernel, clouds of 1025 .. 16384 points): spatially
+"""The pruned farthest-point sampling kernel (csrc/sample.hip: fps_prune_kernel, clouds of 2049 .. 16384 points): spatially
 sorted slots whose distance update is skipped when the new sample cannot change them, per-lane arg-max caches that are
 rescanned only when they went stale.  The samples must be the reference's
-(tf_sample_gpu.cu:7-73 restated in oracle/) bit for bit: same indices in the same order, including every tie."""
+(tf_sample_gpu.cu:7-73 restated in oracle/) bit for bit: same indices in the same order, including every tie.
+Four cases of the list lie outside that range and run the plain kernel, fps_reg_kernel: the 1025-point and the two 2048-point
+clouds (<2>: the pruned kernel starts at 2049 points) and the 16385-point cloud (<24>).  KERNELS names each case's kernel, and
+the test holds the library's plan query to it before it launches."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
-from sph3d_gcn_amd import tf_sample
+from sph3d_gcn_amd import _lib, tf_sample
 from sph3d_gcn_amd.harness import synth
 
 pytestmark = pytest.mark.gpu
@@ -31,11 +34,25 @@ CASES = [("uniform", 2, 6144, 700), ("uniform", 1, 6145, 300), ("uniform", 1, 13
          ("uniform", 3, 1025, 300), ("uniform", 2, 2048, 2048), ("s3dis", 4, 2048, 768), ("uniform", 2, 3000, 700),
          ("s3dis", 2, 4096, 1024), ("uniform", 2, 5000, 1200), ("s3dis", 3, 8192, 2048), ("modelnet", 2, 10000, 2500),
          ("uniform", 1, 12288, 512), ("modelnet", 3, 2500, 625)]
+# (kernel, points per lane / thread) of each case above, in its order (tests/test_fps_forms.py checks the list without a device)
+KERNELS = [("pruned", 8), ("pruned", 8), ("pruned", 16), ("pruned", 16),
+           ("plain", 24),
+           ("plain", 2), ("plain", 2), ("plain", 2), ("pruned", 4),
+           ("pruned", 4), ("pruned", 8), ("pruned", 8), ("pruned", 16),
+           ("pruned", 16), ("pruned", 4)]
+
+
+def _kernel(B, N, m):
+    """what the library will launch: sph3d_farthest_point_sample_plan's fields 0 and 1"""
+    out = np.zeros(12, np.int64)
+    assert _lib.lib().sph3d_farthest_point_sample_plan(B, N, m, out.ctypes.data) == 0
+    return {1: "plain", 2: "pruned"}[int(out[0])], int(out[1])
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "%s-B%d-N%d-m%d" % c)
 def test_pruned_fps_equals_the_oracle(dev, case):
     kind, B, N, m = case
+    assert _kernel(B, N, m) == KERNELS[CASES.index(case)]
     pts = _cloud(kind, B, N, seed=77)
     np.testing.assert_array_equal(_fps(dev, pts, m), oracle.farthest_point_sample(m, pts))
 
