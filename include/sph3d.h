@@ -960,6 +960,57 @@ int sph3d_nn1(long long V, long long F, const float* ref_xyz, const float* query
 int sph3d_scene_lift(int C, long long V, long long F, const int* pred_voxel, const int* idx, const int* label_map,
                      const int* label_full, int* pred_full, long long* confusion, sph3d_stream_t stream);
 
+/* ---- exact k nearest neighbours (csrc/knn.hip; not in the reference, whose searches are range searches that keep the FIRST
+ * nn_sample points in index order).  harness/knn.py states it in numpy (knn_reference); nn_index, nn_count and the bit patterns of
+ * nn_dist equal that statement at every launch form.  database [B,N,3], query [B,M,3] fp32 -> nn_index [B,M,k] int32,
+ * nn_count [B,M] int32, nn_dist [B,M,k] fp32: the format of the range searches, so every consumer of theirs takes the graph.
+ *   d2         dx = q.x - p.x (and y, z), d2 = (dx*dx + dy*dy) + dz*dz: fp32, one rounding per operation (sph3d_nn1's d2).
+ *   admitted   a database point is a candidate of a query iff d2 is finite and d2 < R2, R2 = radius * radius in fp32.  radius = +inf
+ *              is "no radius" (R2 = inf: every finite d2).  THIS PREDICATE IS THE OP'S OWN: it is not the reference kernel's
+ *              fabs(dist - radius) > 1e-6 test, and no radius grows.
+ *   row        the admitted candidates in ascending (d2, index) order — the lowest index first among equal d2 — cut at k.
+ *              nn_count = min(k, admitted): 0 is possible with a radius, and for a query with a non-finite coordinate (a database
+ *              point with one is never returned).  Unused slots hold index 0 and distance 0.
+ *   nn_dist    SPH3D_KNN_DIST_ROOT: sqrt(sqrt(d2)), two correctly rounded fp32 roots — the library's convention (the square root
+ *              of the Euclidean distance), so sph3d_spherical_kernel and the weighted un-pooling take the tensor as it is;
+ *              SPH3D_KNN_DIST_SQUARED: d2 itself.
+ *   mode       SPH3D_KNN_SCAN: every wave scans its cloud from LDS tiles; SPH3D_KNN_GRID: a counting-sorted cell grid per cloud in
+ *              the caller's workspace (the layout of sph3d_nn1's) and a walk of cube shells per query; clouds the grid cannot index
+ *              (fewer than 64 finite points, a zero or non-finite extent) raise a flag on the device and the scan, queued behind
+ *              the search, takes them — the host reads nothing.  SPH3D_KNN_AUTO: the scan up to 2048 points, the grid above (the measured crossover).
+ *              All three give the same output.
+ * 1 <= k <= 64 (k > 64: SPH3D_EUNSUPPORTED; k < 1: SPH3D_EINVAL), then radius > 0 (not NaN), then B >= 0, N >= 1, M >= 0 with
+ * B N <= 2^40 and B M <= 2^40, then mode and dist: validated in this order by the entry and by the plan query alike.  B == 0 or
+ * M == 0 launches nothing.  workspace: sph3d_build_nearest_neighbor_workspace(B, N, M, k, mode) bytes, 16-byte aligned (0 for
+ * the scan and for arguments the entry rejects); too small: SPH3D_EWORKSPACE.  Nothing is allocated.
+ *
+ * sph3d_build_nearest_neighbor_plan: what the call will launch (csrc/knn_plan.hpp: knn_plan, which the entry launches from and the
+ * workspace query sizes from), answered on the host.  out[SPH3D_KNN_PLAN_FIELDS], in this order:
+ *     0 form: SPH3D_KNN_FORM_NONE (B == 0 or M == 0), _SCAN, _GRID   1 queries per workgroup (one wave each)   2 block (threads)
+ *     3 groups = ceil(M / queries) per cloud   4 scan_grid: workgroups of knn_scan_kernel, min(B groups, 2^20) (every kernel strides
+ *     over its work items)   5 scan_lds: its static LDS bytes   6 search_grid, 7 search_lds: knn_grid_kernel (_GRID)
+ *     8 fallback (_GRID: 1, knn_scan_kernel is queued behind the search and runs per cloud only where the build raised the flag)
+ *     9 cells: cells a cloud's grid may have, N / 2 held to [64, cell_cap]   10 cell_cap = 2^21
+ *     11 build_block, 12 build_parts (workgroups per cloud, at most 64), 13 build_grid: the bounding-box, count and fill passes
+ *     14 setup_grid: header reset and grid shape, a thread per cloud   15 prefix_block, 16 prefix_grid: the scan of the cell counts
+ *     17 workspace_bytes, the byte offsets into it: 18 headers, 19 cell ends, 20 sorted points (x, y, z, index bits), and the
+ *     strides per cloud: 21 header (256), 22 cell ends, 23 points (16 N)
+ * -> SPH3D_OK, or the entry's own status and message in the entry's order, then SPH3D_EINVAL for out == NULL. */
+#define SPH3D_KNN_AUTO 0
+#define SPH3D_KNN_SCAN 1
+#define SPH3D_KNN_GRID 2
+#define SPH3D_KNN_DIST_ROOT 0
+#define SPH3D_KNN_DIST_SQUARED 1
+#define SPH3D_KNN_FORM_NONE 0
+#define SPH3D_KNN_FORM_SCAN 1
+#define SPH3D_KNN_FORM_GRID 2
+#define SPH3D_KNN_PLAN_FIELDS 24
+size_t sph3d_build_nearest_neighbor_workspace(int B, int N, int M, int k, int mode);
+int sph3d_build_nearest_neighbor_plan(int B, int N, int M, int k, float radius, int mode, long long* out);
+int sph3d_build_nearest_neighbor(int B, int N, int M, int k, float radius, int mode, int dist, const float* database,
+                                 const float* query, int* nn_index, int* nn_count, float* nn_dist, void* workspace,
+                                 size_t workspace_bytes, sph3d_stream_t stream);
+
 /* ---- surface normals from order-free integer ball moments (csrc/normals.hip; not in the reference, whose facade line reads its
  * normals from the dataset).  harness/normals.py states every entry in numpy: moments and counts equal it bit for bit, normal and
  * variation are held to the per-element bounds of tests/_normal_ref.py.  Every buffer is the caller's; no floating-point atomic.

@@ -114,6 +114,9 @@ SIGNATURES = {
     "sph3d_nn1_workspace": (_S, [_L, _L]),
     "sph3d_nn1": (_I, [_L, _L, _P, _P, _I, _P, _P, _S, _P]),
     "sph3d_scene_lift": (_I, [_I, _L, _L] + [_P] * 6 + [_P]),
+    "sph3d_build_nearest_neighbor_workspace": (_S, [_I] * 5),
+    "sph3d_build_nearest_neighbor_plan": (_I, [_I] * 4 + [_F, _I, _P]),
+    "sph3d_build_nearest_neighbor": (_I, [_I] * 4 + [_F, _I, _I] + [_P] * 5 + [_P, _S, _P]),
     "sph3d_graph_normals": (_I, [_I, _I, _I, _I, _F, _I] + [_P] * 10 + [_P]),
     "sph3d_ball_normals_workspace": (_S, [_L]),
     "sph3d_ball_normals": (_I, [_L, _F, _I] + [_P] * 6 + [_P, _S, _P]),

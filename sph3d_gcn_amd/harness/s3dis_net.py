@@ -106,6 +106,9 @@ class GraphPlan:
                          transposed graphs, level by level — VALU / integer-atomic bound work;
       * main stream    : the feature path (convolutions, GEMMs, normalisation) — L2 / MFMA / HBM bound work,
     and the main stream waits, per level, only on the event of the graph it is about to use.
+    config.unpool_k (not in the reference; absent or None: the sphere search, as always): the decoder's un-pooling graphs are the
+    unpool_k nearest coarse points of every fine point (tf_nnquery.build_nearest_neighbor, squared distances), for
+    config.unpool_method = 'idw' — or 'mean' / 'weighted' over the same rows.
     On CPU tensors (oracle-backed tests) everything is built lazily on the spot."""
 
     def __init__(self, points, config, overlap=True, points_ready=None, decoder=True, global_kernel=None, global_radius=100.0,
@@ -313,7 +316,12 @@ class GraphPlan:
         # build_graph_deconv (util.py:52-58) + spherical_kernel: the intra half fused, the inter search as is
         intra_idx, intra_cnt, intra_dst, filt_idx = s3g_util.build_intra_graph(xyz_c, radius, uplimit, c.kernel, **self._bw_kw())
         from .. import tf_nnquery
-        if (self.need_backward and xyz_c.is_cuda and c.unpool_method == 'mean' and s3g_util.neighbor_fn is s3g_util.build_sphere_neighbor
+        unpool_k = getattr(c, "unpool_k", None)
+        if unpool_k is not None:
+            # config.unpool_k (not in the reference; absent = None): the un-pooling graph is the unpool_k nearest coarse points,
+            # with squared distances (s3g_util.unpool3d's 'idw' weights); 'mean' and 'weighted' take the graph as well
+            inter_idx, inter_cnt, inter_dst = tf_nnquery.build_nearest_neighbor(xyz_c, xyz_unpool, unpool_k, dist="squared")
+        elif (self.need_backward and xyz_c.is_cuda and c.unpool_method == 'mean' and s3g_util.neighbor_fn is s3g_util.build_sphere_neighbor
                 and tf_nnquery.get_radius_mode() == "compat"):
             # the search also counts the in-edges: first pass of the transposed graph of the un-pooling gradient
             inter_idx, inter_cnt, inter_dst = tf_nnquery.build_sphere_neighbor_counted(xyz_c, xyz_unpool, radius, uplimit)
@@ -330,7 +338,11 @@ class GraphPlan:
         _tgraph.transpose(g["intra_idx"], g["intra_cnt"], n_src_conv, bin_index=g["filt_idx"],
                           num_bins=self.config.binSize)
         if n_src_unpool is not None and self.config.unpool_method == 'mean':
-            _tgraph.transpose(g["inter_idx"], g["inter_cnt"], n_src_unpool)
+            if getattr(self.config, "unpool_k", None) is not None:
+                # (a k-NN row lists distinct points)
+                _tgraph.transpose(g["inter_idx"], g["inter_cnt"], n_src_unpool, unique_rows=True)
+            else:
+                _tgraph.transpose(g["inter_idx"], g["inter_cnt"], n_src_unpool)
 
     def _build_all(self, stream):
         """Graph stream schedule: every graph is issued as soon as the sampling levels it needs exist.  Decoder level l

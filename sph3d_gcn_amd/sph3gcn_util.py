@@ -207,8 +207,15 @@ def build_graph(xyz, radius, nn_uplimit, num_sample, sample_method=None, sample_
     return intra_idx, intra_cnt, intra_dst, indices
 
 
-def build_graph_deconv(xyz, xyz_unpool, radius, nn_uplimit):
+def build_graph_deconv(xyz, xyz_unpool, radius, nn_uplimit, unpool_k=None):
+    """utils/sph3gcn_util.py:52-58.  unpool_k (not in the reference): the un-pooling graph lists the `unpool_k` NEAREST points of
+    `xyz` around every point of `xyz_unpool` (tf_nnquery.build_nearest_neighbor, no radius) and inter_dst holds SQUARED distances,
+    what unpool3d's 'idw' forms its weights from; the intra half is the same either way."""
     intra_idx, intra_cnt, intra_dst = neighbor_fn(xyz, xyz, radius=radius, nnsample=nn_uplimit)
+    if unpool_k is not None:
+        from . import tf_nnquery
+        inter_idx, inter_cnt, inter_dst = tf_nnquery.build_nearest_neighbor(xyz, xyz_unpool, unpool_k, dist="squared")
+        return intra_idx, intra_cnt, intra_dst, inter_idx, inter_cnt, inter_dst
     inter_idx, inter_cnt, inter_dst = neighbor_fn(xyz, xyz_unpool, radius=radius, nnsample=nn_uplimit)
     return intra_idx, intra_cnt, intra_dst, inter_idx, inter_cnt, inter_dst
 
@@ -524,13 +531,30 @@ def _unpool_weights(nn_dist):
     return (nn_dist + epsilon) / (sum_nn_dist + epsilon)
 
 
+IDW_EPSILON = 1e-8       # (added in float32: the float32 nearest to 1e-8)
+
+
+def _idw_weights(nn_dist, nn_count):
+    """the 'idw' un-pooling's factors (not in the reference: the three-nearest-neighbour interpolation of PointNet++-style
+    decoders): w_i = (1 / (d2_i + 1e-8)) / sum_j (1 / (d2_j + 1e-8)) over the row's nn_count entries, 0 in the other slots and in
+    a row without neighbours.  nn_dist must hold SQUARED distances (build_nearest_neighbor(..., dist="squared")).  float32: one
+    add, one reciprocal, a sum of nn_count terms and one division."""
+    live = torch.arange(nn_dist.shape[-1], device=nn_dist.device).view(1, 1, -1) < nn_count.unsqueeze(-1)
+    recip = torch.where(live, 1.0 / (nn_dist + IDW_EPSILON), torch.zeros_like(nn_dist))
+    total = torch.sum(recip, dim=-1, keepdim=True)
+    return recip / torch.where(total > 0, total, torch.ones_like(total))
+
+
 def unpool3d(inputs, nn_index, nn_count, nn_dist, scope, method):
     """Feature interpolation back onto the finer point set, method 'mean' or 'weighted' (same signature as
-    utils/sph3gcn_util.py:300-325)."""
+    utils/sph3gcn_util.py:300-325), or 'idw': inverse-distance weights, which REQUIRES nn_dist to hold squared distances
+    (a k-NN graph built with dist="squared": build_graph_deconv(..., unpool_k=k)); see _idw_weights."""
     if method == 'mean':
         outputs = tf_unpool3d.mean_interpolate(inputs, nn_index, nn_count)
     elif method == 'weighted':
         outputs = tf_unpool3d.weighted_interpolate(inputs, _unpool_weights(nn_dist), nn_index, nn_count)
+    elif method == 'idw':
+        outputs = tf_unpool3d.weighted_interpolate(inputs, _idw_weights(nn_dist, nn_count), nn_index, nn_count)
     else:
         raise ValueError("Unknow unpooling method %s." % method)
     return outputs
@@ -541,16 +565,18 @@ def unpool_logits(inputs, nn_index, nn_count, nn_dist, skip, num_out_channels, s
     """pointwise_conv3d_concat(unpool3d(inputs, ...), skip, num_out_channels, scope, ...) — same variables, created in the same
     order — for a layer that is a plain product with few outputs (the logits layer of models/SPH3D_s3dis.py:99-108).
     Interpolation and product are both linear, so the product runs on the COARSE points and the interpolation moves rows of
-    num_out_channels floats (tf_unpool3d.interpolate_linear); `skip` may be None.  Anything else takes the two calls."""
+    num_out_channels floats (tf_unpool3d.interpolate_linear); `skip` may be None.  Anything else takes the two calls.
+    method 'idw' requires squared distances in nn_dist, as in unpool3d."""
     fn = getattr(tf_unpool3d, "interpolate_linear", None)          # (the oracle-backed CPU stand-ins of the tests have none)
     if (FUSE_UNPOOL_LOGITS and fn is not None and inputs.is_cuda and not with_bn and activation_fn is None
-            and (skip is None or FUSE_LOGITS_CONCAT) and method in ('mean', 'weighted')
+            and (skip is None or FUSE_LOGITS_CONCAT) and method in ('mean', 'weighted', 'idw')
             and tf_unpool3d.linear_supported(num_out_channels)):
         cs = 0 if skip is None else skip.shape[-1]
         kernel = _variable_with_weight_decay(scope + '/weights', shape=[inputs.shape[-1] + cs, num_out_channels],
                                              use_xavier=use_xavier, stddev=stddev, with_decay=weight_decay)
         biases = get_variable_store().get_variable(scope + '/biases', [num_out_channels], _constant(0.0)) if with_bias else None
-        weight = _unpool_weights(nn_dist) if method == 'weighted' else None
+        weight = (_unpool_weights(nn_dist) if method == 'weighted' else
+                  _idw_weights(nn_dist, nn_count) if method == 'idw' else None)
         return fn(inputs, skip, kernel, biases, nn_index, nn_count, weight=weight)
     net = unpool3d(inputs, nn_index, nn_count, nn_dist, scope, method)
     if skip is None:

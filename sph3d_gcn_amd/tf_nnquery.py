@@ -99,6 +99,68 @@ def _(database, query, length, nn_sample, grid_size):
             database.new_empty((B, M), dtype=torch.int32))
 
 
+KNN_AUTO, KNN_SCAN, KNN_GRID = 0, 1, 2          # include/sph3d.h: SPH3D_KNN_AUTO, _SCAN, _GRID
+_KNN_DIST = {"root": 0, "squared": 1}            # SPH3D_KNN_DIST_ROOT, _SQUARED
+
+
+def _build_nearest_neighbor_impl(database: torch.Tensor, query: torch.Tensor, k: int, radius: float, dist: int,
+                                 mode: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    _lib.require_device(database, query)
+    if database.dim() != 3 or database.shape[2] != 3:
+        raise ValueError("Shape of database points requires to be (batch, npoint, 3)")
+    if query.dim() != 3 or query.shape[2] != 3 or query.shape[0] != database.shape[0]:
+        raise ValueError("Shape of query points requires to be (batch, mpoint, 3)")
+    database, query = _lib.f32(database), _lib.f32(query)
+    B, N, _ = database.shape
+    M = query.shape[1]
+    l = _lib.lib()
+    nbytes = l.sph3d_build_nearest_neighbor_workspace(B, N, M, k, mode)
+    if k < 1:
+        raise ValueError("build_nearest_neighbor: k>=1 required, got %d" % k)
+    nn_index = _lib.empty((B, M, k), torch.int32, database.device)
+    nn_count = _lib.empty((B, M), torch.int32, database.device)
+    nn_dist = _lib.empty((B, M, k), torch.float32, database.device)
+    ws = _lib.scratch(nbytes, database.device, slot=1)
+    _lib.check(l.sph3d_build_nearest_neighbor(
+        B, N, M, k, radius, mode, dist, _lib.ptr(database), _lib.ptr(query), _lib.ptr(nn_index), _lib.ptr(nn_count),
+        _lib.ptr(nn_dist), _lib.ptr(ws), nbytes, _lib.stream_ptr()))
+    return nn_index, nn_count, nn_dist
+
+
+_build_nearest_neighbor = torch.library.custom_op("sph3d::build_nearest_neighbor", mutates_args=())(_build_nearest_neighbor_impl)
+
+
+@_build_nearest_neighbor.register_fake
+def _(database, query, k, radius, dist, mode):
+    B, M = query.shape[0], query.shape[1]
+    return (database.new_empty((B, M, k), dtype=torch.int32),
+            database.new_empty((B, M), dtype=torch.int32),
+            database.new_empty((B, M, k), dtype=torch.float32))
+
+
+def build_nearest_neighbor(database, query, k, radius=None, dist="root", mode=KNN_AUTO):
+    """Exact k nearest neighbours (not in the reference's API; harness/knn.py: knn_reference states it, and the kernels equal
+    that statement bit for bit): for every query the admitted database points in ascending (d2, index) order, cut at `k`.
+
+    database  [B, N, >=3] fp32 (only x, y, z are used)      query  [B, M, >=3] fp32      1 <= k <= 64
+    radius    None: every point with a finite d2 is admitted; a number > 0: those with d2 < radius * radius in float32.  This is
+              the op's own predicate, not the range searches' (no 1e-6 test, no radius growth)
+    dist      "root": nn_dist = the SQUARE ROOT of the Euclidean distance, the library's convention (spherical_kernel and the
+              'weighted' un-pooling take it as it is); "squared": the squared Euclidean distance ('idw' un-pooling)
+    mode      KNN_AUTO (the library's choice), KNN_SCAN, KNN_GRID: the same output from either launch form
+    returns   nn_index [B, M, k] int32 (unused slots 0), nn_count [B, M] int32 = min(k, admitted), nn_dist [B, M, k] fp32
+              (unused slots 0): what pool, un-pool, the convolutions, _tgraph.transpose and graph_normals consume.
+
+    The radius mode of set_radius_mode does not apply.  No gradient.
+    """
+    if dist not in _KNN_DIST:
+        raise ValueError("dist must be 'root' or 'squared'")
+    database = database[:, :, 0:3]
+    query = query[:, :, 0:3]
+    radius = float("inf") if radius is None else float(radius)
+    return _build_nearest_neighbor_impl(database, query, int(k), radius, _KNN_DIST[dist], int(mode))
+
+
 def build_sphere_neighbor(database, query, radius=0.1, dilation_rate=None, nnsample=100):
     """Range search (public signature of tf_nnquery.py:9-31): for every query point the first `nnsample` database points,
     in ascending index order, that lie strictly inside the search sphere.
