@@ -322,6 +322,55 @@ int sph3d_depthwise_conv3d_grad_t(int B, int N, int M, int F, int C, int r,
                                   const float* input, const float* filter, const float* grad_output,
                                   float* grad_input, float* grad_filter,
                                   void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+
+/* ---- fuzzy spherical kernel (not in the reference tree: the interpolated kernel of its authors' follow-up work; fuzzy.hip) ----
+ * A neighbour contributes to the (up to) eight bins around it with trilinear weights that sum to 1, so the convolution is a
+ * continuous function of the coordinates.  alpha, beta, gamma and the centre rule are those of sph3d_spherical_kernel
+ * (tf_buildkernel_gpu.cu:49-68 with include/sph3d_atan2f.h; there is no device-library variant).  Per axis a lower corner and a
+ * fraction byte:  azimuth a = alpha - 0.5f, i0 = floorf(a), fa8 = min(255, (int)floorf((a - i0) * 256)), lower sector i0 mod n,
+ * upper (i0 + 1) mod n;  elevation j0 = floorf(beta - 0.5f), fb8 likewise, j0 < 0 -> (0, 0), j0 >= p - 1 -> (p - 1, 0), upper
+ * min(j0 + 1, p - 1);  the radial axis the same with gamma and q.
+ *   filt_index[B,M,K] i32   1 + i0 + n*j0 + n*p*k0 (the hard format applied to the lower corner); 0 for a centre slot and for
+ *                           slots k >= nn_count
+ *   filt_frac[B,M,K]  i32   fa8 | fb8 << 8 | fg8 << 16; 0 where filt_index is 0
+ * Consumers: axis weights (256 - f8, f8); a corner's coefficient is the product of its three axis weights times 2^-24 (exact in
+ * fp32, the eight sum to exactly 1); corners that coincide add up; filt_index <= 0 is one term, bin 0 with coefficient 1; bits
+ * 24..31 of filt_frac are ignored and every corner bin is clamped to [0, F-1].
+ * sph3d_gcn_amd/harness/fuzzy.py states the builder and the convolution in numpy (integers bit for bit, sums in float64). */
+int sph3d_fuzzy_spherical_kernel(int B, int N, int M, int K, int n, int p, int q, float radius,
+                                 const float* database, const float* query,
+                                 const int* nn_index, const int* nn_count, const float* nn_dist,
+                                 int* filt_index, int* filt_frac, sph3d_stream_t stream);
+/* out[b,m,c*r+rho] = (1/cnt) * sum_{k < min(cnt,K)} in[b,idx_k,c] * sum_t coef_{k,t} * filt[bin_{k,t},c,rho]; rows with cnt = 0
+ * give exact 0.  filter[F,C,r] with F = n*p*q + 1 <= 257; any C, r >= 1 (F*r <= 16384), K.  The filter table of a column slice
+ * (at most 512 columns and 64 KB) is staged in LDS; wider layers run as several slices. */
+int sph3d_fuzzy_depthwise_conv3d(int B, int N, int M, int F, int C, int r, int K, int n, int p, int q,
+                                 const int* nn_index, const int* nn_count, const int* filt_index, const int* filt_frac,
+                                 const float* input, const float* filter, float* output, sph3d_stream_t stream);
+/* Both gradients, fully written, no float atomics:
+ *   grad_filter[f,c,rho] = sum over edges and their corners t with bin_t = f of coef_t/cnt_m * in[b,n,c] * grad_output[b,m,c*r+rho]
+ *                          — workgroups walk the forward graph by rows and accumulate in LDS tables whose columns each belong to
+ *                          one lane; their partial tables (`workspace`, sph3d_fuzzy_depthwise_conv3d_grad_workspace() bytes) are
+ *                          added in workgroup order: the same bits on every run, in either mode
+ *   grad_input[b,n,c]    = sum over the in-edges of n, sum_rho grad_output[b,m,c*r+rho]/cnt_m * sum_t coef_t * filt[bin_t,c,rho]
+ *                          — a gather over (offsets, ent_edge) of sph3d_graph_transpose_finish_edges below, in list order:
+ *                          reproducible when the lists were built in deterministic mode. */
+size_t sph3d_fuzzy_depthwise_conv3d_grad_workspace(int B, int N, int M, int F, int C, int r, int K);
+int sph3d_fuzzy_depthwise_conv3d_grad(int B, int N, int M, int F, int C, int r, int K, int n, int p, int q,
+                                      const int* nn_index, const int* nn_count, const int* filt_index, const int* filt_frac,
+                                      const int* offsets, const int* ent_edge,
+                                      const float* input, const float* filter, const float* grad_output,
+                                      float* grad_input, float* grad_filter,
+                                      void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+/* The un-binned transposed graph (F = 1) whose entries name the EDGE, not only its row: ent_edge[B*M*K] holds m*K + k of every
+ * in-edge of source (b, n) in [offsets[b*(N+1) + n], offsets[b*(N+1) + n + 1]), so a consumer can read per-slot arrays.  Second
+ * phase on a workspace counted by sph3d_graph_transpose_count(..., F = 1, bin_index = NULL, ...) (scan + fill, as
+ * sph3d_graph_transpose_finish; workspace: sph3d_graph_transpose_workspace(B, N, M, K, 1) bytes).  The order inside a list is
+ * not defined — except in deterministic mode, where it is ascending by edge id. */
+int sph3d_graph_transpose_finish_edges(int B, int N, int M, int K, const int* nn_index, const int* nn_count,
+                                       int* offsets, int* ent_edge, void* workspace, size_t workspace_bytes,
+                                       sph3d_stream_t stream);
+
 /* (transposed graph built with F = 1)  grad_input[B,Nin,C] = sum over in-edges of grad_output[B,Mout,C] * ent_scale: the gradient of
  * avg_pool3d (Nin=N, Mout=M), mean_interpolate and weighted_interpolate (Nin=M coarse, Mout=N fine).
  * Non-finite values: an element with a non-finite term is non-finite, but not always of the reference's kind.  With C <= 128,

@@ -60,6 +60,11 @@ SIGNATURES = {
     "sph3d_build_sphere_graph_ocml": (_I, [_I, _I, _I, _I, _F, _I, _I, _I] + [_P] * 6 + [_P, _S, _P]),
     "sph3d_depthwise_conv3d_grad_t_workspace": (_S, [_I] * 5),
     "sph3d_depthwise_conv3d_grad_t": (_I, [_I] * 6 + [_P] * 10 + [_P, _S, _P]),
+    "sph3d_fuzzy_spherical_kernel": (_I, [_I, _I, _I, _I, _I, _I, _I, _F] + [_P] * 7 + [_P]),
+    "sph3d_fuzzy_depthwise_conv3d": (_I, [_I] * 10 + [_P] * 7 + [_P]),
+    "sph3d_fuzzy_depthwise_conv3d_grad_workspace": (_S, [_I] * 7),
+    "sph3d_fuzzy_depthwise_conv3d_grad": (_I, [_I] * 10 + [_P] * 11 + [_P, _S, _P]),
+    "sph3d_graph_transpose_finish_edges": (_I, [_I] * 4 + [_P] * 4 + [_P, _S, _P]),
     "sph3d_depthwise_conv3d_cat_supported": (_I, [_I] * 4),
     "sph3d_depthwise_conv3d_cat": (_I, [_I] * 8 + [_P] * 8),
     "sph3d_depthwise_conv3d_grad_t_cat": (_I, [_I] * 7 + [_P] * 12 + [_P, _S, _P]),

@@ -201,3 +201,42 @@ def transpose(nn_index, nn_count, n_src, bin_index=None, weight=None, num_bins=1
     while len(_cache) > _MAX_ENTRIES:
         _unique.discard(_cache.popitem(last=False)[0])
     return out
+
+
+def transpose_edges(nn_index, nn_count, n_src, counted_workspace=None):
+    """-> (offsets[B*(n_src+1)] i32, ent_edge[B*M*K] i32): the un-binned transpose whose entries name the edge m*K + k
+    (include/sph3d.h: sph3d_graph_transpose_finish_edges), for the fuzzy convolution's gradient.  Cached under a key of its own
+    ("edges"), in the same LRU and with the same stream rules as transpose()."""
+    cur_raw = _lib.current_raw_stream()
+    key = ("edges", _ident(nn_index), _ident(nn_count), int(n_src), tuple(nn_index.shape))
+    hit = _cache.get(key)
+    if hit is not None:
+        _cache.move_to_end(key)
+        out, _keep, ev, synced = hit
+        if cur_raw not in synced:
+            cur = torch.cuda.current_stream()
+            cur.wait_event(ev)
+            for t in out:
+                t.record_stream(cur)
+            synced.add(cur_raw)
+        return out
+    cur = torch.cuda.current_stream()
+    B, M, K = nn_index.shape
+    dev = nn_index.device
+    offsets = _lib.empty((B * (n_src + 1),), torch.int32, dev)
+    ent_edge = _lib.empty((B * M * K,), torch.int32, dev)
+    l = _lib.lib()
+    wsb = l.sph3d_graph_transpose_workspace(B, n_src, M, K, 1)
+    if counted_workspace is None:
+        counted_workspace = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+        _lib.check(l.sph3d_graph_transpose_count(B, n_src, M, K, 1, _lib.ptr(nn_index), _lib.ptr(nn_count), None, 0,
+                                                 _lib.ptr(counted_workspace), wsb, _lib.stream_ptr()))
+    _lib.check(l.sph3d_graph_transpose_finish_edges(B, n_src, M, K, _lib.ptr(nn_index), _lib.ptr(nn_count), _lib.ptr(offsets),
+                                                    _lib.ptr(ent_edge), _lib.ptr(counted_workspace), wsb, _lib.stream_ptr()))
+    out = (offsets, ent_edge)
+    ev = torch.cuda.Event()
+    ev.record(cur)
+    _cache[key] = (out, (nn_index, nn_count), ev, {cur_raw})
+    while len(_cache) > _MAX_ENTRIES:
+        _unique.discard(_cache.popitem(last=False)[0])
+    return out

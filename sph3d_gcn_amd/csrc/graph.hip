@@ -645,6 +645,88 @@ extern "C" int sph3d_graph_transpose_finish_ordered(int B, int N, int M, int K, 
                      workspace_bytes, stream);
 }
 
+// ---- the un-binned transpose whose entries name the EDGE (fuzzy.hip's grad_input reads the slot's two words) --------------------
+namespace sph3d {
+
+// one wave per graph row, lane = slot, as tg_fill_rows; the entry is the edge id m*K + k inside the cloud
+__global__ __launch_bounds__(1024) void tg_fill_edges(int B, int N, int M, int K, const int* __restrict__ nnIndex,
+                                                      const int* __restrict__ nnCount, const int* __restrict__ offsets,
+                                                      const int* __restrict__ slotPos, int* __restrict__ entEdge)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int wpb = (int)blockDim.x >> 6;
+    const long long nrows = (long long)B * M;
+    const long long wstride = (long long)gridDim.x * wpb;
+    for (long long row = (long long)blockIdx.x * wpb + ((int)threadIdx.x >> 6); row < nrows; row += wstride) {
+        const int cnt = nnCount[row];
+        if (cnt <= 0) continue;
+        const int b = (int)(row / M);
+        const int m = (int)(row - (long long)b * M);
+        const int* __restrict__ ob = offsets + (size_t)b * ((size_t)N + 1);
+        const int lim = cnt < K ? cnt : K;
+        for (int k = lane; k < lim; k += 64) {
+            const long long e = row * K + k;
+            entEdge[ob[nnIndex[e]] + slotPos[e]] = m * K + k;
+        }
+    }
+}
+
+// canonical order of the edge lists: ascending edge id (the ids of a list are distinct).  One wave per source, strips of 64
+// entries ranked against the whole list through the staging words, then copied back; no atomics
+__global__ __launch_bounds__(256) void tg_canonical_edges(int B, int N, const int* __restrict__ offsets, int* entEdge, int* stage)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const long long nsrc = (long long)B * N;
+    const long long wstride = (long long)gridDim.x * 4;
+    for (long long s = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6); s < nsrc; s += wstride) {
+        const int b = (int)(s / N);
+        const int* __restrict__ ob = offsets + (size_t)b * ((size_t)N + 1) + (s - (long long)b * N);
+        const int r0 = uniform(ob[0]), r1 = uniform(ob[1]);
+        if (r1 - r0 < 2) continue;
+        for (int t = r0; t < r1; t += 64) {
+            const int e = t + lane;
+            const int mine = e < r1 ? entEdge[e] : 0x7fffffff;
+            int rank = 0;
+            for (int u = r0; u < r1; u += 64) {
+                const int q = u + lane;
+                const int other = q < r1 ? entEdge[q] : 0x7fffffff;
+                const int cnt = (r1 - u) < 64 ? (r1 - u) : 64;
+                for (int j = 0; j < cnt; j++) rank += __shfl(other, j) < mine ? 1 : 0;
+            }
+            if (e < r1) stage[r0 + rank] = mine;
+        }
+        __threadfence();                        // the staged words were written by other lanes of this wave
+        for (int e = r0 + lane; e < r1; e += 64) entEdge[e] = stage[e];
+    }
+}
+
+}  // namespace sph3d
+
+extern "C" int sph3d_graph_transpose_finish_edges(int B, int N, int M, int K, const int* nn_index, const int* nn_count,
+                                                  int* offsets, int* ent_edge, void* workspace, size_t workspace_bytes,
+                                                  sph3d_stream_t stream)
+{
+    int rc = tg_dims_ok(B, N, M, K, 1, nullptr, workspace, workspace_bytes);
+    if (rc || B == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    const TgWs w = tg_ws(workspace, B, N, M, K, 1);
+    const long long total = (long long)B * M * K;
+    hipLaunchKernelGGL(tg_scan, dim3(B * w.chunks), dim3(256), 0, st, B, w.L, w.chunks, M * K, 1, w.deg, w.status, offsets,
+                       w.bin_used, (int*)nullptr);
+    long long fb = total > 0 ? ((long long)B * M + 15) / 16 : 0;
+    if (fb > 16384) fb = 16384;
+    if (fb > 0)
+        hipLaunchKernelGGL(tg_fill_edges, dim3((unsigned)fb), dim3(1024), 0, st, B, N, M, K, nn_index, nn_count, offsets, w.slot_pos,
+                           ent_edge);
+    // deterministic mode: the slot positions are dead now and stage the sort
+    if (deterministic_on() && total > 0) {
+        long long blocks = ((long long)B * N + 3) / 4;
+        if (blocks > 16384) blocks = 16384;
+        hipLaunchKernelGGL(tg_canonical_edges, dim3((unsigned)blocks), dim3(256), 0, st, B, N, offsets, ent_edge, w.slot_pos);
+    }
+    return check_launch("sph3d_graph_transpose_finish_edges");
+}
+
 extern "C" int sph3d_graph_balanced_order(int B, int N, int F, const int* offsets, int* order, sph3d_stream_t stream)
 {
     SPH3D_REQUIRE(B >= 0 && N > 0 && F > 0, "graph_balanced_order: bad dims B=%d N=%d F=%d", B, N, F);

@@ -105,8 +105,9 @@ def get_model(points, is_training, config=None, dropout_generator=None, points_r
             intra_idx, intra_cnt, intra_dst, indices = s3g_util.build_graph(
                 xyz, config.radius[l], config.nn_uplimit[l], config.num_sample[l], sample_method=config.sample,
                 **({"sample_key": sample_key, "level": l} if config.sample == 'IDS' else {}))
-            filt_idx = s3g_util.spherical_kernel(xyz, xyz, intra_idx, intra_cnt, intra_dst, config.radius[l],
-                                                 kernel=config.kernel)
+            # (config.kernel_fuzzy, absent = False: the fuzzy kernel's pair instead of the hard bins, as in GraphPlan)
+            kernel_fn = s3g_util.fuzzy_spherical_kernel if getattr(config, "kernel_fuzzy", False) else s3g_util.spherical_kernel
+            filt_idx = kernel_fn(xyz, xyz, intra_idx, intra_cnt, intra_dst, config.radius[l], kernel=config.kernel)
         net = _separable_conv3d_block(net, config.channels[l], config.binSize, intra_idx, intra_cnt, filt_idx,
                                       'conv' + str(l + 1), config.multiplier[l], reuse=reuse,
                                       weight_decay=config.weight_decay, with_bn=config.with_bn,
@@ -130,7 +131,8 @@ def get_model(points, is_training, config=None, dropout_generator=None, points_r
         nn_idx, nn_cnt, filt_idx = g["nn_idx"], g["nn_cnt"], g["filt_idx"]
     else:
         nn_idx, nn_cnt, nn_dst = s3g_util.build_global_graph(xyz, query, global_radius)
-        filt_idx = s3g_util.spherical_kernel(xyz, query, nn_idx, nn_cnt, nn_dst, global_radius, kernel=[8, 2, 1])
+        kernel_fn = s3g_util.fuzzy_spherical_kernel if getattr(config, "kernel_fuzzy", False) else s3g_util.spherical_kernel
+        filt_idx = kernel_fn(xyz, query, nn_idx, nn_cnt, nn_dst, global_radius, kernel=[8, 2, 1])
     net = s3g_util.separable_conv3d(net, config.global_channels, 17, config.global_multiplier, 'global_conv', nn_idx,
                                     nn_cnt, filt_idx, reuse=reuse, weight_decay=config.weight_decay,
                                     with_bn=config.with_bn, with_bias=config.with_bias, is_training=is_training)

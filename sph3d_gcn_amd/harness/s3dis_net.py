@@ -134,6 +134,10 @@ class GraphPlan:
         if config.sample not in ('FPS', 'random', 'IDS'):
             raise ValueError('Unknown sampling method.')
         self._ids = config.sample == 'IDS'
+        # config.kernel_fuzzy (not in the reference; absent or False: the hard bins, as always): every intra graph and the global
+        # graph carry the fuzzy spherical kernel's pair (filt_index, filt_frac) as "filt_idx" (tf_buildkernel.fuzzy_spherical_kernel,
+        # on the graph stream behind the search), and the backward pass gets the edge-id transpose instead of the binned one
+        self._fuzzy = bool(getattr(config, "kernel_fuzzy", False))
         self.sample_key = (int(sample_key[0]), int(sample_key[1]))
         self.need_backward = torch.is_grad_enabled() if need_backward is None else bool(need_backward)
         self.decoder = bool(decoder)
@@ -279,11 +283,20 @@ class GraphPlan:
             self.events.append(ev)
 
     # ---- graph construction proper (called on the graph stream, or lazily on CPU) ----
+    def _intra_graph(self, xyz, radius, uplimit):
+        """-> idx, cnt, dst, filt_idx of one point set: the fused search + bins, or (config.kernel_fuzzy) the search and the
+        fuzzy kernel's pair"""
+        c = self.config
+        if self._fuzzy:
+            idx, cnt, dst = s3g_util.neighbor_fn(xyz, xyz, radius=radius, nnsample=uplimit)
+            return idx, cnt, dst, s3g_util.fuzzy_spherical_kernel(xyz, xyz, idx, cnt, dst, radius, kernel=c.kernel)
+        return s3g_util.build_intra_graph(xyz, radius, uplimit, c.kernel, **self._bw_kw())
+
     def _make_enc(self, l):
         c = self.config
         xyz = self.xyz_layers[l]
         # util.py:29 + models/SPH3D_s3dis.py:57: neighbour graph and bins of one point set, one fused kernel on the GPU
-        idx, cnt, dst, filt = s3g_util.build_intra_graph(xyz, c.radius[l], c.nn_uplimit[l], c.kernel, **self._bw_kw())
+        idx, cnt, dst, filt = self._intra_graph(xyz, c.radius[l], c.nn_uplimit[l])
         if self._ids:
             return dict(intra_idx=idx, intra_cnt=cnt, filt_idx=filt, intra_dst=dst)      # (the level's sample reads the distances)
         return dict(intra_idx=idx, intra_cnt=cnt, filt_idx=filt)
@@ -314,7 +327,7 @@ class GraphPlan:
         radius, uplimit = c.radius[L - 1 - l], c.nn_uplimit[L - 1 - l]
         xyz_c, xyz_unpool = self.xyz_layers[L - l], self.xyz_layers[L - 1 - l]     # = reversed(xyz_layers)[l], [l + 1]
         # build_graph_deconv (util.py:52-58) + spherical_kernel: the intra half fused, the inter search as is
-        intra_idx, intra_cnt, intra_dst, filt_idx = s3g_util.build_intra_graph(xyz_c, radius, uplimit, c.kernel, **self._bw_kw())
+        intra_idx, intra_cnt, intra_dst, filt_idx = self._intra_graph(xyz_c, radius, uplimit)
         from .. import tf_nnquery
         unpool_k = getattr(c, "unpool_k", None)
         if unpool_k is not None:
@@ -335,8 +348,11 @@ class GraphPlan:
         if not self.need_backward:
             return
         from .. import _tgraph
-        _tgraph.transpose(g["intra_idx"], g["intra_cnt"], n_src_conv, bin_index=g["filt_idx"],
-                          num_bins=self.config.binSize)
+        if self._fuzzy:
+            _tgraph.transpose_edges(g["intra_idx"], g["intra_cnt"], n_src_conv)
+        else:
+            _tgraph.transpose(g["intra_idx"], g["intra_cnt"], n_src_conv, bin_index=g["filt_idx"],
+                              num_bins=self.config.binSize)
         if n_src_unpool is not None and self.config.unpool_method == 'mean':
             if getattr(self.config, "unpool_k", None) is not None:
                 # (a k-NN row lists distinct points)
@@ -394,7 +410,8 @@ class GraphPlan:
         xyz = self.xyz_layers[-1]
         query = self.global_query if self.global_query is not None else xyz.mean(dim=1, keepdim=True)
         nn_idx, nn_cnt, nn_dst = s3g_util.build_global_graph(xyz, query, self.global_radius)
-        filt = s3g_util.spherical_kernel(xyz, query, nn_idx, nn_cnt, nn_dst, self.global_radius, kernel=self.global_kernel)
+        kernel_fn = s3g_util.fuzzy_spherical_kernel if self._fuzzy else s3g_util.spherical_kernel
+        filt = kernel_fn(xyz, query, nn_idx, nn_cnt, nn_dst, self.global_radius, kernel=self.global_kernel)
         return dict(nn_idx=nn_idx, nn_cnt=nn_cnt, filt_idx=filt, query=query)
 
     def glob(self):
@@ -409,8 +426,9 @@ class GraphPlan:
             return
         self.main.wait_event(ev)
         for t in tensors:
-            if torch.is_tensor(t):
-                t.record_stream(self.main)
+            for u in (t if isinstance(t, (tuple, list)) else (t,)):      # (a fuzzy plan's "filt_idx" is a pair)
+                if torch.is_tensor(u):
+                    u.record_stream(self.main)
         self._synced.add(key)
 
     def input(self, points):

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import tf_conv3d, tf_pool3d, tf_unpool3d
 from .tf_nnquery import build_sphere_neighbor, build_cube_neighbor
 from .tf_sample import farthest_point_sample, inverse_density_sample, inverse_density_sample_keyed, random_sample
-from .tf_buildkernel import spherical_kernel
+from .tf_buildkernel import spherical_kernel, fuzzy_spherical_kernel
 from . import tf_gemm, tf_norm, _lib
 
 neighbor_fn = build_sphere_neighbor  # default nn search method
@@ -347,6 +347,27 @@ def separable_conv3d(inputs,
     # inputs may be a PAIR (a, b): the layer of the reference applied to tf.concat((a, b), axis=2) — same variables, same result —
     # with the depthwise kernels reading the two tensors in place (tf_conv3d.depthwise_conv3d_concat)
     pair = inputs if isinstance(inputs, (tuple, list)) else None
+    if isinstance(filt_index, (tuple, list)):
+        # the fuzzy spherical kernel: filt_index = (index, frac[, [n, p, q]]) of fuzzy_spherical_kernel (which records [n, p, q] on
+        # `index`).  Same variables in the same creation order; the plain depthwise op + the pointwise tail: the one-kernel
+        # layers and the concat kernels have no fuzzy form, their flags are ignored here and an input pair is concatenated
+        index, frac = filt_index[0], filt_index[1]
+        kernel_npq = filt_index[2] if len(filt_index) > 2 else getattr(index, "_sph3d_kernel", None)
+        if kernel_npq is None:
+            raise ValueError("separable_conv3d: a fuzzy filt_index pair needs its kernel [n, p, q] (fuzzy_spherical_kernel records it)")
+        if pair is not None:
+            inputs = torch.cat(tuple(pair), dim=2)
+        num_in_channels = inputs.shape[-1]
+        depthwise_kernel = _variable_with_weight_decay(scope + '/depthwise_weights',
+                                                       shape=[kernel_size, num_in_channels, depth_multiplier],
+                                                       use_xavier=use_xavier, stddev=stddev, with_decay=weight_decay)
+        outputs = tf_conv3d.fuzzy_depthwise_conv3d(inputs, depthwise_kernel, nn_index, nn_count, index, frac, kernel=kernel_npq)
+        batch_size = outputs.shape[0]
+        num_in_channels = outputs.shape[-1]
+        kernel = _variable_with_weight_decay(scope + '/weights', shape=[num_in_channels, num_out_channels],
+                                             use_xavier=use_xavier, stddev=stddev, with_decay=weight_decay)
+        return _gemm_tail(outputs.reshape(-1, num_in_channels), kernel, (batch_size, -1, num_out_channels), num_out_channels, scope,
+                          activation_fn, with_bn, with_bias, reuse, is_training)
     # (only on the HIP device: the oracle-backed CPU stand-ins of the tests have no one-kernel layer)
     infer_fused = (FUSE_SEPARABLE_INFERENCE and is_training is not None and not bool(is_training) and not torch.is_grad_enabled()
                    and (activation_fn is elu or activation_fn is None) and (pair[0] if pair is not None else inputs).is_cuda)

@@ -12,6 +12,8 @@ The angle function of the binning has two modes (``set_atan2``):
   level-0 slots; the exact list on the golden clouds is pinned in tests/golden/ref_gfx950.json).  The oracle-comparison
   tests select it explicitly (tests/conftest.py).
 """
+from typing import Tuple
+
 import torch
 
 from . import _lib
@@ -73,3 +75,52 @@ def spherical_kernel(database, query, nn_index, nn_count, nn_dist, radius, kerne
     database = database[:, :, 0:3]
     query = query[:, :, 0:3]
     return _spherical_kernel_impl(database, query, nn_index, nn_count, nn_dist, float(radius), int(n), int(p), int(q))
+
+
+# ---- fuzzy spherical kernel (csrc/fuzzy.hip; not in the reference tree) -------------------------------------------------------------
+def _fuzzy_spherical_kernel_impl(database: torch.Tensor, query: torch.Tensor, nn_index: torch.Tensor,
+                                 nn_count: torch.Tensor, nn_dist: torch.Tensor, radius: float,
+                                 n_azim: int, p_elev: int, q_radi: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _lib.require_device(database, query, nn_index, nn_count, nn_dist)
+    if database.dim() != 3 or database.shape[2] != 3:
+        raise ValueError("Shape of database points requires to be (batch, npoint, 3)")
+    if query.dim() != 3 or query.shape[2] != 3:
+        raise ValueError("Shape of query points requires to be (batch, mpoint, 3)")
+    if nn_index.dim() != 3:
+        raise ValueError("Shape of nn_index requires to be of rank 3")
+    database, query = _lib.f32(database), _lib.f32(query)
+    nn_index, nn_count, nn_dist = _lib.i32(nn_index), _lib.i32(nn_count), _lib.f32(nn_dist)
+    B, N, _ = database.shape
+    M = query.shape[1]
+    K = nn_index.shape[2]
+    filt_index = _lib.empty((B, M, K), torch.int32, database.device)
+    filt_frac = _lib.empty((B, M, K), torch.int32, database.device)
+    _lib.check(_lib.lib().sph3d_fuzzy_spherical_kernel(
+        B, N, M, K, n_azim, p_elev, q_radi, radius, _lib.ptr(database), _lib.ptr(query),
+        _lib.ptr(nn_index), _lib.ptr(nn_count), _lib.ptr(nn_dist), _lib.ptr(filt_index), _lib.ptr(filt_frac), _lib.stream_ptr()))
+    return filt_index, filt_frac
+
+
+_fuzzy_spherical_kernel = torch.library.custom_op("sph3d::fuzzy_spherical_kernel", mutates_args=())(_fuzzy_spherical_kernel_impl)
+
+
+@_fuzzy_spherical_kernel.register_fake
+def _(database, query, nn_index, nn_count, nn_dist, radius, n_azim, p_elev, q_radi):
+    return torch.empty_like(nn_index, dtype=torch.int32), torch.empty_like(nn_index, dtype=torch.int32)
+
+
+def fuzzy_spherical_kernel(database, query, nn_index, nn_count, nn_dist, radius, kernel=[8, 2, 3]):
+    """Trilinear kernel weights of every graph edge (same arguments as spherical_kernel).
+
+    returns  (filt_index, filt_frac), both [B, M, K] int32: filt_index is spherical_kernel's format applied to the LOWER corner
+             of the edge's cell of bin centres (0 for the query point itself and for unused slots), filt_frac packs the edge's
+             position between the lower and the upper corner per axis in 1/256: azimuth | elevation << 8 | radius << 16.
+             The angle function is always the shared one (set_atan2 does not apply).  No gradient.  include/sph3d.h states
+             the format; harness/fuzzy.py restates the op in numpy, bit for bit.
+    """
+    n, p, q = kernel
+    database = database[:, :, 0:3]
+    query = query[:, :, 0:3]
+    index, frac = _fuzzy_spherical_kernel_impl(database, query, nn_index, nn_count, nn_dist, float(radius), int(n), int(p), int(q))
+    index._sph3d_kernel = (int(n), int(p), int(q))       # for layers that are handed the pair without the kernel's shape
+    return index, frac

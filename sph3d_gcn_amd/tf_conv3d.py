@@ -165,6 +165,123 @@ def depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, bin_in
     return _depthwise_conv3d_grad_impl(input, filter, grad_output, nn_index, nn_count, bin_index)
 
 
+# ---- the fuzzy spherical kernel's convolution (csrc/fuzzy.hip; not in the reference tree) ---------------------------------------
+def _check_fuzzy(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q):
+    _check_conv(input, filter, nn_index, nn_count, filt_index)
+    if filt_frac.shape != filt_index.shape or filt_index.shape != nn_index.shape:
+        raise ValueError("filt_index and filt_frac should have the shape of nn_index")
+    if filter.shape[0] != n * p * q + 1:
+        raise ValueError("filter should hold n*p*q + 1 = %d bins, got %d" % (n * p * q + 1, filter.shape[0]))
+
+
+def _fuzzy_depthwise_conv3d_impl(input: torch.Tensor, filter: torch.Tensor, nn_index: torch.Tensor, nn_count: torch.Tensor,
+                                 filt_index: torch.Tensor, filt_frac: torch.Tensor, n_azim: int, p_elev: int,
+                                 q_radi: int) -> torch.Tensor:
+    _lib.require_device(input, filter, nn_index, nn_count, filt_index, filt_frac)
+    _check_fuzzy(input, filter, nn_index, nn_count, filt_index, filt_frac, n_azim, p_elev, q_radi)
+    input, filter = _lib.f32(input), _lib.f32(filter)
+    nn_index, nn_count, filt_index, filt_frac = _lib.i32(nn_index), _lib.i32(nn_count), _lib.i32(filt_index), _lib.i32(filt_frac)
+    B, N, C = input.shape
+    F, _, r = filter.shape
+    M, K = nn_index.shape[1], nn_index.shape[2]
+    output = torch.empty((B, M, C * r), dtype=torch.float32, device=input.device)
+    _lib.check(_lib.lib().sph3d_fuzzy_depthwise_conv3d(
+        B, N, M, F, C, r, K, n_azim, p_elev, q_radi, _lib.ptr(nn_index), _lib.ptr(nn_count), _lib.ptr(filt_index),
+        _lib.ptr(filt_frac), _lib.ptr(input), _lib.ptr(filter), _lib.ptr(output), _lib.stream_ptr()))
+    return output
+
+
+_fuzzy_depthwise_conv3d = torch.library.custom_op("sph3d::fuzzy_depthwise_conv3d", mutates_args=())(_fuzzy_depthwise_conv3d_impl)
+
+
+@_fuzzy_depthwise_conv3d.register_fake
+def _(input, filter, nn_index, nn_count, filt_index, filt_frac, n_azim, p_elev, q_radi):
+    return input.new_empty((input.shape[0], nn_index.shape[1], input.shape[2] * filter.shape[2]))
+
+
+def _fuzzy_depthwise_conv3d_grad_impl(input: torch.Tensor, filter: torch.Tensor, grad_output: torch.Tensor,
+                                      nn_index: torch.Tensor, nn_count: torch.Tensor, filt_index: torch.Tensor,
+                                      filt_frac: torch.Tensor, n_azim: int, p_elev: int,
+                                      q_radi: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    _lib.require_device(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac)
+    _check_fuzzy(input, filter, nn_index, nn_count, filt_index, filt_frac, n_azim, p_elev, q_radi)
+    input, filter, grad_output = _lib.f32(input), _lib.f32(filter), _lib.f32(grad_output)
+    nn_index, nn_count, filt_index, filt_frac = _lib.i32(nn_index), _lib.i32(nn_count), _lib.i32(filt_index), _lib.i32(filt_frac)
+    B, N, C = input.shape
+    F, _, r = filter.shape
+    M, K = nn_index.shape[1], nn_index.shape[2]
+    grad_input = torch.empty_like(input)
+    grad_filter = torch.empty_like(filter)
+    # grad_input gathers over the transposed graph whose entries name the edge (built once per graph)
+    offsets, ent_edge = _tgraph.transpose_edges(nn_index, nn_count, N)
+    l = _lib.lib()
+    wsb = l.sph3d_fuzzy_depthwise_conv3d_grad_workspace(B, N, M, F, C, r, K)
+    ws = _lib.scratch(wsb, input.device)
+    _lib.check(l.sph3d_fuzzy_depthwise_conv3d_grad(
+        B, N, M, F, C, r, K, n_azim, p_elev, q_radi, _lib.ptr(nn_index), _lib.ptr(nn_count), _lib.ptr(filt_index),
+        _lib.ptr(filt_frac), _lib.ptr(offsets), _lib.ptr(ent_edge), _lib.ptr(input), _lib.ptr(filter), _lib.ptr(grad_output),
+        _lib.ptr(grad_input), _lib.ptr(grad_filter), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    return grad_input, grad_filter
+
+
+_fuzzy_depthwise_conv3d_grad = torch.library.custom_op("sph3d::fuzzy_depthwise_conv3d_grad",
+                                                       mutates_args=())(_fuzzy_depthwise_conv3d_grad_impl)
+
+
+@_fuzzy_depthwise_conv3d_grad.register_fake
+def _(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, n_azim, p_elev, q_radi):
+    return torch.empty_like(input), torch.empty_like(filter)
+
+
+def _fuzzy_setup(ctx, inputs, output):
+    input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q = inputs
+    ctx.save_for_backward(input, filter, nn_index, nn_count, filt_index, filt_frac)
+    ctx.kernel = (n, p, q)
+
+
+def _fuzzy_backward(ctx, grad_output):
+    input, filter, nn_index, nn_count, filt_index, filt_frac = ctx.saved_tensors
+    gi, gf = _fuzzy_depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, *ctx.kernel)
+    return gi, gf, None, None, None, None, None, None, None
+
+
+_fuzzy_depthwise_conv3d.register_autograd(_fuzzy_backward, setup_context=_fuzzy_setup)
+
+
+class _FuzzyDepthwiseConv3dFn(torch.autograd.Function):
+    """eager path of the public API, as _DepthwiseConv3dFn"""
+
+    @staticmethod
+    def forward(ctx, input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q):
+        ctx.save_for_backward(input, filter, nn_index, nn_count, filt_index, filt_frac)
+        ctx.kernel = (n, p, q)
+        return _fuzzy_depthwise_conv3d_impl(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, filter, nn_index, nn_count, filt_index, filt_frac = ctx.saved_tensors
+        gi, gf = _fuzzy_depthwise_conv3d_grad_impl(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, *ctx.kernel)
+        return gi, gf, None, None, None, None, None, None, None
+
+
+def fuzzy_depthwise_conv3d(input, filter, nn_index, nn_count, filt_index, filt_frac, kernel=[8, 2, 3]):
+    """depthwise_conv3d over the fuzzy spherical kernel: every neighbour contributes to the (up to) eight bins around it.
+
+    filt_index, filt_frac  [B, M, K] int32, from tf_buildkernel.fuzzy_spherical_kernel with the same `kernel` = [n, p, q]
+    filter                 [n*p*q + 1, C, r]
+    returns    [B, M, C*r] fp32: out[b,m,c*r+j] = 1/nn_count[b,m] * sum_k input[b,nn_index[b,m,k],c] * sum_t coef[k,t] * filter[bin[k,t],c,j]
+               over the corners t of slot k (include/sph3d.h).  Any C and r; differentiable in `input` and `filter`, no float
+               atomics (grad_filter has the same bits on every run; grad_input too under deterministic()).
+    """
+    n, p, q = (int(v) for v in kernel)
+    return _FuzzyDepthwiseConv3dFn.apply(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q)
+
+
+def fuzzy_depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, kernel=[8, 2, 3]):
+    n, p, q = (int(v) for v in kernel)
+    return _fuzzy_depthwise_conv3d_grad_impl(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, n, p, q)
+
+
 # ---- the whole separable layer in one kernel, inference only (SURVEY 8f.3; csrc/sepconv.hip) ---------------------------
 def separable_fused_supported_dims(N, F, C, r, K, Cout):
     """shapes sph3d_separable_conv3d_fused covers, by dimensions"""
