@@ -1161,6 +1161,36 @@ int sph3d_masked_softmax_xent_parts(int N);
 int sph3d_masked_softmax_xent(int B, int N, int C, const float* logits, const long long* label, const float* inner_label,
                               float* loss_part, float* dlogits, sph3d_stream_t stream);
 
+/* the Lovasz-softmax loss (Berman, Triki, Blaschko, CVPR 2018) of every block and its gradient with respect to the logits
+ * (csrc/lovasz.hip; the float64 statement is harness/lovasz.py: lovasz_reference).  It is not an op of the reference tree.
+ * logits [B,N,C] fp32, label [B,N] int64, inner [B,N] fp32 or NULL (every row).  Per block b:
+ *   valid   row n is valid iff (inner == NULL or inner[b,n] > 0; NaN > 0 is false) and label[b,n] != ignore; n_b valid rows
+ *   probs   p = softmax(logits[b,n,:]) (maximum, expf, a sum in ascending c, a division), written for EVERY row
+ *   class   for a class c with G = #{valid n: label = c} > 0 (a "present" class): e_n = 1 - p[n,c] on the valid rows labelled c
+ *           (foreground), p[n,c] on the other valid rows; the valid rows in the order of DESCENDING e, ties by ASCENDING n (e is
+ *           one fp32 operation on probs, so the order is an integer function of the probs written: bits(e) descending, n ascending);
+ *           F_j foreground rows among the sorted positions 0..j, U_j = G + (j + 1) - F_j; the Lovasz gradient of the Jaccard loss
+ *               g_j = 1 / U_j on a foreground position,   (G - F_j) / (U_j (U_j - 1)) on a background position
+ *           (the paper's jaccard_j - jaccard_{j-1} with jaccard_j = (j + 1) / U_j, written without the cancellation; g >= 0 and
+ *           sum_j g_j = 1);  class_loss[b,c] = sum_j e_(j) g_j, and 0 for a class that is not present
+ *   loss    P_b present classes; loss[b] = (sum over c, ascending, of class_loss[b,c]) / P_b; 0 if P_b = 0
+ *   coef    coef[b,n,c] = d loss[b] / d p[n,c] = -g_rank(n) / P_b on foreground, +g_rank(n) / P_b on background; 0 on rows that are
+ *           not valid and for classes that are not present
+ *   dlogits dlogits[b,n,k] = p_k (coef_k - sum_c coef_c p_c), zeros on rows that are not valid.  dlogits == NULL: no gradient pass
+ *           (loss is produced all the same, with the same bits)
+ *   order   order[b,c,j], [B,C,N] int32: the row at sorted position j of class c (present or not), -1 for j >= n_b.  NULL: not written
+ * A valid row whose label lies outside [0, C), or whose probabilities are not finite, makes loss[b] and every dlogits row of block
+ * b NaN (class_loss and coef of that block are then unspecified); nothing is clamped and every read stays in range.
+ * probs and coef are workspaces the caller owns ([B,N,C] each); every reduction runs in a fixed order: the same inputs give the
+ * same bits, deterministic mode or not.  Three launches; no workspace beyond the arguments.
+ * N <= 16384 and C <= 1024 (the sort holds a block's keys in LDS): sph3d_lovasz_softmax_supported(N, C) -> 1 | 0 on the host.
+ * -> SPH3D_OK; SPH3D_EINVAL for B < 0, N <= 0, C <= 0, B N C > 2^40, B C >= 2^31, B >= 2^16 or a null pointer other than
+ * inner, dlogits and order; SPH3D_EUNSUPPORTED, before any launch and before the pointers are looked at, outside the shapes above. */
+int sph3d_lovasz_softmax_supported(int N, int C);
+int sph3d_lovasz_softmax(int B, int N, int C, const float* logits, const long long* label, const float* inner, long long ignore,
+                         float* probs, float* coef, float* class_loss, float* loss, float* dlogits, int* order,
+                         sph3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

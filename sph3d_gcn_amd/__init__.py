@@ -8,15 +8,16 @@ Layout (only what the path needs):
   tf_gemm.py       the pointwise 1x1 feature GEMM (tf.matmul in the reference)
   tf_surface.py    surface normals from a neighbour graph or a flat cloud (not in the reference)
   tf_dropout.py    dropout whose mask is a counter-based draw of (seed, step) (tf.layers.dropout in the reference)
+  tf_loss.py       training losses beyond the cross-entropy: Lovasz-softmax per block (not in the reference)
   sph3gcn_util.py  the glue with the reference's public signatures (utils/sph3gcn_util.py)
   harness/         torch re-statement of the model graphs' call pattern, used by bench/smoke only
 """
 from . import _lib  # noqa: F401
-from . import tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm, tf_surface, tf_dropout  # noqa: F401
+from . import tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm, tf_surface, tf_dropout, tf_loss  # noqa: F401
 from . import sph3gcn_util  # noqa: F401
 from ._tgraph import set_deterministic, is_deterministic, deterministic  # noqa: F401
 from .tf_gemm import set_float32_matmul_precision, get_float32_matmul_precision, float32_matmul_precision  # noqa: F401
 
-__all__ = ["tf_nnquery", "tf_buildkernel", "tf_conv3d", "tf_pool3d", "tf_unpool3d", "tf_sample", "tf_gemm", "tf_surface", "tf_dropout",
+__all__ = ["tf_nnquery", "tf_buildkernel", "tf_conv3d", "tf_pool3d", "tf_unpool3d", "tf_sample", "tf_gemm", "tf_surface", "tf_dropout", "tf_loss",
            "sph3gcn_util", "set_deterministic", "is_deterministic", "deterministic", "set_float32_matmul_precision",
            "get_float32_matmul_precision", "float32_matmul_precision"]
