@@ -806,6 +806,40 @@ int sph3d_train_update(long long n, float* param, const float* grad, float* slot
                        float beta1_or_momentum, float beta2, float eps, int step, float grad_scale, long long* nonfinite,
                        sph3d_stream_t stream);
 
+/* ---- the guarded update: clip by the global norm, skip a step whose gradient is not finite, keep an averaged copy of the
+ * weights — decided on the device and consumed there, no host read (harness/guard.py is the statement, bit for bit).  Three
+ * launches on `stream`: the sum of squares, the decision, the update.  With gg0_i = fl32(grad_scale grad_i):
+ *   bad  = #{i : gg0_i not finite};   S = sum of (double)gg0_i^2 in ONE fixed order (2^18 lanes, lane l adds the elements
+ *          i = l mod 2^18 in ascending i from +0.0, the lanes are reduced by the adjacent-pair tree), norm = sqrt(S) in double:
+ *          the same bits whatever the pointers' alignment; a NaN's payload is the one thing left open;
+ *   skip = skip_nonfinite && bad > 0: skipped += 1, nonfinite += bad, and param, the slots, ema and the powers keep their bits;
+ *   else   applied += 1; rule 0: b1pow *= (double)beta1, b2pow *= (double)beta2, lr_t = fl32(lr sqrt(1 - b2pow) / (1 - b1pow))
+ *          (running powers: lr_t is a function of the APPLIED count, which the host cannot know; sph3d_train_update's `step` has
+ *          no counterpart here); rule 1: lr_t = lr;
+ *          c = clip_norm / (norm + 1e-6) in double; clipped = clip_norm > 0 && bad == 0 && c < 1; c32 = fl32(c) when
+ *          clip_norm > 0 && bad == 0, else 1; gg_i = fl32(c32 gg0_i) when clipped, else gg0_i; sph3d_train_update's rule 0 or 1
+ *          on gg, operation for operation (with bad > 0 and no skip the NaN propagates as there, nonfinite += bad);
+ *          ema (nullable: no average): d = min(ema_decay, (1 + a) / (10 + a)) with a = the updates applied before this one
+ *          (tf.train.ExponentialMovingAverage(decay, num_updates)), om = fl32(1 - d), ema_i -= fl32(fl32(ema_i - param'_i) om).
+ * state: SPH3D_GUARD_STATE_WORDS 8-byte words on the device, carried from step to step; the caller creates it with every word 0
+ * except b1pow = b2pow = 1.0 and flag = 1.  Words (d: double, u: unsigned 64-bit; the three fp32 scalars are kept as doubles):
+ *    0 d S              1 u bad (this step)   2 u applied          3 u skipped        4 u clipped_steps
+ *    5 d b1pow          6 d b2pow             7 d last_norm        8 d max_norm_seen (a NaN norm never replaces it)
+ *    9 d lr_t          10 d c32              11 d om              12 u flag: 0 skipped, 1 applied, 3 applied and clipped
+ *   13..15 reserved (0).   Words 7..11 are those of the last APPLIED step; a skipped step writes words 0, 1, 3 and 12 only.
+ * workspace: sph3d_train_guard_workspace(n) bytes, 8-byte aligned, the caller's (no entry allocates); dead when the call's
+ * kernels are done.  n == 0 is a no-op.  SPH3D_EINVAL: a rule outside {0, 1}, n < 0, a null buffer with n > 0, ema with an
+ * ema_decay outside (0, 1), a NaN clip_norm; SPH3D_EWORKSPACE: a null, short or misaligned workspace. */
+#define SPH3D_GUARD_STATE_WORDS 16
+size_t sph3d_train_guard_workspace(long long n);
+int sph3d_train_update_guarded(long long n, float* param, const float* grad, float* slot0, float* slot1, float* ema, int rule, float lr,
+                               float beta1_or_momentum, float beta2, float eps, float grad_scale, float clip_norm, int skip_nonfinite,
+                               float ema_decay, long long* state, long long* nonfinite, void* workspace, size_t workspace_bytes,
+                               sph3d_stream_t stream);
+/* dst[0..n) = src[0..n) (fp32) if the state's last decision was a skip (flag == 0); otherwise nothing is written.  What a step
+ * wrote before the decision existed (the batch-norm moving statistics) is put back this way from a copy taken before it. */
+int sph3d_guard_restore(long long n, float* dst, const float* src, const long long* state, sph3d_stream_t stream);
+
 /* ---- the reference's per-step training metrics and its one-pass validation counts (train_s3dis.py:371-376, :461-474) on the
  * device, without the copy of the logits to the host.  logits [B,N,C] fp32, label [B,N] int32, inner [B,N] int32 or NULL (every
  * row counts: the ShapeNet, RueMonge and ModelNet lines; ModelNet with N = 1).  For every counted row (inner > 0): with the

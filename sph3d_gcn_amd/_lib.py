@@ -101,6 +101,9 @@ SIGNATURES = {
     "sph3d_lovasz_softmax": (_I, [_I, _I, _I] + [_P] * 3 + [_L] + [_P] * 6 + [_P]),
     "sph3d_adam_step": (_I, [ctypes.c_longlong] + [_P] * 4 + [_F] * 4 + [_I, _P]),
     "sph3d_train_update": (_I, [_L] + [_P] * 4 + [_I] + [_F] * 4 + [_I, _F, _P, _P]),
+    "sph3d_train_guard_workspace": (_S, [_L]),
+    "sph3d_train_update_guarded": (_I, [_L] + [_P] * 5 + [_I] + [_F] * 6 + [_I, _F, _P, _P, _P, _S, _P]),
+    "sph3d_guard_restore": (_I, [_L, _P, _P, _P, _P]),
     "sph3d_train_metrics": (_I, [_I] * 3 + [_P] * 4 + [_I] + [_P] * 3 + [_P]),
     "sph3d_dropout_keyed": (_I, [_I, _L, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _L, _I, ctypes.c_uint, _F, _P]),
     "sph3d_feed_assemble": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I] + [_P] * 5),

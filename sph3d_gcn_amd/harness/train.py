@@ -31,6 +31,7 @@ import torch
 
 from .. import _lib, _tgraph, tf_gemm, tf_norm
 from . import dist as hdist
+from . import optim as hoptim
 
 # ---------------------------------------------------------------------------------------------------------------
 # the schedule (train_s3dis.py:95-103)
@@ -279,11 +280,17 @@ class Trainer:
     then does a resumed run drop what the uninterrupted one drops; None follows `deterministic`.  Other models are called as
     before.  matmul_precision: "highest" | "high" | "medium" — train_step, eval_one_epoch and fit run under
     sph3d_gcn_amd.float32_matmul_precision(level) and the process setting is back at its previous value when they
-    return; None leaves the process setting alone."""
+    return; None leaves the process setting alone.  clip_norm, skip_nonfinite, ema_decay: the guarded update (optim.Guard,
+    DESIGN.md 4.29) — with all three absent no guard exists and the step is the plain one.  The guard runs after the gradient's
+    all-reduce, so every rank takes the same decision from the same summed gradient.  With skip_nonfinite the model's float32
+    buffers (the batch-norm moving statistics, written by the forward pass before anyone knows the step is bad) become views of
+    one flat buffer: a device copy is taken before the forward pass and put back after a skipped update, decided on the device
+    like the skip itself; train_one_epoch then raises when more than skip_limit steps of a log interval were skipped.  With
+    ema_decay, eval_one_epoch evaluates the averaged weights (`with trainer.ema_weights():`)."""
 
     def __init__(self, model, loss_fn, optimizer_factory, schedule, num_cls, line=s3dis_line, prime=None, seed=0, log_every=50,
                  max_to_keep=500, grad_scale=1.0, class_names=None, log=print, sync_bn=False, deterministic=False, keyed_dropout=None,
-                 matmul_precision=None):
+                 matmul_precision=None, clip_norm=None, skip_nonfinite=False, ema_decay=None, skip_limit=10):
         if prime is None:
             raise ValueError("Trainer: `prime` (one batch of the training shapes) is needed to create the variables")
         self.model, self.loss_fn, self.schedule, self.line = model, loss_fn, schedule, line
@@ -312,6 +319,36 @@ class Trainer:
         if hasattr(self.opt, "nonfinite"):
             self.opt.nonfinite = self.metrics.update_nonfinite          # (read with the metrics: no copy of its own)
         self.flat.broadcast_params()
+        self.guard, self.skip_limit = None, int(skip_limit)
+        self._buf_flat = self._buf_copy = None
+        self._guard_seen = None                                         # the GuardStats of the last log interval's read
+        if clip_norm is not None or skip_nonfinite or ema_decay is not None:
+            guard = hoptim.Guard(clip_norm, skip_nonfinite, ema_decay)
+            if not isinstance(self.opt, hoptim._FlatRule):
+                raise ValueError("Trainer: clip_norm / skip_nonfinite / ema_decay need FlatTFAdam or FlatNesterov, %s has no guarded "
+                                 "update" % type(self.opt).__name__)
+            self.opt.guard = guard
+            self.guard = guard.bind(self.flat.flat_param)               # (after the broadcast: the EMA starts from rank 0's weights)
+            self._guard_seen = hoptim.GuardStats(0, 0, 0, 0.0, 0.0)
+            if guard.skip_nonfinite:
+                self._flatten_buffers()
+
+    def _flatten_buffers(self):
+        """the model's float32 buffers as views of ONE flat buffer, each on a 16-byte boundary (as FlatGradAllReduce lays the
+        parameters out), and a second buffer of the same size for the copy a step takes before its forward pass"""
+        bufs = [b for _n, b in self.model.named_buffers() if b.dtype == torch.float32]
+        n = sum((b.numel() + 3) // 4 * 4 for b in bufs)
+        if n == 0:
+            return
+        self._buf_flat = torch.zeros(n, dtype=torch.float32, device=self.device)
+        off = 0
+        with torch.no_grad():
+            for b in bufs:
+                k = b.numel()
+                self._buf_flat[off:off + k].copy_(b.reshape(-1))
+                b.data = self._buf_flat[off:off + k].view_as(b)
+                off += (k + 3) // 4 * 4
+        self._buf_copy = torch.empty_like(self._buf_flat)
 
     # ---- one step --------------------------------------------------------------------------------------------
     def _total_loss(self, pred, batch):
@@ -355,21 +392,48 @@ class Trainer:
     def _train_step(self, item, feed):
         # sync_bn: every training-mode batch norm takes its statistics over all ranks' rows, one small all-reduce per layer and
         # direction (every rank runs the same layers, each with at least one row; the row counts may differ)
+        if self._buf_flat is not None:
+            self._buf_copy.copy_(self._buf_flat)         # the moving statistics as they are before the forward pass touches them
         with (tf_norm.sync(hdist.stat_all_reduce) if self.sync_bn else contextlib.nullcontext()):
             batch, pred, loss, ready = self._forward(item, True)
             self.flat.backward(loss)
         self.flat.all_reduce()
         self.opt.lr = self.schedule(self.global_step)
         self.opt.step()
+        if self._buf_flat is not None:
+            self.guard.restore(self._buf_flat, self._buf_copy)          # (writes only when the update was skipped)
         self.metrics.add(pred, batch.label, batch.inner, loss.detach().reshape(1))
         if ready is not None and feed is not None and hasattr(feed, "done"):
             feed.done(ready)
         self.global_step += 1
 
-    def _check(self, r, first_step):
+    def _check(self, r, first_step, skipped=None):
+        """skipped: the steps of the interval that a skip_nonfinite guard skipped, None without such a guard.  Those steps changed
+        nothing, so their non-finite rows and gradient elements are no reason to stop (every step whose gradient had one WAS
+        skipped; non-finite rows without a skipped step stop the run as before); too many of them are."""
+        if skipped is not None:
+            if skipped > self.skip_limit:
+                raise _lib.Sph3dError("training skipped %d of the steps %d..%d (skip_limit %d): %d rows with non-finite logits, %d "
+                                      "non-finite gradient elements" % (skipped, first_step, self.global_step - 1, self.skip_limit,
+                                                                        r.nonfinite, r.update_nonfinite))
+            if skipped > 0 or not r.nonfinite:
+                return
         if r.nonfinite or r.update_nonfinite:
             raise _lib.Sph3dError("training diverged in steps %d..%d: %d rows with non-finite logits, %d non-finite gradient elements"
                                   % (first_step, self.global_step - 1, r.nonfinite, r.update_nonfinite))
+
+    def _guard_interval(self):
+        """with a guard: one read of its state, the interval's log line -> the steps skipped since the last read (None unless
+        the guard skips)"""
+        if self.guard is None:
+            return None
+        now, was = self.guard.read(), self._guard_seen
+        self._guard_seen = now
+        if self.rank == 0:
+            self.log('guard: applied %d skipped %d clipped %d (run: %d / %d / %d) last norm %g max norm %g'
+                     % (now.applied - was.applied, now.skipped - was.skipped, now.clipped_steps - was.clipped_steps, now.applied,
+                        now.skipped, now.clipped_steps, now.last_norm, now.max_norm_seen))
+        return now.skipped - was.skipped if self.guard.skip_nonfinite else None
 
     def train_one_epoch(self, feed):
         """feed: any iterable of a feed's items (the last element: the ready event or None).  Every log_every steps one read,
@@ -387,18 +451,45 @@ class Trainer:
                     self.log(' ---- batch: %03d ----' % idx)
                     self.log('mean loss: %f' % r.mean_loss)
                     self.log('accuracy: %f' % r.accuracy)
-                self._check(r, first)
+                self._check(r, first, self._guard_interval())
                 first = self.global_step
         if idx % self.log_every != 0:
             r = self.metrics.read()
             self.metrics.reset()
             out.append(r)
-            self._check(r, first)
+            self._check(r, first, self._guard_interval())
         return out
 
-    def eval_one_epoch(self, feed):
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside, the model's parameters are the averaged weights and the guard's EMA buffer holds the live ones; on the way
+        out they are exchanged back, bit for bit.  Take no training step inside."""
+        if self.guard is None or self.guard.ema is None:
+            raise _lib.Sph3dError("Trainer.ema_weights: no EMA (construct the Trainer with ema_decay)")
+        p, e = self.flat.flat_param.data, self.guard.ema
+
+        def exchange():
+            with torch.no_grad():
+                tmp = p.clone()
+                p.copy_(e)
+                e.copy_(tmp)
+        exchange()
+        try:
+            yield
+        finally:
+            exchange()
+
+    def eval_one_epoch(self, feed, use_ema=None):
         """one pass without voting (train_s3dis.py:394-495): inference mode, no gradients (the loss without its gradient pass),
-        one read at the end and the reference's evaluation lines -> MetricsResult"""
+        one read at the end and the reference's evaluation lines -> MetricsResult.  use_ema: evaluate the averaged weights
+        (ema_weights()); None: yes when an EMA exists"""
+        has_ema = self.guard is not None and self.guard.ema is not None
+        if use_ema is None:
+            use_ema = has_ema
+        with (self.ema_weights() if use_ema else contextlib.nullcontext()):
+            return self._eval_one_epoch(feed)
+
+    def _eval_one_epoch(self, feed):
         m = self.eval_metrics
         m.reset()
         with self._mode(), torch.no_grad():
@@ -421,8 +512,9 @@ class Trainer:
 
     # ---- checkpoints ------------------------------------------------------------------------------------------
     def save(self, ckpt_dir, epoch=None):
-        """model.ckpt-<epoch>.pt: the model's state_dict (moving statistics included), the optimiser's, global_step, epoch, the
-        schedule's settings and the feed seed; rank 0 writes, and prunes the oldest beyond max_to_keep -> the path"""
+        """model.ckpt-<epoch>.pt: the model's state_dict (moving statistics included), the optimiser's (with a guard: its state
+        and the averaged weights, so both copies of the weights), global_step, epoch, the schedule's settings and the feed seed;
+        rank 0 writes, and prunes the oldest beyond max_to_keep -> the path"""
         epoch = self.epoch if epoch is None else int(epoch)
         path = checkpoint_path(ckpt_dir, epoch)
         if self.rank != 0:
@@ -456,6 +548,8 @@ class Trainer:
         if "schedule" in state and hasattr(self.schedule, "settings"):
             self.schedule.__init__(**state["schedule"])
         self.flat.broadcast_params()
+        if self.guard is not None:
+            self._guard_seen = self.guard.read()
         return state
 
     def fit(self, train_feed_factory, epochs, eval_feed_factory=None, ckpt_dir=None):
