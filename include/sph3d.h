@@ -1225,6 +1225,36 @@ int sph3d_lovasz_softmax(int B, int N, int C, const float* logits, const long lo
                          float* probs, float* coef, float* class_loss, float* loss, float* dlogits, int* order,
                          sph3d_stream_t stream);
 
+/* ---- the augmentation stage (csrc/augment.hip; harness/augment.py states it in numpy): the indoor-segmentation recipes published
+ * since the reference (chromatic auto-contrast, translation and jitter, colour drop, flips, anisotropic scaling, elastic
+ * distortion, Mix3D scene mixing), applied IN PLACE to an assembled batch.  points [B,N,C] fp32 with xyz in channels 0:3, C in
+ * {3, 6, 9}; label [B,N] int32; inner [B,N] int32 or NULL.  Every draw is a pure function of (seed, step, b, purpose, counter) of
+ * csrc/feed_draws.hpp, purposes 32..38.  Bit k of cloud b is on iff bit k of `enable` is set and the high word of
+ * draw(ck_b, 32, k) is below threshold[k] (an integer comparison; threshold in [0, 2^32]); MIX (bit 0) is gated once per pair
+ * (2i, 2i+1) from the even cloud's key.  Order on the destination cloud: MIX, FLIPX, FLIPY, ASCALE, ELASTIC (two passes), then
+ * AUTOCONTRAST, CTRANSLATE, CJITTER, CDROP on the three channels at rgb_offset.  A cloud whose gates are all off is copied bit
+ * for bit.  Integer outputs (label, inner, which slot came from which cloud, the counters) equal the numpy statement bit for bit.
+ *   params      by value.  rgb_offset / normal_offset: first channel of the colour / the normal, -1 for none.  inv_g[p] =
+ *               (float)(1 / g_p), scale[p] = (float)(mag_p / (729 * 2^20)): the blurred lattice is kept as exact integers.
+ *               max_nodes: the largest node box (cells + 5 per axis) a cloud's lattice may take.
+ *   workspace   sph3d_augment_workspace(B, N, max_nodes) bytes, 16-byte aligned, the caller's; dead when the call's kernels are done.
+ *   status      [3] int64 or NULL, accumulated, never zeroed or read here: elastic passes skipped [0], [1]; pairs mixed [2].
+ * Nothing is allocated, nothing is read back, no floating-point atomic is used: the per-cloud statistics are min / max of floats
+ * per half cloud (one workgroup each) and integer atomic min / max of cell indices.  At most six launches on `stream`.
+ * SPH3D_EINVAL: C, an offset, a threshold, max_nodes (< 216 or > 2^24), the colour range, a colour bit without rgb_offset, the
+ * alignment or the workspace size. */
+typedef struct sph3d_augment_params {
+    unsigned long long threshold[9];
+    unsigned int enable;
+    int rgb_offset, normal_offset, max_nodes;
+    float rgb_lo, rgb_hi;
+    float inv_g[2], scale[2];
+} sph3d_augment_params;
+size_t sph3d_augment_workspace(int B, int N, int max_nodes);
+int sph3d_augment_apply(int B, int N, int C, float* points, int* label, int* inner, unsigned long long seed,
+                        unsigned long long step, sph3d_augment_params params, void* workspace, size_t workspace_bytes,
+                        long long* status, sph3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,14 @@ _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); one entry per declaration in include/sph3d.h
 _I, _F, _P, _S, _L = _c_int, _c_float, _vp, _c_size_t, ctypes.c_longlong
+
+
+class AugmentParams(ctypes.Structure):
+    """include/sph3d.h: sph3d_augment_params, passed by value"""
+    _fields_ = [("threshold", ctypes.c_ulonglong * 9), ("enable", ctypes.c_uint), ("rgb_offset", _I), ("normal_offset", _I),
+                ("max_nodes", _I), ("rgb_lo", _F), ("rgb_hi", _F), ("inv_g", _F * 2), ("scale", _F * 2)]
+
+
 SIGNATURES = {
     "sph3d_abi_version": (_I, []),
     "sph3d_last_error": (ctypes.c_char_p, []),
@@ -163,6 +171,8 @@ SIGNATURES = {
     "sph3d_elu_bn_forward_apply": (_I, [_I] * 2 + [_P] * 6 + [_F, _F] + [_P] * 4 + [_P]),
     "sph3d_elu_bn_backward_sums": (_I, [_I] * 2 + [_P] * 7 + [_P, _S, _P]),
     "sph3d_elu_bn_backward_apply": (_I, [_I] * 2 + [_P] * 8 + [_P, _S, _P]),
+    "sph3d_augment_workspace": (_S, [_I] * 3),
+    "sph3d_augment_apply": (_I, [_I] * 3 + [_P] * 3 + [ctypes.c_ulonglong, ctypes.c_ulonglong, AugmentParams, _P, _S, _P, _P]),
 }
 # test-only hook exported by the library but not part of the reference surface
 _EXTRA = {

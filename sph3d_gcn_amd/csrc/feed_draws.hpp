@@ -16,7 +16,12 @@ constexpr unsigned long long kFeedGold = 0x9e3779b97f4a7c15ull;
 constexpr int kFeedRounds = 6;
 enum : unsigned long long { kFeedPerm = 1, kFeedRepl = 2, kFeedTurn = 3, kFeedTilt = 4, kFeedJitter = 5, kFeedScale = 6,
                             kFeedShift = 7, kFeedIds = 8 /* + level, 0 <= level < 8: idsample.hip */,
-                            kFeedDropout = 16 /* + layer, 0 <= layer < kFeedDropoutLayers: dropout.hip */ };
+                            kFeedDropout = 16 /* + layer, 0 <= layer < kFeedDropoutLayers: dropout.hip */,
+                            // the augmentation stage (augment.hip; harness/augment.py states the counters)
+                            kFeedAugGate = 32 /* counter = the gate's bit */, kFeedAugScale = 33 /* counter = axis */,
+                            kFeedAugField = 34 /* + pass, 0 <= pass < 2; counter = the packed node */,
+                            kFeedAugContrast = 36, kFeedAugCtrans = 37 /* counter = channel */,
+                            kFeedAugCnoise = 38 /* counters 2 slot, 2 slot + 1 */ };
 constexpr int kFeedDropoutLayers = 16;
 
 __host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long long z)

@@ -253,11 +253,11 @@ class FacadeFeed(feed.TwoSetFeed):
     An epoch visits every facade `repeat` times (epoch_plan above).  The last, smaller batch gets train_recipe of its own size.
     `recipe`: a mask for every cloud instead of the training recipe (0: no augmentation)."""
 
-    def __init__(self, pool, batch_size, num_point, seed, repeat=REPEAT, recipe=None, rank=0, world=1, stream=None):
+    def __init__(self, pool, batch_size, num_point, seed, repeat=REPEAT, recipe=None, rank=0, world=1, stream=None, post=None):
         self.repeat = int(repeat)
         if self.repeat <= 0 or len(pool) * self.repeat >= 1 << 31:
             raise ValueError("FacadeFeed: repeat>0 and len(pool)*repeat<2^31 required")
-        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream, post)
         self._recipe = train_recipe if recipe is None else (lambda b: check_recipe(int(recipe), b))
         self._recipe(self.batch_size)                       # (a bad mask fails here, not in the first epoch)
         self._recipes = {}

@@ -406,9 +406,13 @@ class TwoSetFeed:
     overwrites a set it waits, on its stream, for the event handed back with `done(ready[, event])` for that set — or, when
     none was handed back, for everything issued so far on the stream that is current when the next item is asked for.  The
     second form is safe and slow: item i+2 is then assembled behind ALL of step i+1, so the plan of step i+2 no longer overlaps
-    the step before it (+20 % per step); hand the event back, as early as the last reader of the batch."""
+    the step before it (+20 % per step); hand the event back, as early as the last reader of the batch.
 
-    def __init__(self, pool, batch_size, num_point, seed, rank=0, world=1, stream=None):
+    POST.  `post`, if given, is called as post(seed, step, out) behind every batch's launch, with the feed's stream current and
+    before `ready` is recorded: a second stage that works in place on the assembled set (harness/augment.py: Stage).  Without
+    it a feed launches exactly what its `_launch` launches."""
+
+    def __init__(self, pool, batch_size, num_point, seed, rank=0, world=1, stream=None, post=None):
         import torch
         if batch_size <= 0 or num_point <= 0:
             raise ValueError("%s: batch_size>0 and num_point>0 required" % type(self).__name__)
@@ -417,6 +421,7 @@ class TwoSetFeed:
         self.pool, self.batch_size, self.num_point, self.seed = pool, int(batch_size), int(num_point), int(seed)
         self.rank, self.world, self.epoch = int(rank), int(world), 0
         self.stream = stream if stream is not None else torch.cuda.Stream(device=pool.device)
+        self.post = post
         self._sets = [{"out": self._new_set(pool.device), "ready": torch.cuda.Event(), "released": None, "used": False}
                       for _ in range(2)]
         self._turn = 0
@@ -470,6 +475,8 @@ class TwoSetFeed:
         out = tuple(t[:b] for t in s["out"])
         with torch.cuda.stream(self.stream):
             self._launch(step, ids_dev, out)
+            if self.post is not None:
+                self.post(self.seed, step, out)
             s["ready"].record(self.stream)
         return out + (s["ready"],)
 
@@ -503,9 +510,9 @@ class DeviceFeed(TwoSetFeed):
             ...                                                  # backward, optimiser
     """
 
-    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None):
+    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None, post=None):
         self.augment = bool(augment)
-        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream, post)
 
     def _new_set(self, dev):
         import torch

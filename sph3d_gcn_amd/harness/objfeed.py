@@ -283,8 +283,8 @@ class ObjectFeed(feed.TwoSetFeed):
     point); category [b] int32 is gathered from the pool on the same stream.  `recipe`: a mask for every cloud instead of the
     dataset's training recipe (0: no augmentation)."""
 
-    def __init__(self, pool, batch_size, num_point, seed, dataset="shapenet", recipe=None, rank=0, world=1, stream=None):
-        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
+    def __init__(self, pool, batch_size, num_point, seed, dataset="shapenet", recipe=None, rank=0, world=1, stream=None, post=None):
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream, post)
         self._recipe = (lambda b: train_recipe(b, dataset)) if recipe is None else (lambda b: check_recipe(int(recipe), b))
         self._recipe(self.batch_size)                       # (a bad dataset name or mask fails here, not in the first epoch)
         self._recipes = {}

@@ -216,10 +216,10 @@ class ScanNetFeed(feed.TwoSetFeed):
 
     The last, smaller batch gets train_recipe of its own size.  augment=False: every mask is 0."""
 
-    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None):
+    def __init__(self, pool, batch_size, num_point, seed, augment=True, rank=0, world=1, stream=None, post=None):
         self.augment = bool(augment)
         self._recipes = {}
-        super().__init__(pool, batch_size, num_point, seed, rank, world, stream)
+        super().__init__(pool, batch_size, num_point, seed, rank, world, stream, post)
 
     def recipe(self, b):
         return train_recipe(b) if self.augment else np.zeros((int(b),), dtype=np.int32)
