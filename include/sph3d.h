@@ -267,6 +267,16 @@ int sph3d_graph_transpose_finish(int B, int N, int M, int K, int F,
 int sph3d_gather_rows_count(int B, int N, int S, int K, const int* pairs, const int* nn_index, const int* nn_count,
                             int* out_index, int* out_count, void* transpose_workspace, size_t transpose_workspace_bytes,
                             sph3d_stream_t stream);
+/* The same copy with a ROW LINK in place of the counting phase, for sph3d_max_pool3d_grad_rows: no transposed pooling graph is
+ * built at all.  first [B, N] (zero-filled by the call) and next [B, S]:
+ *   first[b, p] = 0 when no pooled row of cloud b copies intra row p, else (1 + j) for one such row j, with bit 31 set when
+ *                 there are more of them (a sampler may return a point more than once);
+ *   next[b, j]  = 0, or 1 + the next pooled row that copies the same p.  Every pooled row is reached exactly once.
+ * The order of a chain is the order of arrival: SPH3D_EUNSUPPORTED in deterministic mode.  The caller promises
+ * pairs[b*S + j][0] == b (a pooled row copies a row of its own cloud; what a sampler's index pairs are); out-of-range pairs are
+ * clamped as in sph3d_gather_rows_count.  S < 2^31 - 1. */
+int sph3d_gather_rows_link(int B, int N, int S, int K, const int* pairs, const int* nn_index, const int* nn_count,
+                           int* out_index, int* out_count, int* first, int* next, sph3d_stream_t stream);
 /* sph3d_graph_transpose_finish that also writes sph3d_graph_balanced_order's permutation (order[B*N]; NULL: none) from inside its
  * fill launch: scan (one pass) + fill/order = two launches per graph. */
 int sph3d_graph_transpose_finish_ordered(int B, int N, int M, int K, int F,
@@ -402,6 +412,15 @@ int sph3d_max_pool3d_grad_t(int B, int N, int M, int C, const int* offsets, cons
                             const int* max_index, const float* grad_output,
                             const float* addend /* optional [B,N,C]: another gradient of the same input, added in (NULL: none) */,
                             float* grad_input, sph3d_stream_t stream);
+/* the same gradient for a pooling graph whose M rows are rows of the level's intra graph (sph3d_gather_rows_link), without a
+ * transposed pooling graph: offsets / ent_key are the transposed INTRA graph of the N points (F segments per source, packed or
+ * plain entries), first / next the pooling graph's row link, nn_count / max_index / grad_output those of the M pooled rows.
+ * Same terms per element as sph3d_max_pool3d_grad_t, added in the intra graph's entry order (and a chain's order of arrival).
+ * The caller promises that no row of the intra graph lists a point twice (rows of the ball query do not): a pooled row is then
+ * met once per source. */
+int sph3d_max_pool3d_grad_rows(int B, int N, int M, int C, int F, const int* offsets, const int* ent_key, const int* first,
+                               const int* next, const int* nn_count, const int* max_index, const float* grad_output,
+                               const float* addend /* optional [B,N,C], as above */, float* grad_input, sph3d_stream_t stream);
 /* Non-finite values (C <= 128, C % 4 == 0): neighbours are taken in pairs and the last one of an odd count is read twice, the
  * second time with weight 0, so +-inf in that neighbour's row gives NaN (0 * inf) where the reference gives +-inf.  Only an
  * element that was non-finite anyway is affected. */

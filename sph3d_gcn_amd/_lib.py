@@ -59,6 +59,8 @@ SIGNATURES = {
     "sph3d_graph_canonical_order": (_I, [_I] * 5 + [_P] * 3 + [_P, _S, _P]),
     "sph3d_gather_nd": (_I, [_I, _I, ctypes.c_longlong, _I, _P, _P, _P, _P]),
     "sph3d_gather_rows_count": (_I, [_I] * 4 + [_P] * 5 + [_P, _S, _P]),
+    "sph3d_gather_rows_link": (_I, [_I] * 4 + [_P] * 7 + [_P]),
+    "sph3d_max_pool3d_grad_rows": (_I, [_I] * 5 + [_P] * 10),
     "sph3d_graph_transpose_workspace": (_S, [_I] * 5),
     "sph3d_graph_transpose": (_I, [_I] * 5 + [_P] * 8 + [_P, _S, _P]),
     "sph3d_graph_transpose_count": (_I, [_I] * 5 + [_P] * 3 + [_I, _P, _S, _P]),
@@ -232,7 +234,7 @@ def timing_stop():
 
 
 _PURE = ("_workspace", "_blocks", "_supported", "_parts", "_sample_chunk")
-_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_pieces", "_sample_chunk", "_plan")
+_NO_TIME = ("sph3d_abi_version", "sph3d_last_error", "sph3d_build_info", "sph3d_get_deterministic", "workspace", "_release_", "_blocks", "_supported", "_launches", "_parts", "_failures", "_mode", "_pieces", "_sample_chunk", "_plan")
 
 
 class _Proxy:

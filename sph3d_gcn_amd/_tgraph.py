@@ -15,7 +15,7 @@ from . import _lib
 
 BALANCE_MIN_POINTS = 1024   # binned graphs with at least this many source points get a degree-balanced gradient order
 PACK_ENTRIES = True     # (False: always separate key / scale arrays)
-_MAX_ENTRIES = 24      # one S3DIS step builds 16 (8 binned intra graphs, 4 un-pooling and 4 pooling graphs); entries pin ~150 MB each at level 0
+_MAX_ENTRIES = 24      # one S3DIS step builds 12 (8 binned intra graphs, 4 un-pooling graphs; deterministic and fuzzy plans: 4 pooling graphs more); entries pin ~150 MB each at level 0
 _cache = collections.OrderedDict()
 
 
@@ -98,6 +98,48 @@ def peek(nn_index, nn_count, n_src, need_unique_rows=False):
     if key not in _cache or (need_unique_rows and key not in _unique):
         return None
     return transpose(nn_index, nn_count, n_src)
+
+
+def cached(nn_index, nn_count, n_src, bin_index=None, num_bins=1):
+    """what transpose() with these arguments returns if that transpose is in the cache, else None (never builds)"""
+    F = int(num_bins) if bin_index is not None else 1
+    key = (_ident(nn_index), _ident(nn_count), _ident(bin_index), _ident(None), int(n_src), F, tuple(nn_index.shape))
+    if key not in _cache:
+        return None
+    return transpose(nn_index, nn_count, n_src, bin_index=bin_index, num_bins=num_bins)
+
+
+# ---- row link of a pooling graph (include/sph3d.h: sph3d_gather_rows_link) ----
+# A pooling graph whose rows are rows of the level's intra graph needs no transposed graph of its own: the max-pool gradient walks
+# the INTRA graph's transposed graph and this link (tf_pool3d).  The link hangs on the pooled nn_index tensor, as a transposed
+# graph's fast-path entry does, and names the intra graph's tensors: the gradient asks cached() for their transpose when it runs.
+def attach_row_link(pool_index, pool_count, first, next_, intra_index, intra_count, bin_index, num_bins):
+    """record (on the current stream, which has just written them) the link first [B, N] / next [B, S] of the pooling graph
+    (pool_index, pool_count) over the intra graph (intra_index, intra_count[, bin_index with num_bins bins])"""
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream())
+    pool_index._sph3d_rows = ((first, next_, intra_index, intra_count, bin_index, int(num_bins), ev, {_lib.current_raw_stream()}),
+                              pool_count, (_generation[0], pool_index._version, pool_count._version))
+
+
+def row_link(pool_index, pool_count):
+    """-> (first, next, transposed intra graph, F) when (pool_index, pool_count) carry a row link whose intra graph's transposed
+    graph is still cached, else None; orders the current stream behind the link's and the transpose's builders"""
+    hung = pool_index.__dict__.get("_sph3d_rows")
+    if hung is None or hung[1] is not pool_count or hung[2] != (_generation[0], pool_index._version, pool_count._version):
+        return None
+    first, next_, intra_index, intra_count, bin_index, num_bins, ev, synced = hung[0]
+    tg = cached(intra_index, intra_count, intra_index.shape[1], bin_index=bin_index, num_bins=num_bins)
+    if tg is None:
+        return None
+    cur_raw = _lib.current_raw_stream()
+    if cur_raw not in synced:
+        cur = torch.cuda.current_stream()
+        cur.wait_event(ev)
+        first.record_stream(cur)
+        next_.record_stream(cur)
+        synced.add(cur_raw)
+    return first, next_, tg, (num_bins if bin_index is not None else 1)
 
 
 def _attach(nn_index, fkey, hit, nn_count, bin_index, weight):

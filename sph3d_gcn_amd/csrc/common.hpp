@@ -143,6 +143,11 @@ static inline TgLayout tg_layout(void* workspace, int B, int N, int M, int K, in
 constexpr unsigned kTgKeyMask = 0x00ffffffu;
 static inline bool tg_packable(int M, int K, const void* weight) { return weight == nullptr && M <= (1 << 24) && K <= 255; }
 
+// ---- row link of a pooling graph (graph.hip: sph3d_gather_rows_link; pool3d.hip: sph3d_max_pool3d_grad_rows) ----
+// first[b, p] = 0 or (1 + pooled row that copies intra row p) | kRowLinkMore when further rows copy p (they follow in next[])
+constexpr unsigned kRowLinkMore = 0x80000000u;
+constexpr unsigned kRowLinkMask = 0x7fffffffu;
+
 // ---- the vote entry points (vote.hip, shapeeval.hip): what they all require of a batch and its row range; `what` heads the message
 constexpr int kVoteMaxClasses = 64;
 static inline int vote_check_args(const char* what, int B, int C, int num_blocks, long long total_rows, long long row_base,

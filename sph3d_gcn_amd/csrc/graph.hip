@@ -819,6 +819,60 @@ extern "C" int sph3d_gather_rows_count(int B, int N, int S, int K, const int* pa
     return check_launch("sph3d_gather_rows_count");
 }
 
+// The same copy with a ROW LINK instead of the counting pass: the in-edges of source n in the pooling graph are those in-edges
+// (p -> n) of the intra-level graph whose row p was sampled, so the max-pool gradient can walk the intra graph's transposed graph
+// (which the level's conv gradients build anyway) and needs of the pooling graph only "which pooled rows copy intra row p":
+//   first[ob, p] = 0 (p not sampled) or 1 + j, j the pooled row of cloud ob that copies p; bit 31 set when more rows copy it too,
+//   next[ob, j]  = 0 or 1 + the next pooled row that copies the same p (a sampler may return a point more than once).
+// One integer exchange per sampled ROW (the counting pass: one returning atomicAdd per EDGE), no scan, no fill, no entry array.
+// The order of a chain is the order of arrival.
+__global__ __launch_bounds__(256) void gather_rows_link_kernel(int B, int N, int S, int K, const int* __restrict__ pairs,
+                                                               const int* __restrict__ nnIndex, const int* __restrict__ nnCount,
+                                                               int* __restrict__ outIndex, int* __restrict__ outCount,
+                                                               int* __restrict__ first, int* __restrict__ next)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const long long rows = (long long)B * S;
+    for (long long s = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6); s < rows; s += (long long)gridDim.x * 4) {
+        int b = pairs[s * 2], p = pairs[s * 2 + 1];
+        b = b < 0 ? 0 : (b >= B ? B - 1 : b);              // out-of-range pairs are clamped (as sph3d_gather_nd)
+        p = p < 0 ? 0 : (p >= N ? N - 1 : p);
+        const int ob = (int)(s / S);                        // the cloud the OUTPUT row belongs to
+        const long long src = ((long long)b * N + p);
+        if (lane == 0) {
+            outCount[s] = nnCount[src];
+            int* head = &first[(size_t)ob * N + p];
+            const int old = atomicExch(head, (int)(s - (long long)ob * S) + 1);
+            next[s] = (int)((unsigned)old & kRowLinkMask);
+            // a second row of this p: flag whatever head stands there now (every later arrival flags again, so the last word
+            // carries the flag whatever the interleaving)
+            if (old != 0) atomicOr(head, (int)kRowLinkMore);
+        }
+        for (int k = lane; k < K; k += 64) outIndex[s * K + k] = nnIndex[src * K + k];
+    }
+}
+
+extern "C" int sph3d_gather_rows_link(int B, int N, int S, int K, const int* pairs, const int* nn_index, const int* nn_count,
+                                      int* out_index, int* out_count, int* first, int* next, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B > 0 && N > 0 && S >= 0 && K > 0, "gather_rows_link: bad dims B=%d N=%d S=%d K=%d", B, N, S, K);
+    SPH3D_REQUIRE((unsigned)S < kRowLinkMore - 1u, "gather_rows_link: S=%d rows per cloud do not fit the link word", S);
+    SPH3D_REQUIRE(first != nullptr && (next != nullptr || S == 0), "gather_rows_link: first [B, N] and next [B, S] are required");
+    if (deterministic_on()) {
+        set_error("gather_rows_link: deterministic mode is on and a chain of rows that copy one point is linked in arrival order; use "
+                  "sph3d_gather_rows_count and the pooling graph's own transposed graph");
+        return SPH3D_EUNSUPPORTED;
+    }
+    hipStream_t st = as_stream(stream);
+    int rc = zero_async(first, sizeof(int) * (size_t)B * N, st, "gather_rows_link: memset");
+    if (rc || S == 0) return rc;
+    long long blocks = ((long long)B * S + 3) / 4;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(gather_rows_link_kernel, dim3((unsigned)blocks), dim3(256), 0, st, B, N, S, K, pairs, nn_index, nn_count, out_index,
+                       out_count, first, next);
+    return check_launch("sph3d_gather_rows_link");
+}
+
 extern "C" int sph3d_graph_transpose(int B, int N, int M, int K, int F,
                                      const int* nn_index, const int* nn_count, const int* bin_index,
                                      const float* weight, int* offsets, int* ent_key, float* ent_scale, int* active_bins,

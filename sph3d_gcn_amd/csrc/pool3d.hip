@@ -322,6 +322,105 @@ __global__ __launch_bounds__(256) void maxpool_bwd_t(
     }
 }
 
+// The same gather WITHOUT a transposed pooling graph.  A level's pooling graph is the rows of its intra-level graph at the sampled
+// points, so the in-edges of source n in the pooling graph are those in-edges (p -> n) of the INTRA graph whose row p was
+// sampled: the wave walks n's entries of the intra graph's transposed graph (F segments per source, contiguous: graph.hip), 64 per
+// trip, looks every p up in the pooling graph's row link (graph.hip: gather_rows_link_kernel) and takes the pooled rows that copy
+// a sampled p — the same rows, hence the same row loads, as maxpool_bwd_t; about N / S times as many 4-byte entries.  The sampled
+// entries of a trip are moved to the wave's first lanes so that the row loop is a counted one and keeps four rows in flight.
+// Every intra row must list a point at most once (the caller's promise: rows of the ball query do).
+template <int V>
+__global__ __launch_bounds__(256) void maxpool_bwd_rows(
+    int B, int Nin, int Mout, int C, int F, int nblocks, int ppwg,
+    const int* __restrict__ offsets, const int* __restrict__ entKey, const int* __restrict__ first, const int* __restrict__ next,
+    const int* __restrict__ nnCount, const int* __restrict__ maxIndex, const float* __restrict__ gradOutput,
+    const float* __restrict__ addend, float* __restrict__ gradInput)
+{
+    int b, nb;
+    xcd_decode((int)blockIdx.x, B, nblocks, b, nb);
+    if (b < 0) return;
+    const int wave = uniform((int)threadIdx.x >> 6);
+    const int lane = lane_id();
+    const int n_begin = nb * ppwg;
+    const int n_end = (n_begin + ppwg) < Nin ? (n_begin + ppwg) : Nin;
+    const float* gob = gradOutput + (size_t)b * Mout * C;
+    const int* mib = maxIndex + (size_t)b * Mout * C;
+    const int* __restrict__ offb = offsets + (size_t)b * ((size_t)Nin * F + 1);
+    const int* __restrict__ firstb = first + (size_t)b * Nin;
+    const int* __restrict__ nextb = next + (size_t)b * Mout;
+    for (int n = n_begin + wave; n < n_end; n += 4) {
+        const int e0 = offb[(size_t)n * F], e1 = offb[(size_t)n * F + F];
+        for (int c0 = 0; c0 < C; c0 += 64 * V) {
+            const int c = c0 + lane * V;
+            const bool act = c < C;
+            const int cc = act ? c : 0;
+            float acc[V];
+#pragma unroll
+            for (int v = 0; v < V; v++) acc[v] = addend != nullptr ? addend[((size_t)b * Nin + n) * C + cc + v] : 0.f;
+            auto take = [&](int m) {       // branch-free: inactive lanes read channel 0
+                if (V == 4) {
+                    const int4 a = *reinterpret_cast<const int4*>(&mib[(size_t)m * C + cc]);
+                    const float4 g = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
+                    acc[0] += a.x == n ? g.x : 0.f;
+                    acc[1 % V] += a.y == n ? g.y : 0.f;
+                    acc[2 % V] += a.z == n ? g.z : 0.f;
+                    acc[3 % V] += a.w == n ? g.w : 0.f;
+                } else {
+                    acc[0] += mib[(size_t)m * C + cc] == n ? gob[(size_t)m * C + cc] : 0.f;
+                }
+            };
+            for (int ec = e0; ec < e1; ec += 64) {                     // wave-uniform trips
+                const int e = ec + lane;
+                int link = 0;
+                // (an entry word may be packed with the row's count above bit 24: common.hpp; rows are < 2^24 whenever it is)
+                if (e < e1) link = firstb[Nin <= (1 << 24) ? (int)((unsigned)entKey[e] & kTgKeyMask) : entKey[e]];
+                const unsigned long long hit = __ballot(link != 0);
+                if (hit == 0ull) continue;
+                const int hits = (int)__popcll(hit);
+                const int below = prefix_popc(hit);
+                // a permutation of the lanes: sampled entries first, in entry order
+                const int rows = __builtin_amdgcn_ds_permute((link != 0 ? below : hits + lane - below) << 2, link);
+                auto row = [&](int i) { return (int)((unsigned)__builtin_amdgcn_readlane(rows, i) & kRowLinkMask) - 1; };
+                int i = 0;
+                for (; i + 4 <= hits; i += 4) {        // (by hand: a loop with a cross-lane read is not unrolled with a remainder)
+                    const int r0 = row(i), r1 = row(i + 1), r2 = row(i + 2), r3 = row(i + 3);
+                    take(r0);
+                    take(r1);
+                    take(r2);
+                    take(r3);
+                }
+                for (; i < hits; i++) take(row(i));
+                unsigned long long more = __ballot(link < 0);          // points that were sampled more than once: their chains
+                while (more != 0ull) {
+                    const int bit = (int)__builtin_ctzll(more);
+                    more &= more - 1ull;
+                    int r = nextb[(int)((unsigned)__builtin_amdgcn_readlane(link, bit) & kRowLinkMask) - 1];
+                    while (r != 0) {
+                        take(r - 1);
+                        r = nextb[r - 1];
+                    }
+                }
+            }
+            if (n == 0) {                  // rows without neighbours: maxIndex 0 (see maxpool_bwd_t); 64 rows per trip
+                for (int m0 = 0; m0 < Mout; m0 += 64) {
+                    const int mm = m0 + lane;
+                    const int cnt = mm < Mout ? nnCount[(size_t)b * Mout + mm] : 1;
+                    unsigned long long empty = __ballot(cnt == 0);
+                    while (empty != 0ull) {
+                        const int bit = (int)__builtin_ctzll(empty);
+                        empty &= empty - 1ull;
+                        take(m0 + bit);
+                    }
+                }
+            }
+            if (act) {
+#pragma unroll
+                for (int v = 0; v < V; v++) gradInput[((size_t)b * Nin + n) * C + c + v] = acc[v];
+            }
+        }
+    }
+}
+
 // Few sources with many in-edges each (un-pooling: 2048 coarse points collect ~100 fine points each): one WORKGROUP per
 // source, its four waves take every fourth in-edge and the partial sums meet in LDS.  One wave per source (gather_bwd_t)
 // leaves such a launch with eight waves per SIMD in total and a 100-edge dependent chain per wave: 0.13 ms at the decoder's
@@ -607,6 +706,26 @@ extern "C" int sph3d_max_pool3d_grad_t(int B, int N, int M, int C, const int* of
         hipLaunchKernelGGL(maxpool_bwd_t<1>, grid, dim3(256), 0, st, B, N, M, C, nblocks, ppwg, offsets, ent_key, nn_count, max_index,
                            grad_output, addend, grad_input);
     return check_launch("sph3d_max_pool3d_grad_t");
+}
+
+extern "C" int sph3d_max_pool3d_grad_rows(int B, int N, int M, int C, int F, const int* offsets, const int* ent_key, const int* first,
+                                          const int* next, const int* nn_count, const int* max_index, const float* grad_output,
+                                          const float* addend, float* grad_input, sph3d_stream_t stream)
+{
+    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && C > 0 && F > 0, "MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d F=%d", B, N, M, C, F);
+    SPH3D_REQUIRE((long long)N * F < 0x7fffffffll, "MaxPool3dGrad: N=%d sources of F=%d segments exceed the offsets' index range", N, F);
+    if (B == 0) return SPH3D_OK;
+    hipStream_t st = as_stream(stream);
+    const int ppwg = (long long)B * N >= 65536 ? kPtsPerWG : 4;         // (the rule of sph3d_max_pool3d_grad_t)
+    const int nblocks = (N + ppwg - 1) / ppwg;
+    const dim3 grid(xcd_grid(B, nblocks));
+    if (C % 4 == 0)
+        hipLaunchKernelGGL(maxpool_bwd_rows<4>, grid, dim3(256), 0, st, B, N, M, C, F, nblocks, ppwg, offsets, ent_key, first, next, nn_count,
+                           max_index, grad_output, addend, grad_input);
+    else
+        hipLaunchKernelGGL(maxpool_bwd_rows<1>, grid, dim3(256), 0, st, B, N, M, C, F, nblocks, ppwg, offsets, ent_key, first, next, nn_count,
+                           max_index, grad_output, addend, grad_input);
+    return check_launch("sph3d_max_pool3d_grad_rows");
 }
 
 extern "C" int sph3d_avg_pool3d(int B, int N, int M, int C, int K, const int* nn_index, const int* nn_count,

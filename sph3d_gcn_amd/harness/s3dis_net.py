@@ -308,6 +308,17 @@ class GraphPlan:
     def _make_pool(self, l, g):
         fused = getattr(s3g_util, "gather_pooling_graph", None)        # (the oracle-backed CPU stand-ins of the tests have none)
         if fused is not None and g["intra_idx"].is_cuda:
+            from .. import _tgraph
+            # max pooling, training, arrival order: the pooling graph gets no transposed graph of its own — its gradient walks the
+            # intra graph's, which _pretranspose has just built for the conv gradients, through the row link this launch writes.
+            # (A fuzzy plan has the edge-id transpose instead, deterministic mode wants canonical pooling entries: both keep theirs.)
+            if (self.config.pool_method == 'max' and self.need_backward and not self._fuzzy and not _tgraph.is_deterministic()
+                    and hasattr(s3g_util, "gather_pooling_rows")
+                    and _tgraph.cached(g["intra_idx"], g["intra_cnt"], g["intra_idx"].shape[1], bin_index=g["filt_idx"],
+                                       num_bins=self.config.binSize) is not None):
+                g["inter_idx"], g["inter_cnt"] = s3g_util.gather_pooling_rows(g["intra_idx"], g["intra_cnt"], self.indices[l],
+                                                                              bin_index=g["filt_idx"], num_bins=self.config.binSize)
+                return
             # both gathers + (max pooling, training) the counting pass of the pooling graph's transpose in one launch
             g["inter_idx"], g["inter_cnt"] = fused(g["intra_idx"], g["intra_cnt"], self.indices[l],
                                                    with_transpose=self.config.pool_method == 'max' and self.need_backward)

@@ -283,6 +283,29 @@ def gather_pooling_graph(nn_index, nn_count, indices, with_transpose=True):
     return out_idx, out_cnt
 
 
+def gather_pooling_rows(nn_index, nn_count, indices, bin_index=None, num_bins=1):
+    """gather_pooling_graph's two tensors for a max-pool gradient that needs NO transposed pooling graph: the launch that copies the
+    rows also writes the pooling graph's row link (sph3d_gather_rows_link), attached to the returned nn_index (_tgraph.row_link);
+    tf_pool3d's gradient then walks the transposed INTRA graph — _tgraph.transpose(nn_index, nn_count, N[, bin_index, num_bins]),
+    which the caller has built or will build, and which must still be cached when the gradient runs.  For index pairs whose
+    cloud is the row's own (indices[b, :, 0] == b: what build_graph and the samplers return) and an intra graph whose rows list no
+    point twice (the ball query's); not in deterministic mode."""
+    from . import _tgraph
+    nn_index, nn_count, indices = nn_index.contiguous(), nn_count.contiguous(), indices.contiguous()
+    B, N, K = nn_index.shape
+    S = indices.shape[1]
+    dev = nn_index.device
+    out_idx = _lib.empty((B, S, K), torch.int32, dev)
+    out_cnt = _lib.empty((B, S), torch.int32, dev)
+    first = _lib.empty((B, N), torch.int32, dev)
+    nxt = _lib.empty((B, S), torch.int32, dev)
+    _lib.check(_lib.lib().sph3d_gather_rows_link(B, N, S, K, _lib.ptr(indices), _lib.ptr(nn_index), _lib.ptr(nn_count),
+                                                 _lib.ptr(out_idx), _lib.ptr(out_cnt), _lib.ptr(first), _lib.ptr(nxt),
+                                                 _lib.stream_ptr()))
+    _tgraph.attach_row_link(out_idx, out_cnt, first, nxt, nn_index, nn_count, bin_index, num_bins)
+    return out_idx, out_cnt
+
+
 # --------------------------------------------------------------------------------------
 # layers (utils/sph3gcn_util.py:88-273)
 # --------------------------------------------------------------------------------------

@@ -140,6 +140,37 @@ def _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg, addend=
     return grad_input
 
 
+def _max_pool3d_grad_rows_impl(input, grad_output, max_index, nn_count, link, addend=None):
+    """the same gradient without a transposed pooling graph: link = _tgraph.row_link(...) = (first, next, the transposed INTRA
+    graph, its bins per source) of a pooling graph made by sph3gcn_util.gather_pooling_rows (sph3d_max_pool3d_grad_rows)"""
+    first, nxt, tg, F = link
+    grad_output, max_index = _lib.f32(grad_output), _lib.i32(max_index)
+    addend = None if addend is None else _lib.f32(addend)
+    B, N, C = input.shape
+    M = grad_output.shape[1]
+    grad_input = torch.empty((B, N, C), dtype=torch.float32, device=input.device)
+    _lib.check(_lib.lib().sph3d_max_pool3d_grad_rows(B, N, M, C, F, _lib.ptr(tg[0]), _lib.ptr(tg[1]), _lib.ptr(first), _lib.ptr(nxt),
+                                                     _lib.ptr(nn_count), _lib.ptr(max_index), _lib.ptr(grad_output), _lib.ptr(addend),
+                                                     _lib.ptr(grad_input), _lib.stream_ptr()))
+    return grad_input
+
+
+def _gather_form(input, nn_index, nn_count):
+    """how the gradient can run as a gather -> ("t", transposed pooling graph) | ("rows", row link) | None.  In this order: a
+    transposed pooling graph someone built ahead of time WITH the promise that no row repeats a point; the row link of a pooling
+    graph made of intra-graph rows, while the intra graph's transposed graph is cached (sph3gcn_util.gather_pooling_rows: the
+    harness, on its graph stream)"""
+    if not (input.is_cuda and nn_index.dtype == torch.int32 and nn_count.dtype == torch.int32):
+        return None
+    tg = _tgraph.peek(nn_index, nn_count, input.shape[1], need_unique_rows=True)
+    if tg is not None:
+        return "t", tg
+    link = _tgraph.row_link(nn_index, nn_count)
+    if link is None or tuple(link[0].shape) != tuple(input.shape[:2]):         # (first [B, N]: the intra graph's points are the input's)
+        return None
+    return "rows", link
+
+
 def _no_scatter_when_deterministic():
     """deterministic mode: the max-pool gradient is the gather over a unique-rows transposed pooling graph or an error, never the
     scatter with its float atomics"""
@@ -161,14 +192,12 @@ class _MaxPool3dFn(torch.autograd.Function):      # eager fast path (see tf_conv
     @staticmethod
     def backward(ctx, grad_output, grad_index):
         input, max_index, nn_index, nn_count = ctx.saved_tensors
-        # a transposed pooling graph someone built ahead of time WITH the promise that no row repeats a point (the harness
-        # does, on its graph stream: rows of the ball query): gather, no atomics; otherwise the reference's scatter, which adds
-        # a point's gradient once however often a row lists it (tf_pool3d_gpu.cu:38-50)
-        tg = None
-        if input.is_cuda and nn_index.dtype == torch.int32 and nn_count.dtype == torch.int32:
-            tg = _tgraph.peek(nn_index, nn_count, input.shape[1], need_unique_rows=True)
-        if tg is not None:
-            return _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg), None, None
+        # a gather, no atomics, where _gather_form finds one (rows of the ball query: no row repeats a point); otherwise the
+        # reference's scatter, which adds a point's gradient once however often a row lists it (tf_pool3d_gpu.cu:38-50)
+        form = _gather_form(input, nn_index, nn_count)
+        if form is not None:
+            impl = _max_pool3d_grad_t_impl if form[0] == "t" else _max_pool3d_grad_rows_impl
+            return impl(input, grad_output, max_index, nn_count, form[1]), None, None
         _no_scatter_when_deterministic()
         return _max_pool3d_grad_impl(input, grad_output, max_index), None, None
 
@@ -204,14 +233,13 @@ class _MaxPool3dSkipFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output, grad_index, grad_skip):
         input, max_index, nn_index, nn_count = ctx.saved_tensors
-        tg = None
-        if input.is_cuda and nn_index.dtype == torch.int32 and nn_count.dtype == torch.int32:
-            tg = _tgraph.peek(nn_index, nn_count, input.shape[1], need_unique_rows=True)
         if grad_output is None:
             return grad_skip, None, None
-        if tg is not None:
+        form = _gather_form(input, nn_index, nn_count)
+        if form is not None:
             skip = grad_skip.contiguous() if grad_skip is not None else None
-            return _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg, addend=skip), None, None
+            impl = _max_pool3d_grad_t_impl if form[0] == "t" else _max_pool3d_grad_rows_impl
+            return impl(input, grad_output, max_index, nn_count, form[1], addend=skip), None, None
         _no_scatter_when_deterministic()
         g = _max_pool3d_grad_impl(input, grad_output, max_index)
         return (g if grad_skip is None else g + grad_skip), None, None

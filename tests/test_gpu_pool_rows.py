@@ -1,0 +1,297 @@
+"""The max-pool gradient without a transposed pooling graph (csrc/pool3d.hip: maxpool_bwd_rows; csrc/graph.hip:
+gather_rows_link_kernel): a pooling graph whose rows are rows of the level's intra graph is differentiated by walking the INTRA
+graph's transposed graph through the pooling graph's row link.
+
+Every case copies the sampled rows with sph3gcn_util.gather_pooling_rows, restates the link's structure on the host (every pooled
+row reachable exactly once from first / next), and holds sph3d_max_pool3d_grad_rows per element to the float64 scatter
+grad[b, arg[b, m, c], c] += go[b, m, c] (tests/_pool_ref.py) under assert_sum's bound — the one tests/test_gpu_pool_forms.py applies
+to sph3d_max_pool3d_grad_t: |got - ref| <= (terms + 3) * 2^-24 * mag — next to sph3d_max_pool3d_grad_t over a transposed pooling
+graph built the old way from the same rows.  The two kernels add the same terms in different orders (the old one in the pooling
+transpose's arrival order, the new one in the intra transpose's): elements of at most two terms must agree bit for bit.
+
+The shapes are the smallest that reach every path: N = 70 and 200 (no multiple of 64), K = 64 and 5 with a hub point that every
+non-empty row lists (its in-edges need several 64-entry trips), points no row lists, C = 3 / 4 / 260 (V = 1, V = 4, a second
+channel trip), S = 1 / 9 / N, points sampled two and three times, sampled rows without neighbours with and without point 0 among
+the samples, binned (F = 33) and un-binned intra transposes, packed and plain entries, with and without the skip addend."""
+import numpy as np
+import pytest
+import torch
+
+from _pool_ref import assert_sum, bits, make_graph, make_values, max_grad_ref, max_ref
+from sph3d_gcn_amd import _lib, _tgraph, tf_pool3d
+from sph3d_gcn_amd import sph3gcn_util as s3g_util
+from sph3d_gcn_amd.harness import s3dis_net, synth
+
+pytestmark = pytest.mark.gpu
+
+P, S_ = _lib.ptr, _lib.stream_ptr
+F_BINS = 33
+LINK_MORE, LINK_MASK = 0x80000000, 0x7fffffff          # csrc/common.hpp: kRowLinkMore, kRowLinkMask
+
+
+@pytest.fixture(autouse=True)
+def _fresh_transposes():
+    _tgraph.clear()
+    yield
+    _tgraph.clear()
+
+
+def _t(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _n(t):
+    return t.detach().cpu().numpy()
+
+
+# ---- inputs -------------------------------------------------------------------------------------------------------------------
+def _samples(rng, B, N, S, dups):
+    """sel [B, S]: distinct points per cloud, never point 0 in even clouds (so cloud 0's rows without neighbours are collected
+    by a source that is not sampled), point 0 last in odd clouds; dups: sel[1] = sel[0] and sel[4] = sel[3] = sel[2].  S = N
+    samples every point (without dups)."""
+    sel = np.zeros((B, S), np.int32)
+    for b in range(B):
+        if S == N:
+            sel[b] = rng.permutation(N)
+        else:
+            sel[b] = 1 + rng.permutation(N - 1)[:S]
+            if b % 2 == 1 and S > 1:
+                sel[b, -1] = 0
+        if dups:
+            sel[b, 1] = sel[b, 0]
+            sel[b, 4] = sel[b, 3] = sel[b, 2]
+    return sel
+
+
+def _intra_graph(rng, B, N, K, sel):
+    """an intra graph of N points: ascending ids without repeats per row, counts 1..K and one row of 0, point 1 (the hub) in every
+    non-empty row, the last two points in no row.  S > 1: the rows of sel[b, 0] and sel[b, -2] have no neighbours; S = 1: the one
+    sampled row of the odd clouds has none"""
+    cnt = rng.randint(1, K + 1, size=(B, N)).astype(np.int32)
+    cnt[:, rng.permutation(N)[:5]] = np.array([0, 1, 2, K - 1, K], np.int32)
+    for b in range(B):
+        if sel.shape[1] > 1:
+            cnt[b, sel[b, 0]] = cnt[b, sel[b, -2]] = 0
+        else:
+            cnt[b, sel[b, 0]] = 0 if b % 2 == 1 else K
+    idx = np.zeros((B, N, K), np.int32)
+    others = np.array([i for i in range(N - 2) if i != 1])
+    for b in range(B):
+        for p in range(N):
+            c = int(cnt[b, p])
+            if c:
+                idx[b, p, :c] = np.sort(np.concatenate(([1], rng.permutation(others)[:c - 1])))
+    return idx, cnt
+
+
+def _in_degree(idx, cnt, N):
+    live = np.arange(idx.shape[2])[None, None, :] < cnt[:, :, None]
+    return np.stack([np.bincount(idx[b][live[b]], minlength=N) for b in range(idx.shape[0])])
+
+
+def _check_link(first, nxt, sel, N):
+    """every pooled row is reachable exactly once from first / next, through the point it copies; first is 0 exactly at the points
+    that were not sampled and carries the flag exactly where a point was sampled more than once"""
+    B, S = sel.shape
+    assert first.shape == (B, N) and nxt.shape == (B, S)
+    for b in range(B):
+        seen = np.zeros(S, np.int64)
+        for p in range(N):
+            word = int(first[b, p]) & 0xffffffff
+            mult = int((sel[b] == p).sum())
+            assert (word == 0) == (mult == 0), (b, p, word, mult)
+            assert bool(word & LINK_MORE) == (mult > 1), (b, p, hex(word), mult)
+            r, steps = word & LINK_MASK, 0
+            while r != 0:
+                assert 1 <= r <= S and sel[b, r - 1] == p and steps < S, (b, p, r)
+                seen[r - 1] += 1
+                r, steps = int(nxt[b, r - 1]), steps + 1
+            assert steps == mult
+        assert (seen == 1).all(), (b, seen)
+
+
+SAMPLE_CASES = [("S1", 1, False), ("S9", 9, False), ("S9-dups", 9, True), ("SN", None, False), ("SN-dups", None, True)]
+
+
+@pytest.mark.parametrize("packed", [True, False], ids=["packed", "plain"])
+@pytest.mark.parametrize("binned", [True, False], ids=["F33", "F1"])
+@pytest.mark.parametrize("sample", SAMPLE_CASES, ids=[s[0] for s in SAMPLE_CASES])
+@pytest.mark.parametrize("N,K", [(70, 64), (200, 5)], ids=["N70-K64", "N200-K5"])
+@pytest.mark.parametrize("B", [1, 3])
+def test_gradient_over_the_intra_transpose(dev, monkeypatch, B, N, K, sample, binned, packed):
+    monkeypatch.setattr(_tgraph, "PACK_ENTRIES", packed)
+    S = N if sample[1] is None else sample[1]
+    rng = np.random.RandomState(1000 * B + N + S + 7 * binned + 3 * packed + sample[2])
+    sel = _samples(rng, B, N, S, sample[2])
+    idx, cnt = _intra_graph(rng, B, N, K, sel)
+    deg = _in_degree(idx, cnt, N)
+    assert deg.max() > 64 and (deg == 0).any(axis=1).all()          # several entry trips; sources without an in-edge
+    assert (sel[0] != 0).all() or S == N                              # cloud 0: point 0 is not sampled
+    pool_idx = np.stack([idx[b, sel[b]] for b in range(B)])
+    pool_cnt = np.stack([cnt[b, sel[b]] for b in range(B)])
+    # sampled rows without neighbours: in every cloud, or (S = 1) as the odd clouds' only row — B = 1: the one row has neighbours
+    assert ((pool_cnt == 0).any(axis=1) == [S > 1 or b % 2 == 1 for b in range(B)]).all()
+    pairs = np.stack([np.broadcast_to(np.arange(B, dtype=np.int32)[:, None], sel.shape), sel], axis=2)
+
+    it, ct = _t(idx, dev), _t(cnt, dev)
+    bt = _t(rng.randint(0, F_BINS, size=idx.shape).astype(np.int32), dev) if binned else None
+    tg = _tgraph.transpose(it, ct, N, bin_index=bt, num_bins=F_BINS)
+    assert (tg[2] is None) == packed
+    oi, oc = s3g_util.gather_pooling_rows(it, ct, _t(pairs, dev), bin_index=bt, num_bins=F_BINS)
+    np.testing.assert_array_equal(_n(oi), pool_idx)
+    np.testing.assert_array_equal(_n(oc), pool_cnt)
+    link = _tgraph.row_link(oi, oc)
+    assert link is not None and link[2] is tg and link[3] == (F_BINS if binned else 1)
+    first, nxt = link[0], link[1]
+    _check_link(_n(first), _n(nxt), sel, N)
+    assert _tgraph.peek(oi, oc, N, need_unique_rows=True) is None     # no transposed pooling graph was made
+    old = _tgraph.transpose(oi, oc, N, unique_rows=True)              # ... until here: the old way, from the same rows
+
+    l = _lib.lib()
+    for C in (3, 4, 260):
+        x, go = make_values(rng, (B, N, C)), make_values(rng, (B, S, C))
+        arg = max_ref(x, pool_idx, pool_cnt)[1]
+        mit, got = _t(arg, dev), _t(go, dev)
+        for with_addend in (False, True):
+            ref, mag, terms = max_grad_ref(go, arg, N)
+            add = at = None
+            if with_addend:
+                add = make_values(rng, (B, N, C))
+                at = _t(add, dev)
+                ref, mag, terms = ref + add, mag + np.abs(add), terms + 1
+            new_t = torch.full((B, N, C), float("nan"), dtype=torch.float32, device=dev)
+            old_t = torch.full((B, N, C), float("nan"), dtype=torch.float32, device=dev)
+            _lib.check(l.sph3d_max_pool3d_grad_rows(B, N, S, C, link[3], P(tg[0]), P(tg[1]), P(first), P(nxt), P(oc), P(mit), P(got),
+                                                    P(at), P(new_t), S_()))
+            _lib.check(l.sph3d_max_pool3d_grad_t(B, N, S, C, P(old[0]), P(old[1]), P(oc), P(mit), P(got), P(at), P(old_t), S_()))
+            what = "B%d N%d K%d %s %s %s C=%d%s" % (B, N, K, sample[0], "F33" if binned else "F1", "packed" if packed else "plain", C,
+                                                     " + addend" if with_addend else "")
+            new, was = _n(new_t), _n(old_t)
+            assert_sum(new, ref, mag, terms, "rows " + what)
+            assert_sum(was, ref, mag, terms, "grad_t " + what)
+            few = terms <= 2                   # one or two terms: a float sum that no order changes
+            np.testing.assert_array_equal(bits(new)[few], bits(was)[few], err_msg=what)
+            print("%s: %d of %d elements differ in bits from sph3d_max_pool3d_grad_t" % (what, int((bits(new) != bits(was)).sum()), new.size))
+
+
+@pytest.mark.parametrize("C", [8, 3])
+def test_sixteen_points_per_workgroup(dev, C):
+    """B * N >= 65536: sixteen sources per workgroup, so a wave walks four sources one after the other (the shape of
+    tests/test_gpu_pool_forms.py: test_max_gradient_gather_sixteen_points_per_workgroup), the last workgroup ragged"""
+    B, N, K, S = 2, 32771, 8, 200
+    assert B * N >= 65536 and N % 16 != 0
+    rng = np.random.RandomState(43 + C)
+    idx, cnt = make_graph(rng, B, N, N, K)                            # the intra graph: N rows over N points, ascending ids
+    sel = np.stack([rng.permutation(N)[:S] for _ in range(B)]).astype(np.int32)
+    sel[:, 1] = sel[:, 0]                                             # one point sampled twice
+    sel[:, 2:S // 2] = np.sort(sel[:, 2:S // 2] % 64, axis=1)        # many samples (with repeats) among the first sources
+    pool_idx = np.stack([idx[b, sel[b]] for b in range(B)])
+    pool_cnt = np.stack([cnt[b, sel[b]] for b in range(B)])
+    pairs = np.stack([np.broadcast_to(np.arange(B, dtype=np.int32)[:, None], sel.shape), sel], axis=2)
+    it, ct = _t(idx, dev), _t(cnt, dev)
+    tg = _tgraph.transpose(it, ct, N)
+    oi, oc = s3g_util.gather_pooling_rows(it, ct, _t(pairs, dev))
+    np.testing.assert_array_equal(_n(oi), pool_idx)
+    first, nxt, tg_link, F = _tgraph.row_link(oi, oc)
+    assert tg_link is tg and F == 1
+    _check_link(_n(first), _n(nxt), sel, N)
+    x, go, add = make_values(rng, (B, N, C)), make_values(rng, (B, S, C)), make_values(rng, (B, N, C))
+    arg = max_ref(x, pool_idx, pool_cnt)[1]
+    ref, mag, terms = max_grad_ref(go, arg, N)
+    got = torch.full((B, N, C), float("nan"), dtype=torch.float32, device=dev)
+    mit, got_t, at = _t(arg, dev), _t(go, dev), _t(add, dev)
+    _lib.check(_lib.lib().sph3d_max_pool3d_grad_rows(B, N, S, C, 1, P(tg[0]), P(tg[1]), P(first), P(nxt), P(oc), P(mit), P(got_t), P(at),
+                                                     P(got), S_()))
+    assert_sum(_n(got), ref + add, mag + np.abs(add), terms + 1, "rows ppwg 16 C=%d + addend" % C)
+
+
+def test_link_refuses_deterministic_mode(dev):
+    idx, cnt = torch.zeros((1, 8, 4), dtype=torch.int32, device=dev), torch.zeros((1, 8), dtype=torch.int32, device=dev)
+    pairs = torch.zeros((1, 2, 2), dtype=torch.int32, device=dev)
+    with _tgraph.deterministic(True):
+        with pytest.raises(_lib.Sph3dError, match="deterministic"):
+            s3g_util.gather_pooling_rows(idx, cnt, pairs)
+
+
+# ---- routing: which pooling graphs a plan makes and which kernel its backward pass runs ---------------------------------------
+def _train_step_calls(dev, fuzzy=False):
+    """one training step of the reduced S3DIS plan -> (the plan, the names of the backward pass's library calls)"""
+    xyz, label, inner = synth.s3dis_batch(0, 2, 1024, extent=(1.0, 1.0, 1.5))
+    pts = _t(xyz, dev)
+    cfg = s3dis_net.small_config(1024)
+    if fuzzy:
+        cfg.kernel_fuzzy = True
+    model = s3dis_net.SPH3DS3DIS(cfg, device=dev)
+    plan = s3dis_net.build_graphs(pts, model.config)
+    pred, _ = model(pts, is_training=True, graphs=plan)
+    loss = model.loss(pred, _t(label, dev), _t(inner, dev))
+    _lib.timing_start()
+    try:
+        loss.backward()
+    finally:
+        names = [c[0] for c in _lib.timing_stop()]
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in model.parameters() if p.requires_grad)
+    return plan, cfg, names
+
+
+def _pool_levels(plan, cfg):
+    return [(plan.pool(l), plan.xyz_layers[l].shape[1]) for l in range(len(cfg.radius)) if cfg.num_sample[l] > 1]
+
+
+def test_plan_for_backward_takes_the_row_link(dev):
+    plan, cfg, names = _train_step_calls(dev)
+    levels = _pool_levels(plan, cfg)
+    assert levels
+    for g, n in levels:
+        assert _tgraph.row_link(g["inter_idx"], g["inter_cnt"]) is not None
+        assert _tgraph.peek(g["inter_idx"], g["inter_cnt"], n) is None            # no transposed pooling graph is cached
+    assert names.count("sph3d_max_pool3d_grad_rows") == len(levels)
+    assert "sph3d_max_pool3d_grad_t" not in names and "sph3d_max_pool3d_grad" not in names
+
+
+def test_deterministic_plan_keeps_the_transposed_pooling_graph(dev):
+    with _tgraph.deterministic(True):
+        plan, cfg, names = _train_step_calls(dev)
+        levels = _pool_levels(plan, cfg)
+        for g, n in levels:
+            assert _tgraph.row_link(g["inter_idx"], g["inter_cnt"]) is None
+            assert _tgraph.peek(g["inter_idx"], g["inter_cnt"], n, need_unique_rows=True) is not None
+        assert names.count("sph3d_max_pool3d_grad_t") == len(levels) and "sph3d_max_pool3d_grad_rows" not in names
+
+
+def test_fuzzy_plan_keeps_the_transposed_pooling_graph(dev):
+    plan, cfg, names = _train_step_calls(dev, fuzzy=True)
+    levels = _pool_levels(plan, cfg)
+    for g, n in levels:
+        assert _tgraph.row_link(g["inter_idx"], g["inter_cnt"]) is None
+        assert _tgraph.peek(g["inter_idx"], g["inter_cnt"], n, need_unique_rows=True) is not None
+    assert names.count("sph3d_max_pool3d_grad_t") == len(levels) and "sph3d_max_pool3d_grad_rows" not in names
+
+
+def test_backward_falls_back_when_the_intra_transpose_is_gone(dev):
+    """a link whose intra graph's transposed graph is no longer cached is not used: the gradient does what it did without one"""
+    rng = np.random.RandomState(5)
+    B, N, K, S, C = 2, 70, 5, 9, 4
+    sel = _samples(rng, B, N, S, False)
+    idx, cnt = _intra_graph(rng, B, N, K, sel)
+    pairs = np.stack([np.broadcast_to(np.arange(B, dtype=np.int32)[:, None], sel.shape), sel], axis=2)
+    it, ct = _t(idx, dev), _t(cnt, dev)
+    _tgraph.transpose(it, ct, N)
+    oi, oc = s3g_util.gather_pooling_rows(it, ct, _t(pairs, dev))
+    x, go = make_values(rng, (B, N, C)), make_values(rng, (B, S, C))
+    grads = []
+    for drop in (False, True):
+        if drop:
+            _tgraph._cache.clear()
+            assert _tgraph.row_link(oi, oc) is None
+        xin = _t(x, dev).requires_grad_(True)
+        out, mi = tf_pool3d.max_pool3d(xin, oi, oc)
+        _lib.timing_start()
+        try:
+            out.backward(_t(go, dev))
+        finally:
+            names = [c[0] for c in _lib.timing_stop()]
+        assert ("sph3d_max_pool3d_grad" if drop else "sph3d_max_pool3d_grad_rows") in names
+        grads.append(_n(xin.grad))
+        ref = max_grad_ref(go, _n(mi), N)
+        assert_sum(grads[-1], *ref, "autograd, %s" % ("scatter" if drop else "rows"))
