@@ -474,6 +474,50 @@ int sph3d_interpolate_narrow_grad_t(int B, int Nin, int Mout, int C,
                                     const int* offsets, const int* ent_key, const float* ent_scale,
                                     const float* grad_output, float* grad_input, sph3d_stream_t stream);
 
+/* sph3d_pool3d_plan: what an entry of the pooling and un-pooling sections launches for a call (csrc/pool_plan.hpp: pool_plan, which
+ * every entry launches from), answered on the host; no device is touched.  Nin: the points gathered FROM (forward) or the gradient's
+ * rows; Mout: the rows of the neighbour graph — so for the un-pooling entries Nin = M (coarse) and Mout = N (fine).  K is read by the
+ * forward ops, F by _MAX_GRAD_ROWS.  op:
+ *   SPH3D_POOL_FWD            sph3d_max_pool3d, _avg_pool3d, _mean_interpolate, _weighted_interpolate (one rule for the three modes)
+ *   SPH3D_POOL_SUM_GRAD_T     sph3d_scatter_grad_t and the three *_grad wrappers behind their transpose
+ *   SPH3D_POOL_MAX_GRAD       sph3d_max_pool3d_grad (the scatter; its refusal in deterministic mode is the entry's, not the plan's)
+ *   SPH3D_POOL_MAX_GRAD_T     sph3d_max_pool3d_grad_t            SPH3D_POOL_MAX_GRAD_ROWS   sph3d_max_pool3d_grad_rows
+ *   SPH3D_POOL_NARROW         sph3d_interpolate_narrow           SPH3D_POOL_NARROW_GRAD_T   sph3d_interpolate_narrow_grad_t
+ * out[SPH3D_POOL_PLAN_FIELDS], in this order:
+ *     0 kernel: SPH3D_POOL_KERNEL_NONE (nothing is launched: B == 0; forward: Mout == 0; _MAX_GRAD: Mout == 0, grad_input is only
+ *     cleared), _FWD_HALF gather_fwd_half (C % 4 == 0, C <= 128), _FWD gather_fwd, _BWD_T gather_bwd_t, _BWD_T_SPLIT
+ *     gather_bwd_t_split (B Nin <= 65536 and Mout >= 2 Nin), _MAX_BWD maxpool_bwd, _MAX_BWD_T, _MAX_BWD_ROWS, _NARROW_FWD, _NARROW_BWD_T
+ *     1 V: channels per lane of the instantiation, 4 (C % 4 == 0) or 1; 0 for maxpool_bwd and the narrow kernels
+ *     2 pairs: the two halves of a wave take alternate rows (gather_fwd_half; the split gather at V == 4, C <= 128)
+ *     3 passes of a wave over a row's channels, ceil(C / (64 V))   4 ppwg: points per workgroup — 16 from 65536 points (B Mout
+ *     forward, B Nin in the max gradients), else 4; gather_bwd_t 16; the split gather 1; narrow 16 rows, 4 sources
+ *     5 parts: workgroups' worth of points per cloud, ceil(points / ppwg) (maxpool_bwd: grid.x; narrow: 0)
+ *     6 grid.x (the gathers: parts of B clouds dealt to the 8 XCDs; narrow: min(ceil(rows / ppwg), 65536))   7 grid.y (maxpool_bwd: B)
+ *     8 block (256)   9 static LDS bytes (the split gather: 4 * 64 V * 4)   10 zero_bytes: bytes of grad_input maxpool_bwd's entry
+ *     clears first   11 blocks_wanted = ceil(Mout C / 256), 12 blocks_cap = max(ceil(8192 / B), 1): maxpool_bwd's grid.x is their minimum
+ * -> SPH3D_OK, or SPH3D_EINVAL for an op that is none of the above, then the entry's own status and message in the entry's order —
+ * bad dimensions, N F >= 2^31 - 1 (_MAX_GRAD_ROWS), B > 65535 (_MAX_GRAD), C > 16 (narrow: SPH3D_EUNSUPPORTED), a grid.x beyond
+ * 2^31 - 1 (from B Mout = 2 147 483 641: 2^31 - 7 clouds of one point) — then SPH3D_EINVAL for out == NULL. */
+#define SPH3D_POOL_FWD 0
+#define SPH3D_POOL_SUM_GRAD_T 1
+#define SPH3D_POOL_MAX_GRAD 2
+#define SPH3D_POOL_MAX_GRAD_T 3
+#define SPH3D_POOL_MAX_GRAD_ROWS 4
+#define SPH3D_POOL_NARROW 5
+#define SPH3D_POOL_NARROW_GRAD_T 6
+#define SPH3D_POOL_KERNEL_NONE 0
+#define SPH3D_POOL_KERNEL_FWD_HALF 1
+#define SPH3D_POOL_KERNEL_FWD 2
+#define SPH3D_POOL_KERNEL_BWD_T 3
+#define SPH3D_POOL_KERNEL_BWD_T_SPLIT 4
+#define SPH3D_POOL_KERNEL_MAX_BWD 5
+#define SPH3D_POOL_KERNEL_MAX_BWD_T 6
+#define SPH3D_POOL_KERNEL_MAX_BWD_ROWS 7
+#define SPH3D_POOL_KERNEL_NARROW_FWD 8
+#define SPH3D_POOL_KERNEL_NARROW_BWD_T 9
+#define SPH3D_POOL_PLAN_FIELDS 13
+int sph3d_pool3d_plan(int op, int B, int Nin, int Mout, int C, int K, int F, long long* out);
+
 /* ---- sampling -----------------------------------------------------------
  * replaces farthestPointSampleLauncher (tf_ops/sampling/tf_sample_gpu.cu:77-80;
  * kernel farthestpointsampleKernel :7-73; op FarthestPointSample tf_sample.cpp:30-58).

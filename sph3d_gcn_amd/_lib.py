@@ -89,6 +89,7 @@ SIGNATURES = {
     "sph3d_interpolate_narrow_supported": (_I, [_I]),
     "sph3d_interpolate_narrow": (_I, [_I] * 5 + [_P] * 7),
     "sph3d_interpolate_narrow_grad_t": (_I, [_I] * 4 + [_P] * 6),
+    "sph3d_pool3d_plan": (_I, [_I] * 7 + [_P]),
     "sph3d_farthest_point_sample_workspace": (_S, [_I] * 3),
     "sph3d_farthest_point_sample": (_I, [_I] * 3 + [_P, _P, _P, _S, _P]),
     "sph3d_farthest_point_sample_plan": (_I, [_I] * 3 + [_P]),

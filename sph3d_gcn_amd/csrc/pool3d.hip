@@ -10,13 +10,18 @@
 // The reference used one thread per (point, channel) with a global read-modify-write per neighbour
 // and a cudaDeviceSynchronize after every launch (tf_pool3d_gpu.cu:97,104,111,118).
 // Un-pooling "mean" is avg-pooling with the roles of the point sets swapped, so it reuses that kernel.
-// avg / mean / weighted gradients gather over the transposed graph (graph.hip); only the max-pool gradient
-// (one element per output, data-dependent target) still uses hardware fp32 atomics.
+// avg / mean / weighted gradients gather over the transposed graph (graph.hip).  The max-pool gradient (one element per output,
+// data-dependent target) has three forms: a gather over the transposed pooling graph (maxpool_bwd_t), the same gather over the
+// level's intra transpose through a row link (maxpool_bwd_rows) — both write every element once, in a fixed order — and the
+// reference's scatter (maxpool_bwd), the one kernel of the file that adds with hardware fp32 atomics: it serves callers without
+// a transposed graph and is refused in deterministic mode.
+// Which kernel a call launches, and at which shape, is decided in pool_plan.hpp (pool_plan) and nowhere else.
+#include <stddef.h>
+#include <string.h>
 #include "common.hpp"
+#include "pool_plan.hpp"
 
 namespace sph3d {
-
-constexpr int kPtsPerWG = 16;   // 4 waves x 4 points: the launches with many points; small ones take 4 (pts_per_wg)
 
 enum class Mode { Max, Avg, Weighted };
 
@@ -183,6 +188,21 @@ __global__ __launch_bounds__(256) void gather_fwd_half(
 // scale = 1/nn_count[m] (avg / mean) or weight[b,m,k] (weighted).  One wave per source point n, each
 // gradInput element written exactly once: no atomics, no memset (the reference: atomicAdd per
 // (point, neighbour, channel), tf_pool3d_gpu.cu:86, tf_unpool3d_gpu.cu:38,80).
+// acc[0 .. V) += row[0 .. V) * sc
+template <int V>
+__device__ __forceinline__ void fma_row(float (&acc)[V], const float* __restrict__ row, float sc)
+{
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(row);
+        acc[0] = fmaf(t.x, sc, acc[0]);
+        acc[1] = fmaf(t.y, sc, acc[1]);
+        acc[2] = fmaf(t.z, sc, acc[2]);
+        acc[3] = fmaf(t.w, sc, acc[3]);
+    } else {
+        acc[0] = fmaf(row[0], sc, acc[0]);
+    }
+}
+
 template <int V>
 __global__ __launch_bounds__(256) void gather_bwd_t(
     int B, int Nin, int Mout, int C, int nblocks,
@@ -212,17 +232,7 @@ __global__ __launch_bounds__(256) void gather_bwd_t(
                 const int wk = entKey[e];
                 const int m = tg_key(wk, entScale == nullptr);          // (packed entries: common.hpp)
                 const float sc = entScale == nullptr ? tg_packed_scale(wk) : entScale[e];
-                {   // branch-free: inactive lanes read channel 0
-                    if (V == 4) {
-                        const float4 t = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
-                        acc[0] = fmaf(t.x, sc, acc[0]);
-                        acc[1 % V] = fmaf(t.y, sc, acc[1 % V]);
-                        acc[2 % V] = fmaf(t.z, sc, acc[2 % V]);
-                        acc[3 % V] = fmaf(t.w, sc, acc[3 % V]);
-                    } else {
-                        acc[0] = fmaf(gob[(size_t)m * C + cc], sc, acc[0]);
-                    }
-                }
+                fma_row<V>(acc, &gob[(size_t)m * C + cc], sc);          // branch-free: inactive lanes read channel 0
             }
             if (act) {
 #pragma unroll
@@ -259,6 +269,51 @@ __global__ __launch_bounds__(256) void maxpool_bwd(
 // atomics (the scatter above: 4.2 M single-lane atomics at S3DIS level 0, 151 us; 47-83 us on the small levels), and the sum
 // of the (few) terms of an element has a fixed order.  Rows m WITHOUT neighbours keep maxIndex 0 in the forward pass and the
 // scatter adds their gradient to point 0; they have no edge here, so the wave of point 0 looks for them in nn_count.
+// What both gathers do for source n of cloud b at channels c .. c + V: seed the sums, hand `walk` the function take(m) that adds
+// row m's gradient where its arg-max is n, collect the rows without neighbours (n == 0), store.  mib, gob: the cloud's rows.
+template <int V, class Walk>
+__device__ __forceinline__ void maxpool_bwd_source(
+    int b, int n, int c, int lane, int Nin, int Mout, int C, const int* mib, const float* gob, const int* __restrict__ nnCount,
+    const float* __restrict__ addend, float* __restrict__ gradInput, Walk walk)
+{
+    const bool act = c < C;
+    const int cc = act ? c : 0;
+    // addend (optional, [B, Nin, C]): a second gradient of the same tensor — the pooled tensor's other consumer, the
+    // encoder's skip connection — summed here instead of by a separate elementwise kernel over three tensors
+    float acc[V];
+#pragma unroll
+    for (int v = 0; v < V; v++) acc[v] = addend != nullptr ? addend[((size_t)b * Nin + n) * C + cc + v] : 0.f;
+    auto take = [&](int m) {       // branch-free: inactive lanes read channel 0
+        if constexpr (V == 4) {
+            const int4 a = *reinterpret_cast<const int4*>(&mib[(size_t)m * C + cc]);
+            const float4 g = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
+            acc[0] += a.x == n ? g.x : 0.f;
+            acc[1] += a.y == n ? g.y : 0.f;
+            acc[2] += a.z == n ? g.z : 0.f;
+            acc[3] += a.w == n ? g.w : 0.f;
+        } else {
+            acc[0] += mib[(size_t)m * C + cc] == n ? gob[(size_t)m * C + cc] : 0.f;
+        }
+    };
+    walk(take);
+    if (n == 0) {                  // rows without neighbours: maxIndex 0 (see maxpool_bwd_t); 64 rows per trip
+        for (int m0 = 0; m0 < Mout; m0 += 64) {
+            const int mm = m0 + lane;
+            const int cnt = mm < Mout ? nnCount[(size_t)b * Mout + mm] : 1;
+            unsigned long long empty = __ballot(cnt == 0);
+            while (empty != 0ull) {
+                const int bit = (int)__builtin_ctzll(empty);
+                empty &= empty - 1ull;
+                take(m0 + bit);
+            }
+        }
+    }
+    if (act) {
+#pragma unroll
+        for (int v = 0; v < V; v++) gradInput[((size_t)b * Nin + n) * C + c + v] = acc[v];
+    }
+}
+
 template <int V>
 __global__ __launch_bounds__(256) void maxpool_bwd_t(
     int B, int Nin, int Mout, int C, int nblocks, int ppwg,
@@ -279,45 +334,11 @@ __global__ __launch_bounds__(256) void maxpool_bwd_t(
     for (int n = n_begin + wave; n < n_end; n += 4) {
         const int e0 = offb[n], e1 = offb[n + 1];
         for (int c0 = 0; c0 < C; c0 += 64 * V) {
-            const int c = c0 + lane * V;
-            const bool act = c < C;
-            const int cc = act ? c : 0;
-            // addend (optional, [B, Nin, C]): a second gradient of the same tensor — the pooled tensor's other consumer, the
-            // encoder's skip connection — summed here instead of by a separate elementwise kernel over three tensors
-            float acc[V];
-#pragma unroll
-            for (int v = 0; v < V; v++) acc[v] = addend != nullptr ? addend[((size_t)b * Nin + n) * C + cc + v] : 0.f;
-            auto take = [&](int m) {       // branch-free: inactive lanes read channel 0
-                if (V == 4) {
-                    const int4 a = *reinterpret_cast<const int4*>(&mib[(size_t)m * C + cc]);
-                    const float4 g = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
-                    acc[0] += a.x == n ? g.x : 0.f;
-                    acc[1 % V] += a.y == n ? g.y : 0.f;
-                    acc[2 % V] += a.z == n ? g.z : 0.f;
-                    acc[3 % V] += a.w == n ? g.w : 0.f;
-                } else {
-                    acc[0] += mib[(size_t)m * C + cc] == n ? gob[(size_t)m * C + cc] : 0.f;
-                }
-            };
+            maxpool_bwd_source<V>(b, n, c0 + lane * V, lane, Nin, Mout, C, mib, gob, nnCount, addend, gradInput, [&](auto take) {
 #pragma unroll 4
-            // (an entry word may be packed with the row's count above bit 24: common.hpp; rows are < 2^24 whenever it is)
-            for (int e = e0; e < e1; e++) take(Mout <= (1 << 24) ? (int)((unsigned)entKey[e] & kTgKeyMask) : entKey[e]);
-            if (n == 0) {                  // rows without neighbours: maxIndex 0 (see above); 64 rows per trip
-                for (int m0 = 0; m0 < Mout; m0 += 64) {
-                    const int mm = m0 + lane;
-                    const int cnt = mm < Mout ? nnCount[(size_t)b * Mout + mm] : 1;
-                    unsigned long long empty = __ballot(cnt == 0);
-                    while (empty != 0ull) {
-                        const int bit = (int)__builtin_ctzll(empty);
-                        empty &= empty - 1ull;
-                        take(m0 + bit);
-                    }
-                }
-            }
-            if (act) {
-#pragma unroll
-                for (int v = 0; v < V; v++) gradInput[((size_t)b * Nin + n) * C + c + v] = acc[v];
-            }
+                // (an entry word may be packed with the row's count above bit 24: common.hpp; rows are < 2^24 whenever it is)
+                for (int e = e0; e < e1; e++) take(Mout <= (1 << 24) ? (int)((unsigned)entKey[e] & kTgKeyMask) : entKey[e]);
+            });
         }
     }
 }
@@ -351,72 +372,40 @@ __global__ __launch_bounds__(256) void maxpool_bwd_rows(
     for (int n = n_begin + wave; n < n_end; n += 4) {
         const int e0 = offb[(size_t)n * F], e1 = offb[(size_t)n * F + F];
         for (int c0 = 0; c0 < C; c0 += 64 * V) {
-            const int c = c0 + lane * V;
-            const bool act = c < C;
-            const int cc = act ? c : 0;
-            float acc[V];
-#pragma unroll
-            for (int v = 0; v < V; v++) acc[v] = addend != nullptr ? addend[((size_t)b * Nin + n) * C + cc + v] : 0.f;
-            auto take = [&](int m) {       // branch-free: inactive lanes read channel 0
-                if (V == 4) {
-                    const int4 a = *reinterpret_cast<const int4*>(&mib[(size_t)m * C + cc]);
-                    const float4 g = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
-                    acc[0] += a.x == n ? g.x : 0.f;
-                    acc[1 % V] += a.y == n ? g.y : 0.f;
-                    acc[2 % V] += a.z == n ? g.z : 0.f;
-                    acc[3 % V] += a.w == n ? g.w : 0.f;
-                } else {
-                    acc[0] += mib[(size_t)m * C + cc] == n ? gob[(size_t)m * C + cc] : 0.f;
-                }
-            };
-            for (int ec = e0; ec < e1; ec += 64) {                     // wave-uniform trips
-                const int e = ec + lane;
-                int link = 0;
-                // (an entry word may be packed with the row's count above bit 24: common.hpp; rows are < 2^24 whenever it is)
-                if (e < e1) link = firstb[Nin <= (1 << 24) ? (int)((unsigned)entKey[e] & kTgKeyMask) : entKey[e]];
-                const unsigned long long hit = __ballot(link != 0);
-                if (hit == 0ull) continue;
-                const int hits = (int)__popcll(hit);
-                const int below = prefix_popc(hit);
-                // a permutation of the lanes: sampled entries first, in entry order
-                const int rows = __builtin_amdgcn_ds_permute((link != 0 ? below : hits + lane - below) << 2, link);
-                auto row = [&](int i) { return (int)((unsigned)__builtin_amdgcn_readlane(rows, i) & kRowLinkMask) - 1; };
-                int i = 0;
-                for (; i + 4 <= hits; i += 4) {        // (by hand: a loop with a cross-lane read is not unrolled with a remainder)
-                    const int r0 = row(i), r1 = row(i + 1), r2 = row(i + 2), r3 = row(i + 3);
-                    take(r0);
-                    take(r1);
-                    take(r2);
-                    take(r3);
-                }
-                for (; i < hits; i++) take(row(i));
-                unsigned long long more = __ballot(link < 0);          // points that were sampled more than once: their chains
-                while (more != 0ull) {
-                    const int bit = (int)__builtin_ctzll(more);
-                    more &= more - 1ull;
-                    int r = nextb[(int)((unsigned)__builtin_amdgcn_readlane(link, bit) & kRowLinkMask) - 1];
-                    while (r != 0) {
-                        take(r - 1);
-                        r = nextb[r - 1];
+            maxpool_bwd_source<V>(b, n, c0 + lane * V, lane, Nin, Mout, C, mib, gob, nnCount, addend, gradInput, [&](auto take) {
+                for (int ec = e0; ec < e1; ec += 64) {                     // wave-uniform trips
+                    const int e = ec + lane;
+                    int link = 0;
+                    // (an entry word may be packed with the row's count above bit 24: common.hpp; rows are < 2^24 whenever it is)
+                    if (e < e1) link = firstb[Nin <= (1 << 24) ? (int)((unsigned)entKey[e] & kTgKeyMask) : entKey[e]];
+                    const unsigned long long hit = __ballot(link != 0);
+                    if (hit == 0ull) continue;
+                    const int hits = (int)__popcll(hit);
+                    const int below = prefix_popc(hit);
+                    // a permutation of the lanes: sampled entries first, in entry order
+                    const int rows = __builtin_amdgcn_ds_permute((link != 0 ? below : hits + lane - below) << 2, link);
+                    auto row = [&](int i) { return (int)((unsigned)__builtin_amdgcn_readlane(rows, i) & kRowLinkMask) - 1; };
+                    int i = 0;
+                    for (; i + 4 <= hits; i += 4) {        // (by hand: a loop with a cross-lane read is not unrolled with a remainder)
+                        const int r0 = row(i), r1 = row(i + 1), r2 = row(i + 2), r3 = row(i + 3);
+                        take(r0);
+                        take(r1);
+                        take(r2);
+                        take(r3);
+                    }
+                    for (; i < hits; i++) take(row(i));
+                    unsigned long long more = __ballot(link < 0);          // points that were sampled more than once: their chains
+                    while (more != 0ull) {
+                        const int bit = (int)__builtin_ctzll(more);
+                        more &= more - 1ull;
+                        int r = nextb[(int)((unsigned)__builtin_amdgcn_readlane(link, bit) & kRowLinkMask) - 1];
+                        while (r != 0) {
+                            take(r - 1);
+                            r = nextb[r - 1];
+                        }
                     }
                 }
-            }
-            if (n == 0) {                  // rows without neighbours: maxIndex 0 (see maxpool_bwd_t); 64 rows per trip
-                for (int m0 = 0; m0 < Mout; m0 += 64) {
-                    const int mm = m0 + lane;
-                    const int cnt = mm < Mout ? nnCount[(size_t)b * Mout + mm] : 1;
-                    unsigned long long empty = __ballot(cnt == 0);
-                    while (empty != 0ull) {
-                        const int bit = (int)__builtin_ctzll(empty);
-                        empty &= empty - 1ull;
-                        take(m0 + bit);
-                    }
-                }
-            }
-            if (act) {
-#pragma unroll
-                for (int v = 0; v < V; v++) gradInput[((size_t)b * Nin + n) * C + c + v] = acc[v];
-            }
+            });
         }
     }
 }
@@ -463,11 +452,7 @@ __global__ __launch_bounds__(256) void gather_bwd_t_split(
                 const float s0 = pk ? tg_packed_scale(w0) : entScale[e], s1 = two ? (pk ? tg_packed_scale(w1) : entScale[e + 1]) : 0.f;
                 const int m = half ? m1 : m0;
                 const float sc = half ? s1 : s0;
-                const float4 t = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cch]);
-                acc[0] = fmaf(t.x, sc, acc[0]);
-                acc[1 % V] = fmaf(t.y, sc, acc[1 % V]);
-                acc[2 % V] = fmaf(t.z, sc, acc[2 % V]);
-                acc[3 % V] = fmaf(t.w, sc, acc[3 % V]);
+                fma_row<V>(acc, &gob[(size_t)m * C + cch], sc);
             }
 #pragma unroll
             for (int v = 0; v < V; v++) acc[v] += __shfl_xor(acc[v], 32);       // lanes 0..31 now hold channels 4*lane..
@@ -477,15 +462,7 @@ __global__ __launch_bounds__(256) void gather_bwd_t_split(
             const int wk = entKey[e];
             const int m = tg_key(wk, entScale == nullptr);
             const float sc = entScale == nullptr ? tg_packed_scale(wk) : entScale[e];
-            if (V == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(&gob[(size_t)m * C + cc]);
-                acc[0] = fmaf(t.x, sc, acc[0]);
-                acc[1 % V] = fmaf(t.y, sc, acc[1 % V]);
-                acc[2 % V] = fmaf(t.z, sc, acc[2 % V]);
-                acc[3 % V] = fmaf(t.w, sc, acc[3 % V]);
-            } else {
-                acc[0] = fmaf(gob[(size_t)m * C + cc], sc, acc[0]);
-            }
+            fma_row<V>(acc, &gob[(size_t)m * C + cc], sc);
         }
         if (c0 > 0) __syncthreads();              // the previous pass's sums have been read
 #pragma unroll
@@ -600,30 +577,45 @@ __global__ __launch_bounds__(256) void narrow_interp_bwd_t(
     }
 }
 
+// ---- the host side: every entry computes its plan (pool_plan.hpp), answers what the plan refuses, and launches what it says ----
+
+// The status and message of a call the plan refuses: the entries and the plan query answer alike
+static int pool_refusal(const PoolPlan& p, const char* who, int op, int B, int Nin, int Mout, int C, int K, int F)
+{
+    if (p.bad == kPoolBadDims) {
+        if (op == kPoolOpFwd) set_error("%s: bad dims B=%d N=%d M=%d C=%d K=%d", who, B, Nin, Mout, C, K);
+        else if (op == kPoolOpSumGradT) set_error("%s: bad dims B=%d N=%d M=%d C=%d", who, B, Nin, Mout, C);
+        else if (op == kPoolOpMaxGradRows) set_error("MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d F=%d", B, Nin, Mout, C, F);
+        else if (op == kPoolOpNarrow) set_error("interpolate_narrow: bad dims B=%d N=%d M=%d C=%d K=%d", B, Mout, Nin, C, K);
+        else if (op == kPoolOpNarrowGradT) set_error("interpolate_narrow_grad_t: bad dims B=%d N=%d M=%d C=%d", B, Nin, Mout, C);
+        else set_error("MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d", B, Nin, Mout, C);
+        return SPH3D_EINVAL;
+    }
+    SPH3D_REQUIRE(p.bad != kPoolBadSegments, "MaxPool3dGrad: N=%d sources of F=%d segments exceed the offsets' index range", Nin, F);
+    SPH3D_REQUIRE(p.bad != kPoolBadBatch, "MaxPool3dGrad: batch %d exceeds the grid's second dimension", B);
+    if (p.bad == kPoolWide) {
+        set_error("%s: rows of at most 16 channels (got C=%d)", op == kPoolOpNarrow ? "interpolate_narrow" : "interpolate_narrow_grad_t", C);
+        return SPH3D_EUNSUPPORTED;
+    }
+    SPH3D_REQUIRE(p.bad != kPoolBadGrid, "%s: B=%d N=%d M=%d need more than 2^31 - 1 workgroups", who, B, Nin, Mout);
+    return SPH3D_OK;
+}
+
 template <Mode MODE>
 static int launch_fwd(const char* who, int B, int Nin, int Mout, int C, int K,
                       const int* nn_index, const int* nn_count, const float* input, const float* weight,
                       float* output, int* max_index, hipStream_t st)
 {
-    SPH3D_REQUIRE(B >= 0 && Nin > 0 && Mout >= 0 && C > 0 && K > 0, "%s: bad dims B=%d N=%d M=%d C=%d K=%d",
-                  who, B, Nin, Mout, C, K);
-    if (B == 0 || Mout == 0) return SPH3D_OK;
-    // Output points per workgroup: these kernels have no per-workgroup prologue, so the small levels (a few thousand output
-    // points) take ONE point per wave — four per wave left them with 2-8 waves per SIMD walking 4 x ~50 dependent gathers each
-    // (round 3, tools/exp_calls.py: max pooling 36 -> 17 us at 16 x 128 points of 512 channels, 80 -> 64 us at level 0);
-    // launches of >= 65536 points keep four per wave (mean interpolation at level 0: 80 vs 82 us).
-    const int ppwg = (long long)B * Mout >= 65536 ? kPtsPerWG : 4;
-    const int mblocks = (Mout + ppwg - 1) / ppwg;
-    const dim3 grid(xcd_grid(B, mblocks));
-    if (C % 4 == 0 && C <= 128)
-        hipLaunchKernelGGL((gather_fwd_half<MODE>), grid, dim3(256), 0, st, B, Nin, Mout, C, K, mblocks,
-                           nn_index, nn_count, input, weight, output, max_index, ppwg);
-    else if (C % 4 == 0)
-        hipLaunchKernelGGL((gather_fwd<MODE, 4>), grid, dim3(256), 0, st, B, Nin, Mout, C, K, mblocks,
-                           nn_index, nn_count, input, weight, output, max_index, ppwg);
-    else
-        hipLaunchKernelGGL((gather_fwd<MODE, 1>), grid, dim3(256), 0, st, B, Nin, Mout, C, K, mblocks,
-                           nn_index, nn_count, input, weight, output, max_index, ppwg);
+    const PoolPlan p = pool_plan(kPoolOpFwd, B, Nin, Mout, C, K, 0);
+    int rc = pool_refusal(p, who, kPoolOpFwd, B, Nin, Mout, C, K, 0);
+    if (rc || p.kernel == kPoolNone) return rc;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, st, B, Nin, Mout, C, K, (int)p.parts,
+                           nn_index, nn_count, input, weight, output, max_index, (int)p.ppwg);
+    };
+    if (p.kernel == kPoolFwdHalf) go(gather_fwd_half<MODE>);
+    else if (p.V == 4) go(gather_fwd<MODE, 4>);
+    else go(gather_fwd<MODE, 1>);
     return check_launch(who);
 }
 
@@ -631,33 +623,52 @@ static int launch_bwd_t(const char* who, int B, int Nin, int Mout, int C,
                         const int* offsets, const int* ent_key, const float* ent_scale,
                         const float* grad_output, float* grad_input, hipStream_t st)
 {
-    SPH3D_REQUIRE(B >= 0 && Nin > 0 && Mout >= 0 && C > 0, "%s: bad dims B=%d N=%d M=%d C=%d", who, B, Nin, Mout, C);
-    if (B == 0) return SPH3D_OK;
-    const int nblocks = (Nin + kPtsPerWG - 1) / kPtsPerWG;
-    const dim3 grid(xcd_grid(B, nblocks));
-    // few sources, each with (Mout / Nin) x more in-edges than a target has neighbours: one workgroup per source
-    if ((long long)B * Nin <= 65536 && Mout >= 2 * Nin) {
-        const dim3 sgrid((unsigned)((long long)B * Nin));
-        if (C % 4 == 0)
-            hipLaunchKernelGGL(gather_bwd_t_split<4>, sgrid, dim3(256), 0, st, B, Nin, Mout, C, offsets, ent_key, ent_scale,
-                               grad_output, grad_input);
-        else
-            hipLaunchKernelGGL(gather_bwd_t_split<1>, sgrid, dim3(256), 0, st, B, Nin, Mout, C, offsets, ent_key, ent_scale,
-                               grad_output, grad_input);
-        return check_launch(who);
+    const PoolPlan p = pool_plan(kPoolOpSumGradT, B, Nin, Mout, C, 0, 0);
+    int rc = pool_refusal(p, who, kPoolOpSumGradT, B, Nin, Mout, C, 0, 0);
+    if (rc || p.kernel == kPoolNone) return rc;
+    const dim3 grid((unsigned)p.grid), block((unsigned)p.block);
+    if (p.kernel == kPoolBwdTSplit) {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, B, Nin, Mout, C, offsets, ent_key, ent_scale, grad_output, grad_input);
+        };
+        if (p.V == 4) go(gather_bwd_t_split<4>);
+        else go(gather_bwd_t_split<1>);
+    } else {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, st, B, Nin, Mout, C, (int)p.parts, offsets, ent_key, ent_scale, grad_output,
+                               grad_input);
+        };
+        if (p.V == 4) go(gather_bwd_t<4>);
+        else go(gather_bwd_t<1>);
     }
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(gather_bwd_t<4>, grid, dim3(256), 0, st, B, Nin, Mout, C, nblocks, offsets, ent_key,
-                           ent_scale, grad_output, grad_input);
-    else
-        hipLaunchKernelGGL(gather_bwd_t<1>, grid, dim3(256), 0, st, B, Nin, Mout, C, nblocks, offsets, ent_key,
-                           ent_scale, grad_output, grad_input);
     return check_launch(who);
 }
 
 }  // namespace sph3d
 
 using namespace sph3d;
+
+extern "C" int sph3d_pool3d_plan(int op, int B, int Nin, int Mout, int C, int K, int F, long long* out)
+{
+    const PoolPlan p = pool_plan(op, B, Nin, Mout, C, K, F);
+    SPH3D_REQUIRE(p.bad != kPoolBadOp, "sph3d_pool3d_plan: op %d is none of SPH3D_POOL_FWD .. SPH3D_POOL_NARROW_GRAD_T", op);
+    int rc = pool_refusal(p, "sph3d_pool3d_plan", op, B, Nin, Mout, C, K, F);
+    if (rc) return rc;
+    SPH3D_REQUIRE(out != nullptr, "sph3d_pool3d_plan: out is NULL");
+    static_assert(offsetof(PoolPlan, bad) == SPH3D_POOL_PLAN_FIELDS * sizeof(long long), "the plan starts with the documented fields, in their order");
+    static_assert(kPoolOpFwd == SPH3D_POOL_FWD && kPoolOpSumGradT == SPH3D_POOL_SUM_GRAD_T && kPoolOpMaxGrad == SPH3D_POOL_MAX_GRAD &&
+                      kPoolOpMaxGradT == SPH3D_POOL_MAX_GRAD_T && kPoolOpMaxGradRows == SPH3D_POOL_MAX_GRAD_ROWS &&
+                      kPoolOpNarrow == SPH3D_POOL_NARROW && kPoolOpNarrowGradT == SPH3D_POOL_NARROW_GRAD_T,
+                  "the ops as the header numbers them");
+    static_assert(kPoolNone == SPH3D_POOL_KERNEL_NONE && kPoolFwdHalf == SPH3D_POOL_KERNEL_FWD_HALF && kPoolFwd == SPH3D_POOL_KERNEL_FWD &&
+                      kPoolBwdT == SPH3D_POOL_KERNEL_BWD_T && kPoolBwdTSplit == SPH3D_POOL_KERNEL_BWD_T_SPLIT &&
+                      kPoolMaxBwd == SPH3D_POOL_KERNEL_MAX_BWD && kPoolMaxBwdT == SPH3D_POOL_KERNEL_MAX_BWD_T &&
+                      kPoolMaxBwdRows == SPH3D_POOL_KERNEL_MAX_BWD_ROWS && kPoolNarrowFwd == SPH3D_POOL_KERNEL_NARROW_FWD &&
+                      kPoolNarrowBwdT == SPH3D_POOL_KERNEL_NARROW_BWD_T,
+                  "the kernels as the header numbers them");
+    memcpy(out, &p, SPH3D_POOL_PLAN_FIELDS * sizeof(long long));
+    return SPH3D_OK;
+}
 
 extern "C" int sph3d_max_pool3d(int B, int N, int M, int C, int K, const int* nn_index, const int* nn_count,
                                 const float* input, float* output, int* max_index, sph3d_stream_t stream)
@@ -669,23 +680,19 @@ extern "C" int sph3d_max_pool3d(int B, int N, int M, int C, int K, const int* nn
 extern "C" int sph3d_max_pool3d_grad(int B, int N, int M, int C, const int* max_index, const float* grad_output,
                                      float* grad_input, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && C > 0, "MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d", B, N, M, C);
-    if (deterministic_on()) {
+    const PoolPlan p = pool_plan(kPoolOpMaxGrad, B, N, M, C, 0, 0);
+    if (p.bad != kPoolBadDims && deterministic_on()) {
         set_error("MaxPool3dGrad: deterministic mode is on and the scatter form adds with float atomics; use sph3d_max_pool3d_grad_t "
                   "on the transposed pooling graph");
         return SPH3D_EUNSUPPORTED;
     }
-    if (B == 0) return SPH3D_OK;
+    int rc = pool_refusal(p, "sph3d_max_pool3d_grad", kPoolOpMaxGrad, B, N, M, C, 0, 0);
+    if (rc || p.zero_bytes == 0) return rc;
     hipStream_t st = as_stream(stream);
-    int rc = zero_async(grad_input, sizeof(float) * (size_t)B * N * C, st, "sph3d_max_pool3d_grad");
-    if (rc) return rc;
-    const long long per_b = (long long)M * C;
-    if (per_b == 0) return SPH3D_OK;
-    SPH3D_REQUIRE(B <= 65535, "MaxPool3dGrad: batch %d exceeds the grid's second dimension", B);
-    long long blocks = (per_b + 255) / 256;
-    const long long cap = (8192 + B - 1) / B > 1 ? (8192 + B - 1) / B : 1;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(maxpool_bwd, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, B, N, M, C, max_index, grad_output, grad_input);
+    rc = zero_async(grad_input, (size_t)p.zero_bytes, st, "sph3d_max_pool3d_grad");
+    if (rc || p.kernel == kPoolNone) return rc;
+    hipLaunchKernelGGL(maxpool_bwd, dim3((unsigned)p.grid, (unsigned)p.grid_y), dim3((unsigned)p.block), 0, st, B, N, M, C, max_index,
+                       grad_output, grad_input);
     return check_launch("sph3d_max_pool3d_grad");
 }
 
@@ -693,18 +700,15 @@ extern "C" int sph3d_max_pool3d_grad_t(int B, int N, int M, int C, const int* of
                                        const int* max_index, const float* grad_output, const float* addend, float* grad_input,
                                        sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && C > 0, "MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d", B, N, M, C);
-    if (B == 0) return SPH3D_OK;
-    hipStream_t st = as_stream(stream);
-    const int ppwg = (long long)B * N >= 65536 ? kPtsPerWG : 4;
-    const int nblocks = (N + ppwg - 1) / ppwg;
-    const dim3 grid(xcd_grid(B, nblocks));
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(maxpool_bwd_t<4>, grid, dim3(256), 0, st, B, N, M, C, nblocks, ppwg, offsets, ent_key, nn_count, max_index,
-                           grad_output, addend, grad_input);
-    else
-        hipLaunchKernelGGL(maxpool_bwd_t<1>, grid, dim3(256), 0, st, B, N, M, C, nblocks, ppwg, offsets, ent_key, nn_count, max_index,
-                           grad_output, addend, grad_input);
+    const PoolPlan p = pool_plan(kPoolOpMaxGradT, B, N, M, C, 0, 0);
+    int rc = pool_refusal(p, "sph3d_max_pool3d_grad_t", kPoolOpMaxGradT, B, N, M, C, 0, 0);
+    if (rc || p.kernel == kPoolNone) return rc;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, as_stream(stream), B, N, M, C, (int)p.parts,
+                           (int)p.ppwg, offsets, ent_key, nn_count, max_index, grad_output, addend, grad_input);
+    };
+    if (p.V == 4) go(maxpool_bwd_t<4>);
+    else go(maxpool_bwd_t<1>);
     return check_launch("sph3d_max_pool3d_grad_t");
 }
 
@@ -712,19 +716,15 @@ extern "C" int sph3d_max_pool3d_grad_rows(int B, int N, int M, int C, int F, con
                                           const int* next, const int* nn_count, const int* max_index, const float* grad_output,
                                           const float* addend, float* grad_input, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N > 0 && M >= 0 && C > 0 && F > 0, "MaxPool3dGrad: bad dims B=%d N=%d M=%d C=%d F=%d", B, N, M, C, F);
-    SPH3D_REQUIRE((long long)N * F < 0x7fffffffll, "MaxPool3dGrad: N=%d sources of F=%d segments exceed the offsets' index range", N, F);
-    if (B == 0) return SPH3D_OK;
-    hipStream_t st = as_stream(stream);
-    const int ppwg = (long long)B * N >= 65536 ? kPtsPerWG : 4;         // (the rule of sph3d_max_pool3d_grad_t)
-    const int nblocks = (N + ppwg - 1) / ppwg;
-    const dim3 grid(xcd_grid(B, nblocks));
-    if (C % 4 == 0)
-        hipLaunchKernelGGL(maxpool_bwd_rows<4>, grid, dim3(256), 0, st, B, N, M, C, F, nblocks, ppwg, offsets, ent_key, first, next, nn_count,
-                           max_index, grad_output, addend, grad_input);
-    else
-        hipLaunchKernelGGL(maxpool_bwd_rows<1>, grid, dim3(256), 0, st, B, N, M, C, F, nblocks, ppwg, offsets, ent_key, first, next, nn_count,
-                           max_index, grad_output, addend, grad_input);
+    const PoolPlan p = pool_plan(kPoolOpMaxGradRows, B, N, M, C, 0, F);
+    int rc = pool_refusal(p, "sph3d_max_pool3d_grad_rows", kPoolOpMaxGradRows, B, N, M, C, 0, F);
+    if (rc || p.kernel == kPoolNone) return rc;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, as_stream(stream), B, N, M, C, F, (int)p.parts,
+                           (int)p.ppwg, offsets, ent_key, first, next, nn_count, max_index, grad_output, addend, grad_input);
+    };
+    if (p.V == 4) go(maxpool_bwd_rows<4>);
+    else go(maxpool_bwd_rows<1>);
     return check_launch("sph3d_max_pool3d_grad_rows");
 }
 
@@ -736,7 +736,6 @@ extern "C" int sph3d_avg_pool3d(int B, int N, int M, int C, int K, const int* nn
 }
 
 // ---- gradients: transposed-graph entry point + the reference-surface wrappers that build the transpose ----
-
 
 // grad_input[B,Nin,C] = gather over in-edges of grad_output[B,Mout,C] * scale
 extern "C" int sph3d_scatter_grad_t(int B, int Nin, int Mout, int C, const int* offsets, const int* ent_key,
@@ -799,29 +798,22 @@ extern "C" int sph3d_weighted_interpolate(int B, int N, int M, int C, int K, con
                                       output, nullptr, as_stream(stream));
 }
 
-// ---- interpolation of narrow (projected) rows, C <= 16 ----
-extern "C" int sph3d_interpolate_narrow_supported(int C) { return (C >= 1 && C <= 16) ? 1 : 0; }
+// ---- interpolation of narrow (projected) rows ----
+extern "C" int sph3d_interpolate_narrow_supported(int C) { return (C >= 1 && C <= kPoolNarrowMaxC) ? 1 : 0; }
 
 extern "C" int sph3d_interpolate_narrow(int B, int N, int M, int C, int K, const int* nn_index, const int* nn_count,
                                         const float* input, const float* weight, const float* base, float* output,
                                         sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && N >= 0 && M > 0 && C > 0 && K > 0, "interpolate_narrow: bad dims B=%d N=%d M=%d C=%d K=%d", B, N, M, C, K);
-    if (C > 16) {
-        set_error("interpolate_narrow: rows of at most 16 channels (got C=%d)", C);
-        return SPH3D_EUNSUPPORTED;
-    }
-    const long long rows = (long long)B * N;
-    if (rows == 0) return SPH3D_OK;
-    long long wgs = (rows + 15) / 16;
-    if (wgs > 65536) wgs = 65536;
-    hipStream_t st = as_stream(stream);
-    if (weight != nullptr)
-        hipLaunchKernelGGL(narrow_interp_fwd<true>, dim3((unsigned)wgs), dim3(256), 0, st, rows, N, M, C, K, nn_index, nn_count, input,
-                           weight, base, output);
-    else
-        hipLaunchKernelGGL(narrow_interp_fwd<false>, dim3((unsigned)wgs), dim3(256), 0, st, rows, N, M, C, K, nn_index, nn_count, input,
-                           weight, base, output);
+    const PoolPlan p = pool_plan(kPoolOpNarrow, B, /*Nin=*/M, /*Mout=*/N, C, K, 0);
+    int rc = pool_refusal(p, "sph3d_interpolate_narrow", kPoolOpNarrow, B, M, N, C, K, 0);
+    if (rc || p.kernel == kPoolNone) return rc;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, as_stream(stream), (long long)B * N, N, M, C, K,
+                           nn_index, nn_count, input, weight, base, output);
+    };
+    if (weight != nullptr) go(narrow_interp_fwd<true>);
+    else go(narrow_interp_fwd<false>);
     return check_launch("sph3d_interpolate_narrow");
 }
 
@@ -829,17 +821,11 @@ extern "C" int sph3d_interpolate_narrow_grad_t(int B, int Nin, int Mout, int C, 
                                                const float* ent_scale, const float* grad_output, float* grad_input,
                                                sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(B >= 0 && Nin > 0 && Mout >= 0 && C > 0, "interpolate_narrow_grad_t: bad dims B=%d N=%d M=%d C=%d", B, Nin, Mout, C);
-    if (C > 16) {
-        set_error("interpolate_narrow_grad_t: rows of at most 16 channels (got C=%d)", C);
-        return SPH3D_EUNSUPPORTED;
-    }
-    if (B == 0) return SPH3D_OK;
-    const long long sources = (long long)B * Nin;
-    long long wgs = (sources + 3) / 4;
-    if (wgs > 65536) wgs = 65536;
-    hipLaunchKernelGGL(narrow_interp_bwd_t, dim3((unsigned)wgs), dim3(256), 0, as_stream(stream), sources, Nin, Mout, C, offsets,
-                       ent_key, ent_scale, grad_output, grad_input);
+    const PoolPlan p = pool_plan(kPoolOpNarrowGradT, B, Nin, Mout, C, 0, 0);
+    int rc = pool_refusal(p, "sph3d_interpolate_narrow_grad_t", kPoolOpNarrowGradT, B, Nin, Mout, C, 0, 0);
+    if (rc || p.kernel == kPoolNone) return rc;
+    hipLaunchKernelGGL(narrow_interp_bwd_t, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, as_stream(stream), (long long)B * Nin, Nin,
+                       Mout, C, offsets, ent_key, ent_scale, grad_output, grad_input);
     return check_launch("sph3d_interpolate_narrow_grad_t");
 }
 
@@ -851,3 +837,4 @@ extern "C" int sph3d_weighted_interpolate_grad(int B, int N, int M, int C, int K
     return grad_via_transpose("sph3d_weighted_interpolate_grad", B, M, N, C, K, nn_index, nn_count, weight, grad_output,
                               grad_input, workspace, workspace_bytes, stream);
 }
+

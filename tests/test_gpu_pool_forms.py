@@ -1,42 +1,23 @@
 """Pooling and un-pooling (csrc/pool3d.hip) per element against float64 (tests/_pool_ref.py), at every launch form.
 
-The launchers pick a kernel form from the dimensions alone; every case here restates the rule that selects its form as an
-assertion (the _*_form functions are the launchers' rules, copied), calls the C ABI on outputs pre-filled with NaN (ids: -1) —
-the gradient kernels promise "each element written exactly once, no memset" — and compares max-pool values and ids bit for bit
-with the reference's scan and every sum under |got - ref| <= (terms + 3) * 2^-24 * mag (assert_sum, which prints the used
-fraction of that bound: DESIGN.md §2 quotes the maxima per form)."""
+The launchers pick a kernel form from the dimensions alone (csrc/pool_plan.hpp); every case here asserts the form it is there
+for, read from the library's own query (tests/_pool_forms.py: the *_form functions ask sph3d_pool3d_plan; tests/test_pool_forms.py
+holds that query to the rules restated in Python, and the cases listed in plan_cases() below to the full set of kernels), calls
+the C ABI on outputs pre-filled with NaN (ids: -1) — the gradient kernels promise "each element written exactly once, no memset" —
+and compares max-pool values and ids bit for bit with the reference's scan and every sum under
+|got - ref| <= (terms + 3) * 2^-24 * mag (assert_sum, which prints the used fraction of that bound: DESIGN.md §2 quotes the
+maxima per form)."""
 import numpy as np
 import pytest
 import torch
 
+import _pool_forms as PF
+from _pool_forms import bwd_t_form as _bwd_t_form, fwd_form as _fwd_form, max_t_form as _max_t_form, scatter_blocks as _scatter_blocks
 from _pool_ref import (U, assert_sum, bits, gather_ref, make_graph, make_values, make_weights, max_grad_ref, max_ref,
                        scatter_ref)
 from sph3d_gcn_amd import _lib, _tgraph, tf_pool3d
 
 pytestmark = pytest.mark.gpu
-
-
-# ---- the launchers' rules (pool3d.hip: launch_fwd, launch_bwd_t, sph3d_max_pool3d_grad, sph3d_max_pool3d_grad_t) ----------------
-def _fwd_form(B, Mout, C):
-    ppwg = 16 if B * Mout >= 65536 else 4
-    return ("gather_fwd_half" if C % 4 == 0 and C <= 128 else "gather_fwd<4>" if C % 4 == 0 else "gather_fwd<1>"), ppwg
-
-
-def _bwd_t_form(B, Nin, Mout, C):
-    if B * Nin <= 65536 and Mout >= 2 * Nin:
-        if C % 4 == 0:
-            return "split pairs" if C <= 128 else "split<4> %d passes" % ((C + 255) // 256)
-        return "split<1> %d passes" % ((C + 63) // 64)
-    return "gather_bwd_t<4>" if C % 4 == 0 else "gather_bwd_t<1>"
-
-
-def _scatter_blocks(B, M, C):
-    """-> (blocks the elements ask for, the cap)"""
-    return (M * C + 255) // 256, max((8192 + B - 1) // B, 1)
-
-
-def _max_t_form(B, N, C):
-    return ("maxpool_bwd_t<4>" if C % 4 == 0 else "maxpool_bwd_t<1>"), (16 if B * N >= 65536 else 4)
 
 
 # ---- calls ------------------------------------------------------------------------------------------------------------------------
@@ -178,8 +159,11 @@ def test_forward_kernel_forms(dev, kernel, C, repeats):
     _check_forward(g, make_values(rng, (g.B, g.n_src, C)), "C=%d" % C)
 
 
+PLAIN_C = [4, 128, 132, 260, 3, 67, 129]
+
+
 @pytest.mark.parametrize("repeats", [False, True], ids=["unique", "repeated-ids"])
-@pytest.mark.parametrize("C", [4, 128, 132, 260, 3, 67, 129])
+@pytest.mark.parametrize("C", PLAIN_C)
 def test_plain_transposed_gather(dev, C, repeats):
     """the graphs of the forward cases in the pooling direction: 150 rows over 96 sources is short of the split rule"""
     g, rng = _a_graph(dev, repeats)
@@ -188,18 +172,22 @@ def test_plain_transposed_gather(dev, C, repeats):
 
 
 # ---- b. sixteen points per workgroup --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [8, 132, 3])
+FWD16_DIMS, FWD16_C = (2, 64, 32771, 5), [8, 132, 3]             # B, Nin, Mout, K
+MAX16_DIMS, MAX16_C = (2, 32771, 200, 8), [8, 3]
+
+
+@pytest.mark.parametrize("C", FWD16_C)
 def test_forward_sixteen_points_per_workgroup(dev, C):
-    B, N, M, K = 2, 64, 32771, 5
+    B, N, M, K = FWD16_DIMS
     g, rng = _graph(dev, 41, B, N, M, K)
     assert B * M == 65542 and M % 16 != 0                                   # over the threshold, a ragged last workgroup
     assert _fwd_form(B, M, C) == ({8: "gather_fwd_half", 132: "gather_fwd<4>", 3: "gather_fwd<1>"}[C], 16)
     _check_forward(g, make_values(rng, (B, N, C)), "C=%d" % C)
 
 
-@pytest.mark.parametrize("C", [8, 3])
+@pytest.mark.parametrize("C", MAX16_C)
 def test_max_gradient_gather_sixteen_points_per_workgroup(dev, C):
-    B, N, M, K = 2, 32771, 200, 8
+    B, N, M, K = MAX16_DIMS
     g, rng = _graph(dev, 43, B, N, M, K)
     assert _max_t_form(B, N, C) == ("maxpool_bwd_t<4>" if C == 8 else "maxpool_bwd_t<1>", 16) and N % 16 != 0
     x, go = make_values(rng, (B, N, C)), make_values(rng, (B, M, C))
@@ -208,9 +196,12 @@ def test_max_gradient_gather_sixteen_points_per_workgroup(dev, C):
 
 
 # ---- c. counts of 128 and above in packed entries ------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [8, 67])
+PACKED_DIMS, PACKED_C = (1, 256, 40, 200), [8, 67]
+
+
+@pytest.mark.parametrize("C", PACKED_C)
 def test_packed_entries_with_counts_from_128(dev, C):
-    B, N, M, K = 1, 256, 40, 200
+    B, N, M, K = PACKED_DIMS
     g, rng = _graph(dev, 47, B, N, M, K, high_from=128)
     assert int((g.cnt >= 128).sum()) >= M // 2
     x, go = make_values(rng, (B, N, C)), make_values(rng, (B, M, C))
@@ -234,10 +225,13 @@ def test_packed_entries_with_counts_from_128(dev, C):
 
 
 # ---- e. the split gather's three bodies ------------------------------------------------------------------------------------------
+SPLIT_DIMS = (2, 40, 500, 9)
+
+
 def _split_graph(dev):
     """2 clouds, 40 sources, 500 rows of up to 9: source 0 without in-edge, source j with j in-edges (1..17), the others share
     the rest, and source 39 — a hub — closes at least 300 rows"""
-    B, N, M, K = 2, 40, 500, 9
+    B, N, M, K = SPLIT_DIMS
     rng = np.random.RandomState(53)
     idx, cnt = make_graph(rng, B, 22, M, K)
     live = np.arange(K)[None, None, :] < cnt[:, :, None]
@@ -270,8 +264,12 @@ def test_split_gather_bodies(dev, body, C):
 
 
 # ---- f. the selection boundary ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [8, 67])
-@pytest.mark.parametrize("Nin,Mout", [(100, 199), (100, 200)])
+ROW_BOUNDARY, ROW_BOUNDARY_C = [(100, 199), (100, 200)], [8, 67]         # B = 2
+SOURCE_BOUNDARY = [(65536, 131072), (65537, 131074)]                    # B = 1, C = 4
+
+
+@pytest.mark.parametrize("C", ROW_BOUNDARY_C)
+@pytest.mark.parametrize("Nin,Mout", ROW_BOUNDARY)
 def test_split_rule_boundary_on_the_row_count(dev, Nin, Mout, C):
     B, K = 2, 9
     g, rng = _graph(dev, 59 + Mout, B, Nin, Mout, K)
@@ -279,7 +277,7 @@ def test_split_rule_boundary_on_the_row_count(dev, Nin, Mout, C):
     _check_sum_grads(g, make_values(rng, (B, Mout, C)), "Nin=%d Mout=%d C=%d" % (Nin, Mout, C))
 
 
-@pytest.mark.parametrize("Nin,Mout", [(65536, 131072), (65537, 131074)])
+@pytest.mark.parametrize("Nin,Mout", SOURCE_BOUNDARY)
 def test_split_rule_boundary_on_the_source_count(dev, Nin, Mout):
     B, K, C = 1, 2, 4
     g, rng = _graph(dev, 61, B, Nin, Mout, K)
@@ -288,7 +286,10 @@ def test_split_rule_boundary_on_the_source_count(dev, Nin, Mout):
 
 
 # ---- g. the max-pool scatter with a capped grid ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,N,M,C,K", [(64, 40, 300, 131, 4), (1, 64, 4100, 512, 3)])
+SCATTER_CASES = [(64, 40, 300, 131, 4), (1, 64, 4100, 512, 3)]          # B, N, M, C, K
+
+
+@pytest.mark.parametrize("B,N,M,C,K", SCATTER_CASES)
 def test_max_gradient_scatter_capped_grid(dev, B, N, M, C, K):
     blocks, cap = _scatter_blocks(B, M, C)
     assert blocks > cap and cap == {64: 128, 1: 8192}[B]                   # 39 300 > 256 * 128; 2 099 200 > 256 * 8192
@@ -300,8 +301,11 @@ def test_max_gradient_scatter_capped_grid(dev, B, N, M, C, K):
 
 
 # ---- h. the gather form of the max-pool gradient ----------------------------------------------------------------------------------
+H_DIMS, H_C = (2, 96, 150, 19), [4, 128, 260, 3, 67]
+
+
 def _h_graph(dev):
-    B, N, M, K = 2, 96, 150, 19
+    B, N, M, K = H_DIMS
     empty = np.unique(np.concatenate([[64, 149], np.random.RandomState(71).permutation(M)[:75]]))
     g, rng = _graph(dev, 73, B, N, M, K, empty_rows=empty)
     for b in range(B):                                                         # past the first 64-row sweep, and the last row
@@ -310,7 +314,7 @@ def _h_graph(dev):
     return g, rng
 
 
-@pytest.mark.parametrize("C", [4, 128, 260, 3, 67])
+@pytest.mark.parametrize("C", H_C)
 def test_max_gradient_gather_form(dev, C):
     g, rng = _h_graph(dev)
     B, N, M = g.B, g.n_src, g.M
@@ -376,7 +380,10 @@ def _roles_rows(g):
     return int(odd[0]), rest[0], rest[len(rest) // 2]
 
 
-@pytest.mark.parametrize("turn,C", [(0, 8), (1, 132), (2, 67)])
+NON_FINITE_CASES = [(0, 8), (1, 132), (2, 67)]
+
+
+@pytest.mark.parametrize("turn,C", NON_FINITE_CASES)
 def test_non_finite_inputs_stay_in_their_rows(dev, turn, C):
     g, rng = _graph(dev, 79, *A_DIMS)
     B, N, M = g.B, g.n_src, g.M
@@ -414,3 +421,47 @@ def test_non_finite_inputs_stay_in_their_rows(dev, turn, C):
         for m in rows:
             touched[b, ra[b, m], np.arange(C)] = True
     _check_confined(_max_grad_t(g, gp, ra), _max_grad_t(g, g0, ra), touched, "%s C=%d" % (_max_t_form(B, N, C)[0], C))
+
+
+# ---- the calls of the cases above, for tests/test_pool_forms.py ---------------------------------------------------------------------
+def plan_cases():
+    """-> [(op, B, Nin, Mout, C, K, forward modes)] of the parametrize lists above: the library calls their tests make"""
+    out = []
+
+    def add(op, dims, C, modes=PF.MODES):
+        B, N, M, K = dims
+        out.append((op, B, N, M, C, K, modes))
+
+    for _, C in FWD_CASES:
+        add(PF.FWD, A_DIMS, C)
+    for C in PLAIN_C:
+        add(PF.SUM_GRAD_T, A_DIMS, C)
+    for C in FWD16_C:
+        add(PF.FWD, FWD16_DIMS, C)
+    for C in MAX16_C:
+        add(PF.FWD, MAX16_DIMS, C, ("max",))
+        add(PF.MAX_GRAD_T, MAX16_DIMS, C)
+    for C in PACKED_C:
+        add(PF.FWD, PACKED_DIMS, C, ("max", "avg"))
+        add(PF.SUM_GRAD_T, PACKED_DIMS, C)
+        add(PF.MAX_GRAD_T, PACKED_DIMS, C)
+    for _, C in SPLIT_CASES:
+        add(PF.SUM_GRAD_T, SPLIT_DIMS, C)
+    for C in ROW_BOUNDARY_C:
+        for Nin, Mout in ROW_BOUNDARY:
+            add(PF.SUM_GRAD_T, (2, Nin, Mout, 9), C)
+    for Nin, Mout in SOURCE_BOUNDARY:
+        add(PF.SUM_GRAD_T, (1, Nin, Mout, 2), 4)
+    for B, N, M, C, K in SCATTER_CASES:
+        add(PF.FWD, (B, N, M, K), C, ("max",))
+        add(PF.MAX_GRAD, (B, N, M, K), C)
+    for C in H_C:
+        add(PF.FWD, H_DIMS, C, ("max",))
+        add(PF.MAX_GRAD_T, H_DIMS, C)
+        add(PF.MAX_GRAD, H_DIMS, C)
+    for _, C in NON_FINITE_CASES:
+        add(PF.FWD, A_DIMS, C)
+        add(PF.SUM_GRAD_T, A_DIMS, C)
+        add(PF.SUM_GRAD_T, SPLIT_DIMS, C)
+        add(PF.MAX_GRAD_T, A_DIMS, C)
+    return out

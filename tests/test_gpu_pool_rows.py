@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import _pool_forms as PF
 from _pool_ref import assert_sum, bits, make_graph, make_values, max_grad_ref, max_ref
 from sph3d_gcn_amd import _lib, _tgraph, tf_pool3d
 from sph3d_gcn_amd import sph3gcn_util as s3g_util
@@ -111,13 +112,14 @@ def _check_link(first, nxt, sel, N):
 
 
 SAMPLE_CASES = [("S1", 1, False), ("S9", 9, False), ("S9-dups", 9, True), ("SN", None, False), ("SN-dups", None, True)]
+INTRA_B, INTRA_NK, INTRA_C = [1, 3], [(70, 64), (200, 5)], (3, 4, 260)
 
 
 @pytest.mark.parametrize("packed", [True, False], ids=["packed", "plain"])
 @pytest.mark.parametrize("binned", [True, False], ids=["F33", "F1"])
 @pytest.mark.parametrize("sample", SAMPLE_CASES, ids=[s[0] for s in SAMPLE_CASES])
-@pytest.mark.parametrize("N,K", [(70, 64), (200, 5)], ids=["N70-K64", "N200-K5"])
-@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("N,K", INTRA_NK, ids=["N70-K64", "N200-K5"])
+@pytest.mark.parametrize("B", INTRA_B)
 def test_gradient_over_the_intra_transpose(dev, monkeypatch, B, N, K, sample, binned, packed):
     monkeypatch.setattr(_tgraph, "PACK_ENTRIES", packed)
     S = N if sample[1] is None else sample[1]
@@ -148,7 +150,8 @@ def test_gradient_over_the_intra_transpose(dev, monkeypatch, B, N, K, sample, bi
     old = _tgraph.transpose(oi, oc, N, unique_rows=True)              # ... until here: the old way, from the same rows
 
     l = _lib.lib()
-    for C in (3, 4, 260):
+    for C in INTRA_C:
+        assert PF.max_rows_form(B, N, C, link[3]) == ("maxpool_bwd_rows<%d>" % (4 if C % 4 == 0 else 1), 4)
         x, go = make_values(rng, (B, N, C)), make_values(rng, (B, S, C))
         arg = max_ref(x, pool_idx, pool_cnt)[1]
         mit, got = _t(arg, dev), _t(go, dev)
@@ -174,12 +177,15 @@ def test_gradient_over_the_intra_transpose(dev, monkeypatch, B, N, K, sample, bi
             print("%s: %d of %d elements differ in bits from sph3d_max_pool3d_grad_t" % (what, int((bits(new) != bits(was)).sum()), new.size))
 
 
-@pytest.mark.parametrize("C", [8, 3])
+SIXTEEN_DIMS, SIXTEEN_C = (2, 32771, 8, 200), [8, 3]            # B, N, K, S
+
+
+@pytest.mark.parametrize("C", SIXTEEN_C)
 def test_sixteen_points_per_workgroup(dev, C):
     """B * N >= 65536: sixteen sources per workgroup, so a wave walks four sources one after the other (the shape of
     tests/test_gpu_pool_forms.py: test_max_gradient_gather_sixteen_points_per_workgroup), the last workgroup ragged"""
-    B, N, K, S = 2, 32771, 8, 200
-    assert B * N >= 65536 and N % 16 != 0
+    B, N, K, S = SIXTEEN_DIMS
+    assert PF.max_rows_form(B, N, C, 1) == ("maxpool_bwd_rows<%d>" % (4 if C == 8 else 1), 16) and N % 16 != 0
     rng = np.random.RandomState(43 + C)
     idx, cnt = make_graph(rng, B, N, N, K)                            # the intra graph: N rows over N points, ascending ids
     sel = np.stack([rng.permutation(N)[:S] for _ in range(B)]).astype(np.int32)
@@ -295,3 +301,16 @@ def test_backward_falls_back_when_the_intra_transpose_is_gone(dev):
         grads.append(_n(xin.grad))
         ref = max_grad_ref(go, _n(mi), N)
         assert_sum(grads[-1], *ref, "autograd, %s" % ("scatter" if drop else "rows"))
+
+
+# ---- the calls of the parametrized cases above, for tests/test_pool_forms.py ----------------------------------------------------
+def plan_cases():
+    """-> [(op, B, Nin, Mout, C, F)]: sph3d_max_pool3d_grad_rows and, beside it, sph3d_max_pool3d_grad_t on the same rows"""
+    out = []
+    for B in INTRA_B:
+        for N, _ in INTRA_NK:
+            for _, S, _ in SAMPLE_CASES:
+                for C in INTRA_C:
+                    out += [(PF.MAX_GRAD_ROWS, B, N, S or N, C, F) for F in (F_BINS, 1)] + [(PF.MAX_GRAD_T, B, N, S or N, C, 1)]
+    B, N, _, S = SIXTEEN_DIMS
+    return out + [(PF.MAX_GRAD_ROWS, B, N, S, C, 1) for C in SIXTEEN_C]

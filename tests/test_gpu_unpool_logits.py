@@ -16,14 +16,16 @@ pytestmark = pytest.mark.gpu
 K_SMALL = 8
 C_COARSE = 20
 EPS = 2.0 ** -23
+# B, Nf, Mc, K.  "wide": more than one 16-id chunk per row (the headline plan has 64 slots): counts 17, 33 and 40 among the rows
+GRAPH_DIMS = {"small": (2, 96, 24, K_SMALL), "hub": (2, 300, 3, K_SMALL), "wide": (2, 80, 48, 40)}
+NUM_CLS = [1, 13, 16]
 
 
 def _graph(kind, seed):
     """-> nn_index [B, Nf, K] i32, nn_count [B, Nf] i32, nn_dist [B, Nf, K] f32, Mc.  The last coarse point has no in-edge;
     slots past a row's count name that point (a valid id nobody may read)."""
     rng = np.random.RandomState(seed)
-    # "wide": more than one 16-id chunk per row (the headline plan has 64 slots): counts 17, 33 and 40 among the rows
-    B, Nf, Mc, K = {"small": (2, 96, 24, K_SMALL), "hub": (2, 300, 3, K_SMALL), "wide": (2, 80, 48, 40)}[kind]
+    B, Nf, Mc, K = GRAPH_DIMS[kind]
     idx = np.full((B, Nf, K), Mc - 1, np.int32)
     cnt = np.zeros((B, Nf), np.int32)
     top = min(K, Mc - 1)
@@ -130,7 +132,7 @@ def _check_against_float64(dev, kind, method, c_coarse, c_skip, num_cls):
     assert bool((new[1][:, Mc - 1] == 0).all())
 
 
-@pytest.mark.parametrize("num_cls", [1, 13, 16])
+@pytest.mark.parametrize("num_cls", NUM_CLS)
 @pytest.mark.parametrize("c_skip", [0, 12])
 @pytest.mark.parametrize("method", ["mean", "weighted"])
 @pytest.mark.parametrize("kind", ["small", "hub"])
@@ -235,3 +237,9 @@ def test_s3dis_reduced_plan_fused_tail_equals_unfused(dev):
     s = max(1e-3, float(gu.abs().max()))
     print("loss fused %.7f unfused %.7f; flat gradient max |diff| / scale %.3e" % (lf, lu, float((gf - gu).abs().max()) / s))
     assert float((gf - gu).abs().max()) / s <= 5e-3
+
+
+def plan_cases():
+    """-> [(B, Nf, Mc, C, K)] of the narrow interpolation (mean and weighted) and its gradient behind the fused tails above"""
+    cases = [(kind, C) for kind in ("small", "hub") for C in NUM_CLS] + [(kind, 13) for kind in GRAPH_DIMS]
+    return [GRAPH_DIMS[kind][:3] + (C, GRAPH_DIMS[kind][3]) for kind, C in cases]
