@@ -1288,6 +1288,36 @@ int sph3d_lovasz_softmax(int B, int N, int C, const float* logits, const long lo
                          float* probs, float* coef, float* class_loss, float* loss, float* dlogits, int* order,
                          sph3d_stream_t stream);
 
+/* softmax cross-entropy with class weights, label smoothing and an ignore label, per block, and its gradient with respect to the
+ * logits (csrc/xent.hip; the float64 statement is harness/xent.py: xent_reference).  It is not an op of the reference tree.
+ * logits [B,N,C] fp32; label [B,N] int32 (label_bits = 32, as the feeds yield them) or int64 (label_bits = 64); inner [B,N] fp32 or
+ * NULL (every row); weight [C] fp32, finite and >= 0, or NULL (all 1); eps = label_smoothing in [0, 1).  Per block b, with
+ * p = softmax(x) and lse = log sum exp x of a row:
+ *   counted  row n counts iff (inner == NULL or inner[b,n] > 0; NaN > 0 is false) and (has_ignore == 0 or label[b,n] != ignore)
+ *   targets  t[n,c] = (1 - eps) w_y [c == y] + (eps / C) w_c,  A_n = sum_c t[n,c]
+ *   row      l_n = sum_c t[n,c] (lse_n - x[n,c]), computed as (1 - eps) w_y ((m + logf(se)) - x_y) + (eps / C) sum_c w_c (lse - x_c)
+ *            (ascending c; with eps == 0 the first product alone, without the factor)
+ *   hist     hist[b,c] = #{counted n: label = c}, int32, exact
+ *   D_b      normalize 0 ("count"): (float)(sum_c hist[b,c]);  1 ("weight"): (float)(sum_c (double)hist[b,c] (double)w_c), ascending c
+ *   outputs  loss_part[b * S + s], S = sph3d_softmax_xent_parts(N): the shares of S slices of the block's rows in
+ *            loss_b = sum_{counted n} l_n / D_b;  dlogits[b,n,:] = (A_n p - t[n,:]) / D_b, computed as
+ *            expf(x - m) * ((A * inv) / se) - t * inv with inv = 1 / D_b, on counted rows and exact zeros elsewhere.
+ *            D_b == 0: inv = 0, so the loss and the gradient are zeros.  dlogits == NULL: the losses and hist only.
+ * A counted row whose label lies outside [0, C) is in no class of hist; it makes its part of loss_part and its own gradient row
+ * NaN, and every read stays in range.  With weight == NULL, eps == 0, has_ignore == 0, normalize == 0, int64 labels and a mask,
+ * loss_part and dlogits are sph3d_masked_softmax_xent's bit for bit for N <= 16384 (S is then the same; beyond it S keeps growing:
+ * ceil(N / 1024), at most 256).  Two launches, fixed-order reductions, integer LDS atomics only: the same inputs give the same
+ * bits.  workspace: sph3d_softmax_xent_workspace(B, N, C) bytes (the slices' histograms), 4-byte aligned, the caller's; dead when
+ * the call's kernels are done.  C <= 4096 (weights and histogram live in LDS): sph3d_softmax_xent_supported(N, C) -> 1 | 0.
+ * -> SPH3D_OK; SPH3D_EINVAL for bad dims (B < 0, N <= 0, C <= 0, B >= 2^16, N > 2^30, B N >= 2^31), label_bits, eps or normalize, or a null
+ * pointer other than inner, weight and dlogits; SPH3D_EUNSUPPORTED before the pointers are looked at; SPH3D_EWORKSPACE. */
+int sph3d_softmax_xent_parts(int N);
+int sph3d_softmax_xent_supported(int N, int C);
+size_t sph3d_softmax_xent_workspace(int B, int N, int C);
+int sph3d_softmax_xent(int B, int N, int C, const float* logits, const void* label, int label_bits, const float* inner,
+                       const float* weight, float label_smoothing, int has_ignore, long long ignore, int normalize,
+                       float* loss_part, int* hist, float* dlogits, void* workspace, size_t workspace_bytes, sph3d_stream_t stream);
+
 /* ---- the augmentation stage (csrc/augment.hip; harness/augment.py states it in numpy): the indoor-segmentation recipes published
  * since the reference (chromatic auto-contrast, translation and jitter, colour drop, flips, anisotropic scaling, elastic
  * distortion, Mix3D scene mixing), applied IN PLACE to an assembled batch.  points [B,N,C] fp32 with xyz in channels 0:3, C in

@@ -110,6 +110,10 @@ SIGNATURES = {
     "sph3d_masked_softmax_xent": (_I, [_I, _I, _I] + [_P] * 5 + [_P]),
     "sph3d_lovasz_softmax_supported": (_I, [_I, _I]),
     "sph3d_lovasz_softmax": (_I, [_I, _I, _I] + [_P] * 3 + [_L] + [_P] * 6 + [_P]),
+    "sph3d_softmax_xent_parts": (_I, [_I]),
+    "sph3d_softmax_xent_supported": (_I, [_I, _I]),
+    "sph3d_softmax_xent_workspace": (_S, [_I] * 3),
+    "sph3d_softmax_xent": (_I, [_I, _I, _I, _P, _P, _I, _P, _P, _F, _I, _L, _I] + [_P] * 3 + [_P, _S, _P]),
     "sph3d_adam_step": (_I, [ctypes.c_longlong] + [_P] * 4 + [_F] * 4 + [_I, _P]),
     "sph3d_train_update": (_I, [_L] + [_P] * 4 + [_I] + [_F] * 4 + [_I, _F, _P, _P]),
     "sph3d_train_guard_workspace": (_S, [_L]),
