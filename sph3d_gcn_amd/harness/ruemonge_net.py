@@ -13,7 +13,7 @@ import copy
 import torch
 import torch.nn.functional as F
 
-from .. import sph3gcn_util as s3g_util
+from .. import sph3gcn_util as s3g_util, tf_loss
 from . import s3dis_net
 from .s3dis_net import GraphPlan  # noqa: F401
 
@@ -63,7 +63,7 @@ def get_loss(pred, label, end_points=None):
     B, N, C = pred.shape
     if pred.is_cuda:
         ones = torch.ones((B, N), dtype=torch.float32, device=pred.device)
-        return s3dis_net._MaskedXentFn.apply(pred, label, ones).sum() / B
+        return tf_loss.masked_softmax_xent(pred, label, ones).sum() / B
     return F.cross_entropy(pred.reshape(-1, C), label.long().reshape(-1))
 
 

@@ -2,7 +2,8 @@
 
 PyTorch custom ops ``sph3d::depthwise_conv3d`` and ``sph3d::depthwise_conv3d_grad``; the
 gradient wiring is the reference's @RegisterGradient("DepthwiseConv3d") (:23-32):
-[grad_input, grad_filter, None, None, None].
+[grad_input, grad_filter, None, None, None].  It is stated once, for the dispatcher and for the eager path of the public
+functions (_op.differentiable).
 """
 import ctypes
 from typing import Tuple
@@ -10,7 +11,7 @@ from typing import Tuple
 import torch
 import torch.nn.functional as Fn
 
-from . import _lib, _tgraph
+from . import _lib, _op, _tgraph
 
 
 def _channel_pad(C, r):
@@ -117,33 +118,17 @@ def _(input, filter, grad_output, nn_index, nn_count, bin_index):
 
 
 def _conv_setup(ctx, inputs, output):
-    input, filter, nn_index, nn_count, bin_index = inputs
-    ctx.save_for_backward(input, filter, nn_index, nn_count, bin_index)
+    ctx.save_for_backward(*inputs)
 
 
-def _conv_backward(ctx, grad_output):
+def _conv_vjp(grad, ctx, grad_output):
     input, filter, nn_index, nn_count, bin_index = ctx.saved_tensors
-    grad_input, grad_filter = _depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, bin_index)
+    grad_input, grad_filter = grad(input, filter, grad_output, nn_index, nn_count, bin_index)
     return grad_input, grad_filter, None, None, None
 
 
-_depthwise_conv3d.register_autograd(_conv_backward, setup_context=_conv_setup)
-
-
-class _DepthwiseConv3dFn(torch.autograd.Function):
-    """Eager fast path of the public API: same implementation functions as the registered custom ops, without the
-    dispatcher round trip (the step issues ~230 op calls; the torch.library path costs ~4x more host time each)."""
-
-    @staticmethod
-    def forward(ctx, input, filter, nn_index, nn_count, bin_index):
-        ctx.save_for_backward(input, filter, nn_index, nn_count, bin_index)
-        return _depthwise_conv3d_impl(input, filter, nn_index, nn_count, bin_index)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        input, filter, nn_index, nn_count, bin_index = ctx.saved_tensors
-        gi, gf = _depthwise_conv3d_grad_impl(input, filter, grad_output, nn_index, nn_count, bin_index)
-        return gi, gf, None, None, None
+_depthwise_conv3d_apply = _op.differentiable(_depthwise_conv3d, _depthwise_conv3d_impl, _conv_setup, _conv_vjp,
+                                             _depthwise_conv3d_grad, _depthwise_conv3d_grad_impl)
 
 
 def depthwise_conv3d(input, filter, nn_index, nn_count, bin_index):
@@ -158,7 +143,7 @@ def depthwise_conv3d(input, filter, nn_index, nn_count, bin_index):
 
     Differentiable in `input` and `filter` (gradients through the transposed graph, see _tgraph.py).
     """
-    return _DepthwiseConv3dFn.apply(input, filter, nn_index, nn_count, bin_index)
+    return _depthwise_conv3d_apply(input, filter, nn_index, nn_count, bin_index)
 
 
 def depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, bin_index):
@@ -234,34 +219,19 @@ def _(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, n_a
 
 
 def _fuzzy_setup(ctx, inputs, output):
-    input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q = inputs
-    ctx.save_for_backward(input, filter, nn_index, nn_count, filt_index, filt_frac)
-    ctx.kernel = (n, p, q)
+    ctx.save_for_backward(*inputs[:6])
+    ctx.kernel = inputs[6:]                      # (n, p, q)
 
 
-def _fuzzy_backward(ctx, grad_output):
+def _fuzzy_vjp(grad, ctx, grad_output):
     input, filter, nn_index, nn_count, filt_index, filt_frac = ctx.saved_tensors
-    gi, gf = _fuzzy_depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, *ctx.kernel)
+    gi, gf = grad(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, *ctx.kernel)
     return gi, gf, None, None, None, None, None, None, None
 
 
-_fuzzy_depthwise_conv3d.register_autograd(_fuzzy_backward, setup_context=_fuzzy_setup)
-
-
-class _FuzzyDepthwiseConv3dFn(torch.autograd.Function):
-    """eager path of the public API, as _DepthwiseConv3dFn"""
-
-    @staticmethod
-    def forward(ctx, input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q):
-        ctx.save_for_backward(input, filter, nn_index, nn_count, filt_index, filt_frac)
-        ctx.kernel = (n, p, q)
-        return _fuzzy_depthwise_conv3d_impl(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        input, filter, nn_index, nn_count, filt_index, filt_frac = ctx.saved_tensors
-        gi, gf = _fuzzy_depthwise_conv3d_grad_impl(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, *ctx.kernel)
-        return gi, gf, None, None, None, None, None, None, None
+_fuzzy_depthwise_conv3d_apply = _op.differentiable(_fuzzy_depthwise_conv3d, _fuzzy_depthwise_conv3d_impl, _fuzzy_setup,
+                                                   _fuzzy_vjp, _fuzzy_depthwise_conv3d_grad,
+                                                   _fuzzy_depthwise_conv3d_grad_impl)
 
 
 def fuzzy_depthwise_conv3d(input, filter, nn_index, nn_count, filt_index, filt_frac, kernel=[8, 2, 3]):
@@ -274,7 +244,7 @@ def fuzzy_depthwise_conv3d(input, filter, nn_index, nn_count, filt_index, filt_f
                atomics (grad_filter has the same bits on every run; grad_input too under deterministic()).
     """
     n, p, q = (int(v) for v in kernel)
-    return _FuzzyDepthwiseConv3dFn.apply(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q)
+    return _fuzzy_depthwise_conv3d_apply(input, filter, nn_index, nn_count, filt_index, filt_frac, n, p, q)
 
 
 def fuzzy_depthwise_conv3d_grad(input, filter, grad_output, nn_index, nn_count, filt_index, filt_frac, kernel=[8, 2, 3]):

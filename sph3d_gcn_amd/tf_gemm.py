@@ -2,14 +2,15 @@
 fully_connected (utils/sph3gcn_util.py:146-150, 204-206, 260; cuBLAS SGEMM in the reference).
 
 ``matmul(x, w)`` computes x[R,Cin] @ w[Cin,Cout] in exact fp32 with libsph3d's hand-written fp32-MFMA kernels
-(sph3d_pointwise_gemm*): custom op ``sph3d::pointwise_gemm`` with its two backward products.  (The library yardstick,
+(sph3d_pointwise_gemm*): custom op ``sph3d::pointwise_gemm`` with its two backward products, wired once for the dispatcher and
+the eager path (_op.differentiable).  (The library yardstick,
 torch.matmul on rocBLAS / hipBLASLt, lives in tools/exp_gemm.py, not here.)
 """
 import contextlib
 
 import torch
 
-from . import _lib
+from . import _lib, _op
 
 # ---- float32 matmul precision of the products on the bf16 matrix pipe (include/sph3d.h: sph3d_pointwise_gemm_pieces; DESIGN.md 4.22) ----
 # The names and meanings of torch.set_float32_matmul_precision; torch's own global is NOT read: the default path cannot change
@@ -85,34 +86,22 @@ def _gemm_setup(ctx, inputs, output):
     ctx.trans_w = trans_w
 
 
-def _gemm_backward(ctx, dy):
+def _gemm_vjp(grad, ctx, dy):
+    gemm, gemm_tn = grad
     x, w = ctx.saved_tensors
     if ctx.trans_w:
         raise RuntimeError("gradient of the transposed-weight form is not needed by the path")
-    dx = _pointwise_gemm(dy, w, True) if ctx.needs_input_grad[0] else None
-    dw = _pointwise_gemm_tn(x, dy) if ctx.needs_input_grad[1] else None
+    dx = gemm(dy, w, True) if ctx.needs_input_grad[0] else None
+    dw = gemm_tn(x, dy) if ctx.needs_input_grad[1] else None
     return dx, dw, None
 
 
-_pointwise_gemm.register_autograd(_gemm_backward, setup_context=_gemm_setup)
-
-
-class _PointwiseGemmFn(torch.autograd.Function):      # eager fast path (see tf_conv3d._DepthwiseConv3dFn)
-    @staticmethod
-    def forward(ctx, x, w):
-        ctx.save_for_backward(x, w)
-        return _pointwise_gemm_impl(x, w, False)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dx = _pointwise_gemm_impl(dy, w, True) if ctx.needs_input_grad[0] else None
-        dw = _pointwise_gemm_tn_impl(x, dy) if ctx.needs_input_grad[1] else None
-        return dx, dw
+_pointwise_gemm_apply = _op.differentiable(_pointwise_gemm, _pointwise_gemm_impl, _gemm_setup, _gemm_vjp,
+                                           (_pointwise_gemm, _pointwise_gemm_tn), (_pointwise_gemm_impl, _pointwise_gemm_tn_impl))
 
 
 def matmul(x, w):
-    return _PointwiseGemmFn.apply(x, w)
+    return _pointwise_gemm_apply(x, w, False)
 
 
 # ---- GEMM with the bias / ELU epilogue of the library (layers with biases and no batch norm) --------------------------

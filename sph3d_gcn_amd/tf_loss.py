@@ -10,6 +10,9 @@ torch statement above that.
 scope="block", return_counts=False) -> [B]`` ([1] for scope="batch"): the softmax cross-entropy with class weights, label smoothing
 and an ignore label (include/sph3d.h: sph3d_softmax_xent; csrc/xent.hip; the float64 statement is harness/xent.py: xent_reference).
 C <= 4096 (``xent_supported(N, C)``); harness/xent.py: loss() falls back to the torch statement beyond that.
+
+``masked_softmax_xent(pred, label, inner_label) -> [B, S]``: the reference models' own training loss (include/sph3d.h:
+sph3d_masked_softmax_xent), what harness/s3dis_net.py and harness/ruemonge_net.py: get_loss call.
 """
 import weakref
 
@@ -58,6 +61,38 @@ def lovasz_softmax(pred, label, inner_label=None, ignore=-1):
     # (grad mode is off inside forward(), and needs_input_grad ignores no_grad: the question is asked here)
     want_grad = torch.is_grad_enabled() and pred.requires_grad
     return _LovaszSoftmaxFn.apply(pred, label, inner_label, ignore, want_grad)
+
+
+# ---- the S3DIS / ScanNet / RueMonge training loss: mean cross-entropy over a block's inner points -------------------------------
+class _MaskedXentFn(torch.autograd.Function):
+    """one kernel that also produces the gradient with respect to the logits (include/sph3d.h: sph3d_masked_softmax_xent)"""
+
+    @staticmethod
+    def forward(ctx, pred, label, inner_label):
+        B, N, C = pred.shape
+        pred = _lib.f32(pred)
+        label = label.reshape(B, N).long().contiguous()
+        inner = inner_label.reshape(B, N).float().contiguous()
+        S = _lib.lib().sph3d_masked_softmax_xent_parts(N)
+        loss_part = torch.empty((B, S), dtype=torch.float32, device=pred.device)       # a block's loss in S slices of its points
+        # (evaluation / no_grad: the losses only — no gradient pass, no [B, N, C] store)
+        dlogits = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        _lib.check(_lib.lib().sph3d_masked_softmax_xent(B, N, C, _lib.ptr(pred), _lib.ptr(label), _lib.ptr(inner),
+                                                        _lib.ptr(loss_part), _lib.ptr(dlogits), _lib.stream_ptr()))
+        if dlogits is not None:
+            ctx.save_for_backward(dlogits)
+        return loss_part
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g[:, 0].reshape(-1, 1, 1), None, None       # (the slices of a block share its upstream gradient)
+
+
+def masked_softmax_xent(pred, label, inner_label):
+    """pred [B, N, C] logits, label [B, N], inner_label [B, N] (rows with inner_label > 0 count) -> [B, S] float32: a block's mean
+    cross-entropy over its inner points in S shares (sum(1) is the block's loss; models/SPH3D_s3dis.py:116-133)"""
+    return _MaskedXentFn.apply(pred, label, inner_label)
 
 
 # ---- softmax cross-entropy with class weights, label smoothing and an ignore label ------------------------------------------------

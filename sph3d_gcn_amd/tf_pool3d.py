@@ -1,27 +1,19 @@
 """Graph pooling — mirrors tf_ops/pooling/tf_pool3d.py:9-28.
 
 Custom ops ``sph3d::max_pool3d`` (+ ``max_pool3d_grad``) and ``sph3d::avg_pool3d``
-(+ ``avg_pool3d_grad``); gradients wired as the reference's RegisterGradient blocks.
+(+ ``avg_pool3d_grad``); gradients wired as the reference's RegisterGradient blocks, once for the dispatcher and the eager path
+(_op.differentiable).
 """
 from typing import Tuple
 
 import torch
 
-from . import _lib, _tgraph
-
-
-def _check_pool(input, nn_index, nn_count):
-    if input.dim() != 3:
-        raise ValueError("rank of input should be 3")
-    if nn_index.dim() != 3:
-        raise ValueError("rank of nn_index should be 3")
-    if nn_count.dim() != 2:
-        raise ValueError("rank of nn_count should be 2")
+from . import _lib, _op, _tgraph
 
 
 def _max_pool3d_impl(input: torch.Tensor, nn_index: torch.Tensor, nn_count: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     _lib.require_device(input, nn_index, nn_count)
-    _check_pool(input, nn_index, nn_count)
+    _op.check_graph_ranks(input, nn_index, nn_count)
     input, nn_index, nn_count = _lib.f32(input), _lib.i32(nn_index), _lib.i32(nn_count)
     B, N, C = input.shape
     M, K = nn_index.shape[1], nn_index.shape[2]
@@ -60,22 +52,9 @@ def _(input, grad_output, max_index):
     return torch.empty_like(input)
 
 
-def _max_setup(ctx, inputs, output):
-    ctx.save_for_backward(inputs[0], output[1])
-    ctx.mark_non_differentiable(output[1])
-
-
-def _max_backward(ctx, grad_output, grad_index):
-    input, max_index = ctx.saved_tensors
-    return _max_pool3d_grad(input, grad_output, max_index), None, None
-
-
-_max_pool3d.register_autograd(_max_backward, setup_context=_max_setup)
-
-
 def _avg_pool3d_impl(input: torch.Tensor, nn_index: torch.Tensor, nn_count: torch.Tensor) -> torch.Tensor:
     _lib.require_device(input, nn_index, nn_count)
-    _check_pool(input, nn_index, nn_count)
+    _op.check_graph_ranks(input, nn_index, nn_count)
     input, nn_index, nn_count = _lib.f32(input), _lib.i32(nn_index), _lib.i32(nn_count)
     B, N, C = input.shape
     M, K = nn_index.shape[1], nn_index.shape[2]
@@ -118,12 +97,12 @@ def _avg_setup(ctx, inputs, output):
     ctx.save_for_backward(*inputs)
 
 
-def _avg_backward(ctx, grad_output):
+def _avg_vjp(grad, ctx, grad_output):
     input, nn_index, nn_count = ctx.saved_tensors
-    return _avg_pool3d_grad(input, grad_output, nn_index, nn_count), None, None
+    return grad(input, grad_output, nn_index, nn_count), None, None
 
 
-_avg_pool3d.register_autograd(_avg_backward, setup_context=_avg_setup)
+_avg_pool3d_apply = _op.differentiable(_avg_pool3d, _avg_pool3d_impl, _avg_setup, _avg_vjp, _avg_pool3d_grad, _avg_pool3d_grad_impl)
 
 
 def _max_pool3d_grad_t_impl(input, grad_output, max_index, nn_count, tg, addend=None):
@@ -181,41 +160,33 @@ def _no_scatter_when_deterministic():
                            "unique_rows=True)) while the mode is on")
 
 
-class _MaxPool3dFn(torch.autograd.Function):      # eager fast path (see tf_conv3d._DepthwiseConv3dFn)
-    @staticmethod
-    def forward(ctx, input, nn_index, nn_count):
-        output, max_index = _max_pool3d_impl(input, nn_index, nn_count)
-        ctx.save_for_backward(input, max_index, nn_index, nn_count)
-        ctx.mark_non_differentiable(max_index)
-        return output, max_index
-
-    @staticmethod
-    def backward(ctx, grad_output, grad_index):
-        input, max_index, nn_index, nn_count = ctx.saved_tensors
-        # a gather, no atomics, where _gather_form finds one (rows of the ball query: no row repeats a point); otherwise the
-        # reference's scatter, which adds a point's gradient once however often a row lists it (tf_pool3d_gpu.cu:38-50)
-        form = _gather_form(input, nn_index, nn_count)
-        if form is not None:
-            impl = _max_pool3d_grad_t_impl if form[0] == "t" else _max_pool3d_grad_rows_impl
-            return impl(input, grad_output, max_index, nn_count, form[1]), None, None
-        _no_scatter_when_deterministic()
-        return _max_pool3d_grad_impl(input, grad_output, max_index), None, None
+def _max_grad(scatter, input, grad_output, max_index, nn_index, nn_count, addend=None):
+    """a gather, no atomics, where _gather_form finds one (rows of the ball query: no row repeats a point); otherwise `scatter`,
+    the reference's form, which adds a point's gradient once however often a row lists it (tf_pool3d_gpu.cu:38-50)"""
+    form = _gather_form(input, nn_index, nn_count)
+    if form is not None:
+        impl = _max_pool3d_grad_t_impl if form[0] == "t" else _max_pool3d_grad_rows_impl
+        return impl(input, grad_output, max_index, nn_count, form[1], addend=addend)
+    _no_scatter_when_deterministic()
+    g = scatter(input, grad_output, max_index)
+    return g if addend is None else g + addend
 
 
-class _AvgPool3dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, input, nn_index, nn_count):
-        ctx.save_for_backward(input, nn_index, nn_count)
-        return _avg_pool3d_impl(input, nn_index, nn_count)
+def _max_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], output[1], inputs[1], inputs[2])
+    ctx.mark_non_differentiable(output[1])
 
-    @staticmethod
-    def backward(ctx, grad_output):
-        input, nn_index, nn_count = ctx.saved_tensors
-        return _avg_pool3d_grad_impl(input, grad_output, nn_index, nn_count), None, None
+
+def _max_vjp(grad, ctx, grad_output, grad_index):
+    input, max_index, nn_index, nn_count = ctx.saved_tensors
+    return _max_grad(grad, input, grad_output, max_index, nn_index, nn_count), None, None
+
+
+_max_pool3d_apply = _op.differentiable(_max_pool3d, _max_pool3d_impl, _max_setup, _max_vjp, _max_pool3d_grad, _max_pool3d_grad_impl)
 
 
 def max_pool3d(input, nn_index, nn_count):
-    return _MaxPool3dFn.apply(input, nn_index, nn_count)
+    return _max_pool3d_apply(input, nn_index, nn_count)
 
 
 class _MaxPool3dSkipFn(torch.autograd.Function):
@@ -235,14 +206,8 @@ class _MaxPool3dSkipFn(torch.autograd.Function):
         input, max_index, nn_index, nn_count = ctx.saved_tensors
         if grad_output is None:
             return grad_skip, None, None
-        form = _gather_form(input, nn_index, nn_count)
-        if form is not None:
-            skip = grad_skip.contiguous() if grad_skip is not None else None
-            impl = _max_pool3d_grad_t_impl if form[0] == "t" else _max_pool3d_grad_rows_impl
-            return impl(input, grad_output, max_index, nn_count, form[1], addend=skip), None, None
-        _no_scatter_when_deterministic()
-        g = _max_pool3d_grad_impl(input, grad_output, max_index)
-        return (g if grad_skip is None else g + grad_skip), None, None
+        skip = grad_skip.contiguous() if grad_skip is not None else None
+        return _max_grad(_max_pool3d_grad_impl, input, grad_output, max_index, nn_index, nn_count, addend=skip), None, None
 
 
 def max_pool3d_with_skip(input, nn_index, nn_count):
@@ -255,7 +220,7 @@ def max_pool3d_grad(input, grad_output, max_index):
 
 
 def avg_pool3d(input, nn_index, nn_count):
-    return _AvgPool3dFn.apply(input, nn_index, nn_count)
+    return _avg_pool3d_apply(input, nn_index, nn_count)
 
 
 def avg_pool3d_grad(input, grad_output, nn_index, nn_count):

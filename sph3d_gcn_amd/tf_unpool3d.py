@@ -1,25 +1,17 @@
 """Graph un-pooling (feature interpolation) — mirrors tf_ops/unpooling/tf_unpool3d.py:9-28.
 
 Custom ops ``sph3d::mean_interpolate`` / ``sph3d::weighted_interpolate`` (+ ``_grad``).
-As in the reference (:21-28) ``weight`` receives no gradient.
+As in the reference (:21-28) ``weight`` receives no gradient.  The wiring is stated once for the dispatcher and the eager path
+(_op.differentiable).
 """
 import torch
 
-from . import _lib, _tgraph
-
-
-def _check(input, nn_index, nn_count):
-    if input.dim() != 3:
-        raise ValueError("rank of input should be 3")
-    if nn_index.dim() != 3:
-        raise ValueError("rank of nn_index should be 3")
-    if nn_count.dim() != 2:
-        raise ValueError("rank of nn_count should be 2")
+from . import _lib, _op, _tgraph
 
 
 def _mean_interpolate_impl(input: torch.Tensor, nn_index: torch.Tensor, nn_count: torch.Tensor) -> torch.Tensor:
     _lib.require_device(input, nn_index, nn_count)
-    _check(input, nn_index, nn_count)
+    _op.check_graph_ranks(input, nn_index, nn_count)
     input, nn_index, nn_count = _lib.f32(input), _lib.i32(nn_index), _lib.i32(nn_count)
     B, M, C = input.shape
     N, K = nn_index.shape[1], nn_index.shape[2]
@@ -62,18 +54,19 @@ def _mean_setup(ctx, inputs, output):
     ctx.save_for_backward(*inputs)
 
 
-def _mean_backward(ctx, grad_output):
+def _mean_vjp(grad, ctx, grad_output):
     input, nn_index, nn_count = ctx.saved_tensors
-    return _mean_interpolate_grad(input, grad_output, nn_index, nn_count), None, None
+    return grad(input, grad_output, nn_index, nn_count), None, None
 
 
-_mean_interpolate.register_autograd(_mean_backward, setup_context=_mean_setup)
+_mean_interpolate_apply = _op.differentiable(_mean_interpolate, _mean_interpolate_impl, _mean_setup, _mean_vjp,
+                                             _mean_interpolate_grad, _mean_interpolate_grad_impl)
 
 
 def _weighted_interpolate_impl(input: torch.Tensor, weight: torch.Tensor, nn_index: torch.Tensor,
                           nn_count: torch.Tensor) -> torch.Tensor:
     _lib.require_device(input, weight, nn_index, nn_count)
-    _check(input, nn_index, nn_count)
+    _op.check_graph_ranks(input, nn_index, nn_count)
     input, weight = _lib.f32(input), _lib.f32(weight)
     nn_index, nn_count = _lib.i32(nn_index), _lib.i32(nn_count)
     B, M, C = input.shape
@@ -119,40 +112,17 @@ def _w_setup(ctx, inputs, output):
     ctx.save_for_backward(*inputs)
 
 
-def _w_backward(ctx, grad_output):
+def _w_vjp(grad, ctx, grad_output):
     input, weight, nn_index, nn_count = ctx.saved_tensors
-    return _weighted_interpolate_grad(input, grad_output, weight, nn_index, nn_count), None, None, None
+    return grad(input, grad_output, weight, nn_index, nn_count), None, None, None
 
 
-_weighted_interpolate.register_autograd(_w_backward, setup_context=_w_setup)
-
-
-class _MeanInterpolateFn(torch.autograd.Function):      # eager fast path (see tf_conv3d._DepthwiseConv3dFn)
-    @staticmethod
-    def forward(ctx, input, nn_index, nn_count):
-        ctx.save_for_backward(input, nn_index, nn_count)
-        return _mean_interpolate_impl(input, nn_index, nn_count)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        input, nn_index, nn_count = ctx.saved_tensors
-        return _mean_interpolate_grad_impl(input, grad_output, nn_index, nn_count), None, None
-
-
-class _WeightedInterpolateFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, input, weight, nn_index, nn_count):
-        ctx.save_for_backward(input, weight, nn_index, nn_count)
-        return _weighted_interpolate_impl(input, weight, nn_index, nn_count)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        input, weight, nn_index, nn_count = ctx.saved_tensors
-        return _weighted_interpolate_grad_impl(input, grad_output, weight, nn_index, nn_count), None, None, None
+_weighted_interpolate_apply = _op.differentiable(_weighted_interpolate, _weighted_interpolate_impl, _w_setup, _w_vjp,
+                                                 _weighted_interpolate_grad, _weighted_interpolate_grad_impl)
 
 
 def mean_interpolate(input, nn_index, nn_count):
-    return _MeanInterpolateFn.apply(input, nn_index, nn_count)
+    return _mean_interpolate_apply(input, nn_index, nn_count)
 
 
 def mean_interpolate_grad(input, grad_output, nn_index, nn_count):
@@ -160,7 +130,7 @@ def mean_interpolate_grad(input, grad_output, nn_index, nn_count):
 
 
 def weighted_interpolate(input, weight, nn_index, nn_count):
-    return _WeightedInterpolateFn.apply(input, weight, nn_index, nn_count)
+    return _weighted_interpolate_apply(input, weight, nn_index, nn_count)
 
 
 def weighted_interpolate_grad(input, grad_output, weight, nn_index, nn_count):
@@ -229,7 +199,7 @@ class _InterpolateLinearFn(torch.autograd.Function):
     def forward(ctx, input, skip, w, bias, weight, nn_index, nn_count):
         from . import tf_gemm                      # noqa: F401  (the products below)
         _lib.require_device(input, w, nn_index, nn_count)
-        _check(input, nn_index, nn_count)
+        _op.check_graph_ranks(input, nn_index, nn_count)
         input, w = _lib.f32(input), _lib.f32(w)
         nn_index, nn_count = _lib.i32(nn_index), _lib.i32(nn_count)
         skip = None if skip is None or skip.shape[-1] == 0 else _lib.f32(skip)

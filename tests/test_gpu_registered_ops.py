@@ -1,13 +1,14 @@
 """The ``torch.ops.sph3d.*`` registrations: every op is callable through the dispatcher, agrees with the public function of
 the mirrored module (which takes an eager fast path around the dispatcher), has a consistent schema / fake kernel /
-autograd registration (``torch.library.opcheck``), and its registered gradient equals the fast path's.  Plus the two
+autograd registration (``torch.library.opcheck``), and its registered gradient equals the fast path's: both come from one
+statement (``_op.differentiable``), and the comparison runs over ``_op.WIRED``, the list of ops wired that way.  Plus the two
 RNG samplers of tf_sample.py and the 'IDS' / 'random' branches of build_graph."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
-from sph3d_gcn_amd import (tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm,
+from sph3d_gcn_amd import (_op, _tgraph, tf_nnquery, tf_buildkernel, tf_conv3d, tf_pool3d, tf_unpool3d, tf_sample, tf_gemm, tf_norm,
                            sph3gcn_util as s3g_util)
 from sph3d_gcn_amd.harness import synth
 
@@ -49,30 +50,52 @@ def _grads(fn, inputs, go):
     return out.detach(), [t.grad for t in leaves]
 
 
-def test_feature_ops_registered_gradients_equal_fast_path(dev):
+def _feature_cases(dev):
+    """registered op's name -> (through the dispatcher, the public function, differentiable inputs, output shape), on _graph's shapes"""
     db, q, idx, cnt, dst, filt = _graph(dev)
+    fi, ff = tf_buildkernel.fuzzy_spherical_kernel(db, q, idx, cnt, dst, 0.3, kernel=[8, 2, 2])
     B, N, M, K, C, r = 2, 120, 50, 12, 8, 2
     g = torch.Generator(device="cpu").manual_seed(0)
     x = torch.randn(B, N, C, generator=g).to(dev)
     w = torch.randn(33, C, r, generator=g).to(dev)
     wt = torch.rand(B, M, K, generator=g).to(dev)
-    cases = [
-        ("depthwise_conv3d", lambda a, b: torch.ops.sph3d.depthwise_conv3d(a, b, idx, cnt, filt),
-         lambda a, b: tf_conv3d.depthwise_conv3d(a, b, idx, cnt, filt), (x, w), (B, M, C * r)),
-        ("max_pool3d", lambda a: torch.ops.sph3d.max_pool3d(a, idx, cnt), lambda a: tf_pool3d.max_pool3d(a, idx, cnt), (x,), (B, M, C)),
-        ("avg_pool3d", lambda a: torch.ops.sph3d.avg_pool3d(a, idx, cnt), lambda a: tf_pool3d.avg_pool3d(a, idx, cnt), (x,), (B, M, C)),
-        ("mean_interpolate", lambda a: torch.ops.sph3d.mean_interpolate(a, idx, cnt),
-         lambda a: tf_unpool3d.mean_interpolate(a, idx, cnt), (x,), (B, M, C)),
-        ("weighted_interpolate", lambda a: torch.ops.sph3d.weighted_interpolate(a, wt, idx, cnt),
-         lambda a: tf_unpool3d.weighted_interpolate(a, wt, idx, cnt), (x,), (B, M, C)),
-    ]
-    for name, reg, fast, inputs, oshape in cases:
+    x2, w2 = torch.randn(300, 20, generator=g).to(dev), torch.randn(20, 12, generator=g).to(dev)
+    ops = torch.ops.sph3d
+    cases = {
+        "sph3d::depthwise_conv3d": (lambda a, b: ops.depthwise_conv3d(a, b, idx, cnt, filt),
+                                    lambda a, b: tf_conv3d.depthwise_conv3d(a, b, idx, cnt, filt), (x, w), (B, M, C * r)),
+        "sph3d::fuzzy_depthwise_conv3d": (lambda a, b: ops.fuzzy_depthwise_conv3d(a, b, idx, cnt, fi, ff, 8, 2, 2),
+                                          lambda a, b: tf_conv3d.fuzzy_depthwise_conv3d(a, b, idx, cnt, fi, ff, kernel=[8, 2, 2]),
+                                          (x, w), (B, M, C * r)),
+        "sph3d::max_pool3d": (lambda a: ops.max_pool3d(a, idx, cnt), lambda a: tf_pool3d.max_pool3d(a, idx, cnt), (x,), (B, M, C)),
+        "sph3d::avg_pool3d": (lambda a: ops.avg_pool3d(a, idx, cnt), lambda a: tf_pool3d.avg_pool3d(a, idx, cnt), (x,), (B, M, C)),
+        "sph3d::mean_interpolate": (lambda a: ops.mean_interpolate(a, idx, cnt), lambda a: tf_unpool3d.mean_interpolate(a, idx, cnt),
+                                    (x,), (B, M, C)),
+        "sph3d::weighted_interpolate": (lambda a: ops.weighted_interpolate(a, wt, idx, cnt),
+                                        lambda a: tf_unpool3d.weighted_interpolate(a, wt, idx, cnt), (x,), (B, M, C)),
+        "sph3d::pointwise_gemm": (lambda a, b: ops.pointwise_gemm(a, b, False), tf_gemm.matmul, (x2, w2), (300, 12)),
+    }
+    return cases, (idx, cnt, filt, fi, ff, x, w, wt, g)
+
+
+def test_every_wired_op_has_a_case(dev):
+    cases, _ = _feature_cases(dev)
+    assert len(_op.WIRED) == 7 and sorted(op._qualname for op, _ in _op.WIRED) == sorted(cases)
+
+
+def test_feature_ops_registered_gradients_equal_fast_path(dev):
+    B, N, M, K, C, r = 2, 120, 50, 12, 8, 2
+    cases, (idx, cnt, filt, fi, ff, x, w, wt, g) = _feature_cases(dev)
+    for op, _apply in _op.WIRED:                     # every op wired through _op.differentiable: an eighth cannot go uncompared
+        name = op._qualname
+        reg, fast, inputs, oshape = cases[name]
         go = torch.randn(*oshape, generator=g).to(dev)
         o1, g1 = _grads(reg, inputs, go)
         o2, g2 = _grads(fast, inputs, go)
         torch.testing.assert_close(o1, o2, rtol=0, atol=0)
+        assert len(g1) == len(g2) == len(inputs)
         for a, b in zip(g1, g2):
-            torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6), name
+            torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6, msg=lambda m: "%s: %s" % (name, m))
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     torch.library.opcheck(torch.ops.sph3d.depthwise_conv3d, (xr, wr, idx, cnt, filt), test_utils=CHECKS)
     torch.library.opcheck(torch.ops.sph3d.max_pool3d, (xr, idx, cnt), test_utils=CHECKS)
@@ -81,6 +104,39 @@ def test_feature_ops_registered_gradients_equal_fast_path(dev):
     torch.library.opcheck(torch.ops.sph3d.weighted_interpolate, (xr, wt, idx, cnt), test_utils=CHECKS)
     go = torch.randn(B, M, C * r, generator=g).to(dev)
     torch.library.opcheck(torch.ops.sph3d.depthwise_conv3d_grad, (x, w, go, idx, cnt, filt), test_utils=("test_schema", "test_faketensor"))
+    torch.library.opcheck(torch.ops.sph3d.fuzzy_depthwise_conv3d, (xr, wr, idx, cnt, fi, ff, 8, 2, 2), test_utils=CHECKS)
+
+
+def test_registered_max_pool_takes_the_gather_where_the_public_function_does(dev):
+    """with a transposed pooling graph whose builder promised unique rows, both paths run the atomics-free gather: the same bits"""
+    db, q, idx, cnt, dst, filt = _graph(dev)
+    B, N, M, C = 2, 120, 50, 8
+    g = torch.Generator(device="cpu").manual_seed(2)
+    x = torch.randn(B, N, C, generator=g).to(dev)
+    go = torch.randn(B, M, C, generator=g).to(dev)
+    _tgraph.transpose(idx, cnt, N, unique_rows=True)
+    assert tf_pool3d._gather_form(x, idx, cnt)[0] == "t"
+    o1, (g1,) = _grads(lambda a: torch.ops.sph3d.max_pool3d(a, idx, cnt), (x,), go)
+    o2, (g2,) = _grads(lambda a: tf_pool3d.max_pool3d(a, idx, cnt), (x,), go)
+    assert torch.equal(o1, o2) and torch.equal(g1, g2)
+    # (and it is the pooling gradient: every output's gradient lands on its winner)
+    want = torch.zeros(B, N, C, dtype=torch.float64, device=dev)
+    _, arg = tf_pool3d.max_pool3d(x, idx, cnt)
+    want.scatter_add_(1, arg.long(), go.double())
+    torch.testing.assert_close(g1.double(), want, rtol=1e-6, atol=1e-6)
+
+
+def test_registered_max_pool_follows_deterministic_mode(dev):
+    """deterministic mode, no transposed pooling graph with unique rows and no row link: backward refuses on the host, through the
+    dispatcher as through the public function, before anything is launched for the gradient"""
+    with _tgraph.deterministic():
+        db, q, idx, cnt, dst, filt = _graph(dev)
+        x = torch.randn(2, 120, 8, device=dev)
+        assert tf_pool3d._gather_form(x, idx, cnt) is None
+        for fn in (torch.ops.sph3d.max_pool3d, tf_pool3d.max_pool3d):
+            out, _ = fn(x.clone().requires_grad_(True), idx, cnt)
+            with pytest.raises(RuntimeError, match="deterministic mode is on"):
+                out.backward(torch.ones_like(out))
 
 
 def test_gemm_and_elu_bn_registered(dev):

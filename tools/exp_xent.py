@@ -84,7 +84,7 @@ def op_only(config):
         pred, label, inner, weight = inputs(B, N, C)
         fn = {"defaults": lambda p, l, i: tf_loss.softmax_xent(p, l, i),
               "options": lambda p, l, i: tf_loss.softmax_xent(p, l, i, **options(weight)),
-              "existing": lambda p, l, i: s3dis_net._MaskedXentFn.apply(p, l, i)}[config]
+              "existing": lambda p, l, i: tf_loss.masked_softmax_xent(p, l, i)}[config]
         t = timed(lambda: fwd_bwd(fn, pred, label, inner))
         print("%d x %d x %d  %s, forward + backward: %.1f us" % (B, N, C, config, t), flush=True)
 
@@ -93,7 +93,7 @@ def ops():
     compare("(a) the new op beside the existing op", SHAPES, lambda w: (
         ("softmax_xent, defaults", lambda p, l, i: tf_loss.softmax_xent(p, l, i)),
         ("softmax_xent, options on", lambda p, l, i: tf_loss.softmax_xent(p, l, i, **options(w))),
-        ("masked_softmax_xent", lambda p, l, i: s3dis_net._MaskedXentFn.apply(p, l, i))))
+        ("masked_softmax_xent", lambda p, l, i: tf_loss.masked_softmax_xent(p, l, i))))
     compare("(b) the new op beside the torch statement, block scope", SHAPES, lambda w: (
         ("softmax_xent, options on", lambda p, l, i: tf_loss.softmax_xent(p, l, i, **options(w))),
         ("xent_torch, options on", lambda p, l, i: xent.xent_torch(p, l, i, **options(w)))))
