@@ -656,7 +656,10 @@ size_t sph3d_pointwise_gemm_tn_workspace(int R, int Cin, int Cout);
  * y[R,C] is the matmul output; out = (elu(y) - mean) * rstd * gamma + beta with per-channel statistics of
  * elu(y) over the R rows (training) or the running statistics (inference).  `momentum` is the weight of
  * the NEW batch statistics (1 - 0.99).  save_mean / save_rstd [C] feed the backward pass, which needs only
- * y (elu(y) is recomputed).  Requires C % 4 == 0 and C <= 1024.  workspace: sph3d_elu_bn_workspace(). */
+ * y (elu(y) is recomputed).  Requires C % 4 == 0, C <= 1024 and 0 < R <= 2^31 - 1024 = 2147482624 (the
+ * statistics pass indexes rows in int and forms R + 1023); all seven sph3d_elu_bn_* entries answer SPH3D_EINVAL
+ * to anything else before they read or launch anything, then SPH3D_EWORKSPACE to a missing or short workspace
+ * where they take one.  workspace: sph3d_elu_bn_workspace(), defined for every int R. */
 size_t sph3d_elu_bn_workspace(int R, int C);
 int sph3d_elu_bn_forward(int R, int C, const float* y, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, float momentum, float eps, int training,
@@ -686,7 +689,7 @@ int sph3d_elu_bn_forward_partials(int R, int C, int nblk, const float* partial, 
  * the caller adds the other ranks' buffers on top (one all-reduce, ordered on `stream`), `*_apply` forms the statistics from the
  * summed buffer and runs the apply pass.  Nothing returns to the host, nothing is allocated, no entry point synchronises; with the
  * buffer left as `*_sums` wrote it the pair computes sph3d_elu_bn_forward / _backward (training) bit for bit.  Same shapes
- * (C % 4 == 0, C <= 1024, R > 0: every rank needs at least one row); workspace: sph3d_elu_bn_workspace(R, C) of the rank's own R. */
+ * (C % 4 == 0, C <= 1024, 0 < R <= 2^31 - 1024: every rank needs at least one row); workspace: sph3d_elu_bn_workspace(R, C) of the rank's own R. */
 /* sums [2C + 1] (double) = sum elu(y), sum elu(y)^2 per channel, then the row count R.  partial == NULL: the statistics pass over y
  * runs here (needs the workspace; nblk is ignored); else partial[nblk][2][C] as sph3d_elu_bn_forward_partials takes it (y and the
  * workspace are not read). */

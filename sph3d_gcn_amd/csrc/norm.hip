@@ -122,19 +122,14 @@ __device__ __forceinline__ void sum_partials_32x8(int C, int nblk, const float* 
     }
 }
 
-// forward finalize: mean / rstd from the partials (double), running statistics update
+// ---- what follows the sums, stated once: the uncut finalize kernels and the kernels after the cut both call these -----------------
+// forward: mean / rstd of channel c from s = sum z, q = sum z*z over R rows (double), running statistics update
 // running = (1-m)*running + m*batch with the BIASED batch variance: tf.layers.batch_normalization on rank-2/3 inputs takes
 // the non-fused path (tf.nn.moments), which stores the population variance — torch's F.batch_norm would store the
 // Bessel-corrected one (3 % larger at the ModelNet fc layers, where R = batch size)
-__global__ __launch_bounds__(1024) void norm_fwd_finalize(int R, int C, int nblk, const float* __restrict__ partial, float eps, float momentum,
-                                  float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ run_mean,
-                                  float* __restrict__ run_var)
+__device__ __forceinline__ void norm_fwd_stats(int c, double s, double q, double R, float eps, float momentum, float* mean, float* rstd,
+                                               float* run_mean, float* run_var)
 {
-    const int c = blockIdx.x * 32 + ((int)threadIdx.x & 31);
-    const int py = (int)threadIdx.x >> 5;
-    double s, q;
-    sum_partials_32x8(C, nblk, partial, c, py, s, q);
-    if (c >= C || py != 0) return;
     const double m = s / R;
     double var = q / R - m * m;
     if (var < 0.0) var = 0.0;
@@ -144,6 +139,26 @@ __global__ __launch_bounds__(1024) void norm_fwd_finalize(int R, int C, int nblk
         run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * m);
         run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * var);
     }
+}
+
+// backward: the two per-channel means the apply pass needs, coef [2][C] = dbeta/R, dgamma/R from s = sum dout, q = sum dout * zhat
+__device__ __forceinline__ void norm_bwd_coef(int c, int C, double s, double q, double R, int training, float* coef)
+{
+    coef[c] = training ? (float)(s / R) : 0.f;          // with fixed (running) statistics the two mean terms vanish
+    coef[C + c] = training ? (float)(q / R) : 0.f;
+}
+
+// forward finalize: the statistics from the partials
+__global__ __launch_bounds__(1024) void norm_fwd_finalize(int R, int C, int nblk, const float* __restrict__ partial, float eps, float momentum,
+                                  float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ run_mean,
+                                  float* __restrict__ run_var)
+{
+    const int c = blockIdx.x * 32 + ((int)threadIdx.x & 31);
+    const int py = (int)threadIdx.x >> 5;
+    double s, q;
+    sum_partials_32x8(C, nblk, partial, c, py, s, q);
+    if (c >= C || py != 0) return;
+    norm_fwd_stats(c, s, q, (double)R, eps, momentum, mean, rstd, run_mean, run_var);
 }
 
 // inference: statistics come from the running buffers
@@ -156,10 +171,9 @@ __global__ void norm_eval_stats(int C, const float* __restrict__ run_mean, const
     rstd[c] = (float)(1.0 / sqrt((double)run_var[c] + (double)eps));
 }
 
-// backward finalize: dgamma, dbeta, and the two per-channel means the apply pass needs
+// backward finalize: dgamma, dbeta and coef
 __global__ __launch_bounds__(1024) void norm_bwd_finalize(int R, int C, int nblk, int training, const float* __restrict__ partial,
-                                  float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                  float* __restrict__ coef /* [2][C]: dbeta/R, dgamma/R (0 in inference mode) */)
+                                  float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef)
 {
     const int c = blockIdx.x * 32 + ((int)threadIdx.x & 31);
     const int py = (int)threadIdx.x >> 5;
@@ -168,14 +182,13 @@ __global__ __launch_bounds__(1024) void norm_bwd_finalize(int R, int C, int nblk
     if (c >= C || py != 0) return;
     dbeta[c] = (float)s;
     dgamma[c] = (float)q;
-    coef[c] = training ? (float)(s / R) : 0.f;          // with fixed (running) statistics the two mean terms vanish
-    coef[C + c] = training ? (float)(q / R) : 0.f;
+    norm_bwd_coef(c, C, s, q, (double)R, training, coef);
 }
 
 // ---- the same two finalizes cut at the statistics (batch norm over the rows of several ranks) ---------------
 // A rank's per-channel sums leave in double, a collective the caller issues adds the other ranks' on top, and the statistics are
-// formed from what comes back.  The arithmetic after the cut is norm_fwd_finalize's / norm_bwd_finalize's, expression for
-// expression, with the row count a double read from the buffer: unchanged sums give bit-identical statistics.
+// formed from what comes back by the two functions above, with the row count a double read from the buffer: unchanged sums give
+// bit-identical statistics.
 
 // forward, before the cut: sums[0..C) = sum z, sums[C..2C) = sum z*z, sums[2C] = R
 __global__ __launch_bounds__(1024) void norm_fwd_sums(int R, int C, int nblk, const float* __restrict__ partial,
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(1024) void norm_fwd_sums(int R, int C, int nblk, co
     if (c == 0) sums[2 * C] = (double)R;
 }
 
-// forward, after the cut: mean / rstd / running statistics from the summed buffer; the global row count stays on the device
+// forward, after the cut: the statistics from the summed buffer; the global row count stays on the device
 __global__ __launch_bounds__(256) void norm_fwd_stats_from_sums(int C, const double* __restrict__ sums, float eps, float momentum,
                                                                 float* __restrict__ mean, float* __restrict__ rstd,
                                                                 float* __restrict__ run_mean, float* __restrict__ run_var,
@@ -199,17 +212,8 @@ __global__ __launch_bounds__(256) void norm_fwd_stats_from_sums(int C, const dou
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const double s = sums[c], q = sums[C + c], R = sums[2 * C];
-    const double m = s / R;
-    double var = q / R - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (run_mean != nullptr) {
-        run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * m);
-        run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * var);
-    }
-    if (c == 0) count[0] = R;
+    norm_fwd_stats(c, sums[c], sums[C + c], sums[2 * C], eps, momentum, mean, rstd, run_mean, run_var);
+    if (c == 0) count[0] = sums[2 * C];
 }
 
 // backward, before the cut: this rank's dgamma / dbeta (they stay local sums: the gradient all-reduce adds the ranks') and
@@ -228,15 +232,12 @@ __global__ __launch_bounds__(1024) void norm_bwd_sums(int C, int nblk, const flo
     sums[C + c] = q;
 }
 
-// backward, after the cut: the two per-channel means over the global rows
+// backward, after the cut: coef over the global rows
 __global__ __launch_bounds__(256) void norm_bwd_coef_from_sums(int C, const double* __restrict__ sums, const double* __restrict__ count,
                                                                float* __restrict__ coef)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const double R = count[0];
-    coef[c] = (float)(sums[c] / R);
-    coef[C + c] = (float)(sums[C + c] / R);
+    if (c < C) norm_bwd_coef(c, C, sums[c], sums[C + c], count[0], 1, coef);
 }
 
 // BWD = false: out = (elu(y) - mean) * rstd * gamma + beta
@@ -288,8 +289,26 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(long long total4, int C
     }
 }
 
+// ---- the host side: one preamble, one launcher per stage, seven entries ------------------------------------------------------------
+// The most rows an entry takes: the largest R at which every int expression of norm_reduce_kernel is exact.  Its largest values:
+//   rows_per_block = (R + gridDim.x - 1) / gridDim.x    the numerator, gridDim.x <= kNormMaxBlocks = 1024:     at most R + 1023
+//   r0 + rows_per_block <= gridDim.x * ceil(R / gridDim.x)                                                    at most R + 1023
+//   rb += UN * rows_per_iter, from a row rb <= r1 - 1 <= R - 1, UN = 4, rows_per_iter = 256 / cg <= 256:      at most R + 1023
+//   rb + u * rows_per_iter, u <= 3, lies below that.
+// So R + 1023 <= INT_MAX.  (Everything past the row index is size_t or long long: (size_t)rc * C, total4.)
+constexpr int kNormMaxRows = 0x7fffffff - 1023;
+
 // one workgroup per ~32 rows (the small levels have only a few thousand rows: 128-row blocks left most CUs idle)
-static int norm_blocks(int R) { int b = (R + 31) / 32; return b < 1 ? 1 : (b > kNormMaxBlocks ? kNormMaxBlocks : b); }
+static int norm_blocks(int R)
+{
+    const long long b = ((long long)R + 31) / 32;
+    return b < 1 ? 1 : (b > kNormMaxBlocks ? kNormMaxBlocks : (int)b);
+}
+
+struct NormWorkspace {                               // the workspace's layout: partial[nblk][2][C], then coef[2][C]
+    int nblk;
+    float *partial, *coef;
+};
 
 }  // namespace sph3d
 
@@ -300,6 +319,59 @@ extern "C" size_t sph3d_elu_bn_workspace(int R, int C)
     return sizeof(float) * ((size_t)norm_blocks(R) * 2 * C + 2 * (size_t)C);
 }
 
+// What every entry does first: the dimension check and, for an entry that needs the workspace (ws != NULL), the workspace check and
+// the carve.  Nothing is read or launched before it answers.
+static int norm_enter(const char* who, int R, int C, NormWorkspace* ws = nullptr, void* workspace = nullptr, size_t workspace_bytes = 0)
+{
+    SPH3D_REQUIRE(R > 0 && R <= kNormMaxRows && C > 0 && C % 4 == 0 && C <= 1024, "%s: needs 0<R<=%d, C%%4==0, C<=1024 (got R=%d C=%d)", who,
+                  kNormMaxRows, R, C);
+    if (ws == nullptr) return SPH3D_OK;
+    const size_t need = sph3d_elu_bn_workspace(R, C);
+    if (workspace == nullptr || workspace_bytes < need) {
+        set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, need);
+        return SPH3D_EWORKSPACE;
+    }
+    ws->nblk = norm_blocks(R);
+    ws->partial = (float*)workspace;
+    ws->coef = ws->partial + (size_t)ws->nblk * 2 * C;
+    return SPH3D_OK;
+}
+
+template <bool BWD>
+static void launch_reduce(hipStream_t st, int R, int C, const NormWorkspace& ws, const float* y, const float* dout, const float* mean,
+                          const float* rstd)
+{
+    hipLaunchKernelGGL(norm_reduce_kernel<BWD>, dim3(ws.nblk), dim3(256), 0, st, R, C, y, dout, mean, rstd, ws.partial);
+}
+
+// the finalize family: a kernel that sums the partials takes 32 channels x kFinLanes threads per workgroup, one that starts from
+// per-channel values 256 channels
+template <class... Params, class... Args>
+static void launch_stats(void (*kern)(Params...), bool sums_partials, int C, hipStream_t st, Args... args)
+{
+    const int per = sums_partials ? 32 : 256;
+    kern<<<dim3((C + per - 1) / per), dim3(sums_partials ? 32 * kFinLanes : 256), 0, st>>>(args...);
+}
+
+template <bool BWD>
+static void launch_apply(hipStream_t st, int R, int C, const float* y, const float* dout, const float* mean, const float* rstd,
+                         const float* gamma, const float* beta, const float* coef, float* out)
+{
+    const long long total4 = (long long)R * C / 4;
+    const long long blocks = (total4 + 255) / 256;
+    hipLaunchKernelGGL(norm_apply_kernel<BWD>, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, total4, C, y, dout, mean,
+                       rstd, gamma, beta, coef, out);
+}
+
+// training-mode forward once the partials exist: finalize + apply
+static void forward_from_partials(hipStream_t st, int R, int C, int nblk, const float* partial, const float* y, const float* gamma,
+                                  const float* beta, float* running_mean, float* running_var, float momentum, float eps, float* out,
+                                  float* save_mean, float* save_rstd)
+{
+    launch_stats(norm_fwd_finalize, true, C, st, R, C, nblk, partial, eps, momentum, save_mean, save_rstd, running_mean, running_var);
+    launch_apply<false>(st, R, C, y, nullptr, save_mean, save_rstd, gamma, beta, nullptr, out);
+}
+
 // training != 0: batch statistics (saved to save_mean / save_rstd for the backward pass), running stats updated.
 // training == 0: normalise with running_mean / running_var (save_* receive the statistics used).
 extern "C" int sph3d_elu_bn_forward(int R, int C, const float* y, const float* gamma, const float* beta,
@@ -307,29 +379,18 @@ extern "C" int sph3d_elu_bn_forward(int R, int C, const float* y, const float* g
                                     float* out, float* save_mean, float* save_rstd,
                                     void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    const size_t need = sph3d_elu_bn_workspace(R, C);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("elu_bn_forward: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
+    NormWorkspace ws;
+    if (int rc = norm_enter("sph3d_elu_bn_forward", R, C, &ws, workspace, workspace_bytes)) return rc;
     hipStream_t st = as_stream(stream);
-    float* partial = (float*)workspace;
-    const int nblk = norm_blocks(R);
     if (training) {
-        hipLaunchKernelGGL(norm_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, R, C, y, nullptr, nullptr, nullptr, partial);
-        hipLaunchKernelGGL(norm_fwd_finalize, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, R, C, nblk, partial, eps, momentum,
-                           save_mean, save_rstd, running_mean, running_var);
+        launch_reduce<false>(st, R, C, ws, y, nullptr, nullptr, nullptr);
+        forward_from_partials(st, R, C, ws.nblk, ws.partial, y, gamma, beta, running_mean, running_var, momentum, eps, out, save_mean,
+                              save_rstd);
     } else {
-        SPH3D_REQUIRE(running_mean != nullptr && running_var != nullptr, "elu_bn: inference needs running statistics");
-        hipLaunchKernelGGL(norm_eval_stats, dim3((C + 255) / 256), dim3(256), 0, st, C, running_mean, running_var, eps,
-                           save_mean, save_rstd);
+        SPH3D_REQUIRE(running_mean != nullptr && running_var != nullptr, "sph3d_elu_bn_forward: inference needs running statistics");
+        launch_stats(norm_eval_stats, false, C, st, C, running_mean, running_var, eps, save_mean, save_rstd);
+        launch_apply<false>(st, R, C, y, nullptr, save_mean, save_rstd, gamma, beta, nullptr, out);
     }
-    const long long total4 = (long long)R * C / 4;
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(norm_apply_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, total4, C, y, nullptr, save_mean,
-                       save_rstd, gamma, beta, nullptr, out);
     return check_launch("sph3d_elu_bn_forward");
 }
 
@@ -339,16 +400,10 @@ extern "C" int sph3d_elu_bn_forward_partials(int R, int C, int nblk, const float
                                              const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                                              float* out, float* save_mean, float* save_rstd, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024 && nblk > 0, "elu_bn_partials: needs R>0, C%%4==0, C<=1024, nblk>0 (got R=%d C=%d nblk=%d)",
-                  R, C, nblk);
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(norm_fwd_finalize, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, R, C, nblk, partial, eps, momentum,
-                       save_mean, save_rstd, running_mean, running_var);
-    const long long total4 = (long long)R * C / 4;
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(norm_apply_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, total4, C, y, nullptr, save_mean,
-                       save_rstd, gamma, beta, nullptr, out);
+    if (int rc = norm_enter("sph3d_elu_bn_forward_partials", R, C)) return rc;
+    SPH3D_REQUIRE(nblk > 0, "sph3d_elu_bn_forward_partials: nblk=%d partial row blocks", nblk);
+    forward_from_partials(as_stream(stream), R, C, nblk, partial, y, gamma, beta, running_mean, running_var, momentum, eps, out, save_mean,
+                          save_rstd);
     return check_launch("sph3d_elu_bn_forward_partials");
 }
 
@@ -357,55 +412,34 @@ extern "C" int sph3d_elu_bn_backward(int R, int C, const float* y, const float* 
                                      float* dy, float* dgamma, float* dbeta,
                                      void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    const size_t need = sph3d_elu_bn_workspace(R, C);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("elu_bn_backward: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
+    NormWorkspace ws;
+    if (int rc = norm_enter("sph3d_elu_bn_backward", R, C, &ws, workspace, workspace_bytes)) return rc;
     hipStream_t st = as_stream(stream);
-    float* partial = (float*)workspace;
-    const int nblk = norm_blocks(R);
-    float* coef = partial + (size_t)nblk * 2 * C;
-    hipLaunchKernelGGL(norm_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, R, C, y, dout, save_mean, save_rstd, partial);
-    hipLaunchKernelGGL(norm_bwd_finalize, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, R, C, nblk, training, partial, dgamma, dbeta, coef);
-    const long long total4 = (long long)R * C / 4;
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(norm_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, total4, C, y, dout, save_mean,
-                       save_rstd, gamma, nullptr, coef, dy);
+    launch_reduce<true>(st, R, C, ws, y, dout, save_mean, save_rstd);
+    launch_stats(norm_bwd_finalize, true, C, st, R, C, ws.nblk, training, ws.partial, dgamma, dbeta, ws.coef);
+    launch_apply<true>(st, R, C, y, dout, save_mean, save_rstd, gamma, nullptr, ws.coef, dy);
     return check_launch("sph3d_elu_bn_backward");
 }
 
 // ---- batch norm over several ranks' rows: the two ops above cut at the statistics (include/sph3d.h) -------------------------
-static int norm_apply_blocks(long long total4)
-{
-    long long blocks = (total4 + 255) / 256;
-    return (int)(blocks > 4096 ? 4096 : blocks);
-}
-
 // partial == NULL: the statistics pass over y runs here, into the workspace; else partial[nblk][2][C] as in
 // sph3d_elu_bn_forward_partials (no workspace needed).  sums: double [2C + 1] = sum elu(y), sum elu(y)^2, R.
 extern "C" int sph3d_elu_bn_forward_sums(int R, int C, int nblk, const float* partial, const float* y, double* sums,
                                          void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_forward_sums: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    SPH3D_REQUIRE(sums != nullptr, "elu_bn_forward_sums: sums is NULL");
+    NormWorkspace ws;
+    if (int rc = norm_enter("sph3d_elu_bn_forward_sums", R, C, partial == nullptr ? &ws : nullptr, workspace, workspace_bytes)) return rc;
+    SPH3D_REQUIRE(sums != nullptr, "sph3d_elu_bn_forward_sums: sums is NULL");
     hipStream_t st = as_stream(stream);
     if (partial == nullptr) {
-        const size_t need = sph3d_elu_bn_workspace(R, C);
-        if (workspace == nullptr || workspace_bytes < need) {
-            set_error("elu_bn_forward_sums: workspace %zu B < required %zu B", workspace_bytes, need);
-            return SPH3D_EWORKSPACE;
-        }
-        SPH3D_REQUIRE(y != nullptr, "elu_bn_forward_sums: y is NULL");
-        nblk = norm_blocks(R);
-        hipLaunchKernelGGL(norm_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, R, C, y, nullptr, nullptr, nullptr, (float*)workspace);
-        partial = (const float*)workspace;
+        SPH3D_REQUIRE(y != nullptr, "sph3d_elu_bn_forward_sums: y is NULL");
+        launch_reduce<false>(st, R, C, ws, y, nullptr, nullptr, nullptr);
+        nblk = ws.nblk;
+        partial = ws.partial;
     } else {
-        SPH3D_REQUIRE(nblk > 0, "elu_bn_forward_sums: nblk=%d partial row blocks", nblk);
+        SPH3D_REQUIRE(nblk > 0, "sph3d_elu_bn_forward_sums: nblk=%d partial row blocks", nblk);
     }
-    hipLaunchKernelGGL(norm_fwd_sums, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, R, C, nblk, partial, sums);
+    launch_stats(norm_fwd_sums, true, C, st, R, C, nblk, partial, sums);
     return check_launch("sph3d_elu_bn_forward_sums");
 }
 
@@ -415,14 +449,11 @@ extern "C" int sph3d_elu_bn_forward_apply(int R, int C, const double* sums, cons
                                           float* running_mean, float* running_var, float momentum, float eps,
                                           float* out, float* save_mean, float* save_rstd, double* count, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_forward_apply: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "elu_bn_forward_apply: sums / count is NULL");
+    if (int rc = norm_enter("sph3d_elu_bn_forward_apply", R, C)) return rc;
+    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "sph3d_elu_bn_forward_apply: sums / count is NULL");
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(norm_fwd_stats_from_sums, dim3((C + 255) / 256), dim3(256), 0, st, C, sums, eps, momentum, save_mean, save_rstd,
-                       running_mean, running_var, count);
-    const long long total4 = (long long)R * C / 4;
-    hipLaunchKernelGGL(norm_apply_kernel<false>, dim3((unsigned)norm_apply_blocks(total4)), dim3(256), 0, st, total4, C, y, nullptr,
-                       save_mean, save_rstd, gamma, beta, nullptr, out);
+    launch_stats(norm_fwd_stats_from_sums, false, C, st, C, sums, eps, momentum, save_mean, save_rstd, running_mean, running_var, count);
+    launch_apply<false>(st, R, C, y, nullptr, save_mean, save_rstd, gamma, beta, nullptr, out);
     return check_launch("sph3d_elu_bn_forward_apply");
 }
 
@@ -431,18 +462,12 @@ extern "C" int sph3d_elu_bn_backward_sums(int R, int C, const float* y, const fl
                                           const float* save_rstd, float* dgamma, float* dbeta, double* sums,
                                           void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_backward_sums: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    SPH3D_REQUIRE(sums != nullptr, "elu_bn_backward_sums: sums is NULL");
-    const size_t need = sph3d_elu_bn_workspace(R, C);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("elu_bn_backward_sums: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
+    NormWorkspace ws;
+    if (int rc = norm_enter("sph3d_elu_bn_backward_sums", R, C, &ws, workspace, workspace_bytes)) return rc;
+    SPH3D_REQUIRE(sums != nullptr, "sph3d_elu_bn_backward_sums: sums is NULL");
     hipStream_t st = as_stream(stream);
-    float* partial = (float*)workspace;
-    const int nblk = norm_blocks(R);
-    hipLaunchKernelGGL(norm_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, R, C, y, dout, save_mean, save_rstd, partial);
-    hipLaunchKernelGGL(norm_bwd_sums, dim3((C + 31) / 32), dim3(32 * kFinLanes), 0, st, C, nblk, partial, dgamma, dbeta, sums);
+    launch_reduce<true>(st, R, C, ws, y, dout, save_mean, save_rstd);
+    launch_stats(norm_bwd_sums, true, C, st, C, ws.nblk, ws.partial, dgamma, dbeta, sums);
     return check_launch("sph3d_elu_bn_backward_sums");
 }
 
@@ -451,18 +476,11 @@ extern "C" int sph3d_elu_bn_backward_apply(int R, int C, const double* sums, con
                                            const float* gamma, const float* save_mean, const float* save_rstd, float* dy,
                                            void* workspace, size_t workspace_bytes, sph3d_stream_t stream)
 {
-    SPH3D_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && C <= 1024, "elu_bn_backward_apply: needs R>0, C%%4==0, C<=1024 (got R=%d C=%d)", R, C);
-    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "elu_bn_backward_apply: sums / count is NULL");
-    const size_t need = sph3d_elu_bn_workspace(R, C);
-    if (workspace == nullptr || workspace_bytes < need) {
-        set_error("elu_bn_backward_apply: workspace %zu B < required %zu B", workspace_bytes, need);
-        return SPH3D_EWORKSPACE;
-    }
+    NormWorkspace ws;
+    if (int rc = norm_enter("sph3d_elu_bn_backward_apply", R, C, &ws, workspace, workspace_bytes)) return rc;
+    SPH3D_REQUIRE(sums != nullptr && count != nullptr, "sph3d_elu_bn_backward_apply: sums / count is NULL");
     hipStream_t st = as_stream(stream);
-    float* coef = (float*)workspace + (size_t)norm_blocks(R) * 2 * C;
-    hipLaunchKernelGGL(norm_bwd_coef_from_sums, dim3((C + 255) / 256), dim3(256), 0, st, C, sums, count, coef);
-    const long long total4 = (long long)R * C / 4;
-    hipLaunchKernelGGL(norm_apply_kernel<true>, dim3((unsigned)norm_apply_blocks(total4)), dim3(256), 0, st, total4, C, y, dout,
-                       save_mean, save_rstd, gamma, nullptr, coef, dy);
+    launch_stats(norm_bwd_coef_from_sums, false, C, st, C, sums, count, ws.coef);
+    launch_apply<true>(st, R, C, y, dout, save_mean, save_rstd, gamma, nullptr, ws.coef, dy);
     return check_launch("sph3d_elu_bn_backward_apply");
 }

@@ -348,14 +348,9 @@ class _SeparableTrainFn(torch.autograd.Function):
     def forward(ctx, input, filter, weights, bias, gamma, beta, moving_mean, moving_var, nn_index, nn_count, bin_index):
         from . import tf_norm
         dw, y, partial = _separable_conv3d_train_impl(input, filter, weights, bias, nn_index, nn_count, bin_index)
-        Cout = y.shape[-1]
-        ctx.reducer = tf_norm.sync_reducer()          # statistics over all ranks' rows: the kernel's partials through the same cut
-        count = None
-        if ctx.reducer is not None:
-            out, save_mean, save_rstd, count = tf_norm._sync_fwd(ctx.reducer, y.view(-1, Cout), partial, gamma, beta, moving_mean,
-                                                                 moving_var)
-        else:
-            out, save_mean, save_rstd = tf_norm._elu_bn_partials_impl(y.view(-1, Cout), partial, gamma, beta, moving_mean, moving_var)
+        # (under a reducer, statistics over all ranks' rows: the kernel's partials go through the same cut)
+        out, (save_mean, save_rstd, count, ctx.reducer) = tf_norm.tail_forward(y.view(-1, y.shape[-1]), partial, gamma, beta,
+                                                                               moving_mean, moving_var, True)
         ctx.save_for_backward(input, filter, weights, dw, y, gamma, save_mean, save_rstd, nn_index, nn_count, bin_index, count)
         ctx.has_bias = bias is not None
         return out.view(y.shape)
@@ -365,11 +360,8 @@ class _SeparableTrainFn(torch.autograd.Function):
         from . import tf_gemm, tf_norm
         input, filter, weights, dw, y, gamma, save_mean, save_rstd, nn_index, nn_count, bin_index, count = ctx.saved_tensors
         Cout = y.shape[-1]
-        if ctx.reducer is not None:
-            dy, dgamma, dbeta = tf_norm._sync_bwd(ctx.reducer, y.view(-1, Cout), dout.reshape(-1, Cout), gamma, save_mean, save_rstd,
-                                                  count)
-        else:
-            dy, dgamma, dbeta = tf_norm._bwd_impl(y.view(-1, Cout), dout.reshape(-1, Cout), gamma, save_mean, save_rstd, True)
+        dy, dgamma, dbeta = tf_norm.tail_backward((save_mean, save_rstd, count, ctx.reducer), y.view(-1, Cout), dout.reshape(-1, Cout),
+                                                  gamma, True)
         ddw = tf_gemm._pointwise_gemm_impl(dy, weights, True).view(dw.shape)
         dweights = tf_gemm._pointwise_gemm_tn_impl(dw.view(-1, dw.shape[-1]), dy) if ctx.needs_input_grad[2] else None
         dbias = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[3]) else None

@@ -7,6 +7,7 @@ as ONE custom op (``sph3d::elu_bn``) whose backward needs only y.
 
 ``set_sync(reducer)`` / ``with sync(reducer):`` switch every training-mode batch norm of the layer functions to statistics over
 all ranks' rows: the ops are cut at the statistics, and ``reducer`` sums the cut's float64 buffer over the ranks.
+``tail_forward`` / ``tail_backward`` are the tail of every layer function, and the one place that chooses between the two.
 """
 import contextlib
 from typing import Optional, Tuple
@@ -17,6 +18,7 @@ from . import _lib
 
 MOMENTUM = 0.99       # tf.layers.batch_normalization(momentum=0.99): weight of the OLD moving statistics
 EPSILON = 1e-3        # TF default epsilon
+MAX_ROWS = 2 ** 31 - 1024      # csrc/norm.hip: kNormMaxRows, the most rows the statistics pass indexes in int
 
 
 def supported(C):
@@ -53,6 +55,32 @@ def sync(reducer):
         set_sync(prev)
 
 
+# ---- what every wrapper below does before its launch -------------------------------------------------------------------------------
+def _rows(op, y):
+    """y [..., C] -> y as contiguous float32 on the device, R, C.  More rows than the kernels index are a ValueError here: ctypes
+    would wrap R into the C ABI's int without a word."""
+    if not y.is_cuda:
+        _lib.require_device(y)
+    C = y.shape[-1]
+    R = y.numel() // C
+    if R > MAX_ROWS:
+        raise ValueError("%s: %d rows, at most %d" % (op, R, MAX_ROWS))
+    return _lib.f32(y), R, C
+
+
+def _on_device(t):
+    """another operand of y's kind (dout, partial) -> contiguous float32 on the device"""
+    if not t.is_cuda:
+        _lib.require_device(t)
+    return _lib.f32(t)
+
+
+def _workspace(R, C, device):
+    """-> the address and size of the call-local workspace of one C-ABI call"""
+    wsb = _lib.lib().sph3d_elu_bn_workspace(R, C)
+    return _lib.ptr(_lib.scratch(wsb, device)), wsb
+
+
 def _per_channel(op, C, names, *operands):
     """every per-channel operand of a launch: on the device, float32, contiguous, exactly [C].  The kernels take them as bare
     addresses and read C floats (write C floats into the moving statistics, which can therefore not be converted into a copy):
@@ -67,6 +95,13 @@ def _per_channel(op, C, names, *operands):
                                      % (op, name, C, str(t.dtype).replace("torch.", ""), list(t.shape), list(t.stride())))
 
 
+def _summed(op, name, t, n):
+    """a float64 buffer of the cut: on the device, contiguous, exactly [n]"""
+    _lib.require_device(t)
+    if t.dtype != torch.float64 or t.numel() != n or not t.is_contiguous():
+        raise ValueError("%s: %s should be a contiguous float64 [%d]" % (op, name, n))
+
+
 _F32, _UNIT = torch.float32, (1,)
 _FWD_NAMES = ("gamma", "beta", "moving_mean", "moving_var")
 _BWD_NAMES = ("gamma", "save_mean", "save_rstd")
@@ -74,37 +109,28 @@ _BWD_NAMES = ("gamma", "save_mean", "save_rstd")
 
 def _fwd_impl(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, moving_mean: torch.Tensor,
               moving_var: torch.Tensor, training: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    _lib.require_device(y)
-    y = _lib.f32(y)
-    C = y.shape[-1]
-    R = y.numel() // C
+    y, R, C = _rows("elu_bn", y)
     _per_channel("elu_bn", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
     save_mean, save_rstd = torch.empty_like(gamma), torch.empty_like(gamma)      # (gamma was just checked: float32 [C] on the device)
-    l = _lib.lib()
-    wsb = l.sph3d_elu_bn_workspace(R, C)
-    ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_forward(R, C, y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), moving_mean.data_ptr(),
-                                      moving_var.data_ptr(), 1.0 - MOMENTUM, EPSILON, 1 if training else 0, out.data_ptr(),
-                                      save_mean.data_ptr(), save_rstd.data_ptr(), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    ws, wsb = _workspace(R, C, y.device)
+    _lib.check(_lib.lib().sph3d_elu_bn_forward(R, C, y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), moving_mean.data_ptr(),
+                                                moving_var.data_ptr(), 1.0 - MOMENTUM, EPSILON, 1 if training else 0, out.data_ptr(),
+                                                save_mean.data_ptr(), save_rstd.data_ptr(), ws, wsb, _lib.stream_ptr()))
     return out, save_mean, save_rstd
 
 
 def _bwd_impl(y: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, save_mean: torch.Tensor,
               save_rstd: torch.Tensor, training: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    _lib.require_device(y, dout)
-    y, dout = _lib.f32(y), _lib.f32(dout)
-    C = y.shape[-1]
-    R = y.numel() // C
+    y, R, C = _rows("elu_bn_grad", y)
+    dout = _on_device(dout)
     _per_channel("elu_bn_grad", C, _BWD_NAMES, gamma, save_mean, save_rstd)
     dy = torch.empty_like(y)
     dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
-    l = _lib.lib()
-    wsb = l.sph3d_elu_bn_workspace(R, C)
-    ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_backward(R, C, y.data_ptr(), dout.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
-                                       save_rstd.data_ptr(), 1 if training else 0, dy.data_ptr(), dgamma.data_ptr(),
-                                       dbeta.data_ptr(), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    ws, wsb = _workspace(R, C, y.device)
+    _lib.check(_lib.lib().sph3d_elu_bn_backward(R, C, y.data_ptr(), dout.data_ptr(), gamma.data_ptr(), save_mean.data_ptr(),
+                                                 save_rstd.data_ptr(), 1 if training else 0, dy.data_ptr(), dgamma.data_ptr(),
+                                                 dbeta.data_ptr(), ws, wsb, _lib.stream_ptr()))
     return dy, dgamma, dbeta
 
 
@@ -126,23 +152,17 @@ def _(y, dout, gamma, save_mean, save_rstd, training):
 def elu_bn_forward_sums(y: torch.Tensor, partial: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> float64 [2C + 1]: per-channel sum elu(y), sum elu(y)^2 over this rank's rows, then the row count.  partial [nblk, 2, C]:
     the statistics' partial sums where a producer of y already wrote them (the GEMM's epilogue, the one-kernel separable layer)"""
-    _lib.require_device(y)
-    y = _lib.f32(y)
-    C = y.shape[-1]
-    R = y.numel() // C
+    y, R, C = _rows("elu_bn_forward_sums", y)
     sums = torch.empty((2 * C + 1,), dtype=torch.float64, device=y.device)
-    l = _lib.lib()
     if partial is None:
-        wsb = l.sph3d_elu_bn_workspace(R, C)
-        ws = _lib.scratch(wsb, y.device)
-        _lib.check(l.sph3d_elu_bn_forward_sums(R, C, 0, None, _lib.ptr(y), _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+        nblk, ws, wsb = 0, *_workspace(R, C, y.device)
     else:
-        _lib.require_device(partial)
-        partial = _lib.f32(partial)
+        partial = _on_device(partial)
         if partial.dim() != 3 or partial.shape[1] != 2 or partial.shape[2] != C or partial.shape[0] < 1:
             raise ValueError("elu_bn_forward_sums: partial should be [nblk >= 1, 2, %d]" % C)
-        _lib.check(l.sph3d_elu_bn_forward_sums(R, C, partial.shape[0], _lib.ptr(partial), _lib.ptr(y), _lib.ptr(sums), None, 0,
-                                               _lib.stream_ptr()))
+        nblk, ws, wsb = partial.shape[0], None, 0
+    _lib.check(_lib.lib().sph3d_elu_bn_forward_sums(R, C, nblk, _lib.ptr(partial), _lib.ptr(y), _lib.ptr(sums), ws, wsb,
+                                                     _lib.stream_ptr()))
     return sums
 
 
@@ -150,16 +170,11 @@ def elu_bn_forward_apply(y: torch.Tensor, sums: torch.Tensor, gamma: torch.Tenso
                          moving_var: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """sums: the [2C + 1] buffer summed over the ranks -> out, save_mean, save_rstd, count (float64 [1]: the global row count,
     kept on the device for elu_bn_backward_apply); updates the moving statistics"""
-    _lib.require_device(y, sums, gamma, beta, moving_mean, moving_var)
-    y = _lib.f32(y)
-    C = y.shape[-1]
-    R = y.numel() // C
-    if sums.dtype != torch.float64 or sums.numel() != 2 * C + 1 or not sums.is_contiguous():
-        raise ValueError("elu_bn_forward_apply: sums should be a contiguous float64 [%d]" % (2 * C + 1))
+    y, R, C = _rows("elu_bn_forward_apply", y)
+    _summed("elu_bn_forward_apply", "sums", sums, 2 * C + 1)
     _per_channel("elu_bn_forward_apply", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
-    save_mean = torch.empty((C,), dtype=torch.float32, device=y.device)
-    save_rstd = torch.empty((C,), dtype=torch.float32, device=y.device)
+    save_mean, save_rstd = torch.empty_like(gamma), torch.empty_like(gamma)
     count = torch.empty((1,), dtype=torch.float64, device=y.device)
     _lib.check(_lib.lib().sph3d_elu_bn_forward_apply(R, C, _lib.ptr(sums), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta),
                                                       _lib.ptr(moving_mean), _lib.ptr(moving_var), 1.0 - MOMENTUM, EPSILON,
@@ -172,41 +187,30 @@ def elu_bn_backward_sums(y: torch.Tensor, dout: torch.Tensor, save_mean: torch.T
                          save_rstd: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """-> dgamma, dbeta (this rank's sums, fp32: the gradient all-reduce adds the ranks') and float64 [2C]: per-channel
     sum dout, sum dout * zhat over this rank's rows"""
-    _lib.require_device(y, dout, save_mean, save_rstd)
-    y, dout = _lib.f32(y), _lib.f32(dout)
-    C = y.shape[-1]
-    R = y.numel() // C
+    y, R, C = _rows("elu_bn_backward_sums", y)
+    dout = _on_device(dout)
     _per_channel("elu_bn_backward_sums", C, _BWD_NAMES[1:], save_mean, save_rstd)
-    dgamma = torch.empty((C,), dtype=torch.float32, device=y.device)
-    dbeta = torch.empty((C,), dtype=torch.float32, device=y.device)
+    dgamma, dbeta = torch.empty_like(save_mean), torch.empty_like(save_mean)
     sums = torch.empty((2 * C,), dtype=torch.float64, device=y.device)
-    l = _lib.lib()
-    wsb = l.sph3d_elu_bn_workspace(R, C)
-    ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_backward_sums(R, C, _lib.ptr(y), _lib.ptr(dout), _lib.ptr(save_mean), _lib.ptr(save_rstd),
-                                            _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(sums), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+    ws, wsb = _workspace(R, C, y.device)
+    _lib.check(_lib.lib().sph3d_elu_bn_backward_sums(R, C, _lib.ptr(y), _lib.ptr(dout), _lib.ptr(save_mean), _lib.ptr(save_rstd),
+                                                      _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(sums), ws, wsb, _lib.stream_ptr()))
     return dgamma, dbeta, sums
 
 
 def elu_bn_backward_apply(y: torch.Tensor, dout: torch.Tensor, gamma: torch.Tensor, save_mean: torch.Tensor,
                           save_rstd: torch.Tensor, sums: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
     """sums: the [2C] buffer summed over the ranks; count: elu_bn_forward_apply's -> dy over this rank's rows"""
-    _lib.require_device(y, dout, gamma, save_mean, save_rstd, sums, count)
-    y, dout = _lib.f32(y), _lib.f32(dout)
-    C = y.shape[-1]
-    R = y.numel() // C
-    if sums.dtype != torch.float64 or sums.numel() != 2 * C or not sums.is_contiguous():
-        raise ValueError("elu_bn_backward_apply: sums should be a contiguous float64 [%d]" % (2 * C))
-    if count.dtype != torch.float64 or count.numel() != 1:
-        raise ValueError("elu_bn_backward_apply: count should be a float64 [1]")
+    y, R, C = _rows("elu_bn_backward_apply", y)
+    dout = _on_device(dout)
+    _summed("elu_bn_backward_apply", "sums", sums, 2 * C)
+    _summed("elu_bn_backward_apply", "count", count, 1)
     _per_channel("elu_bn_backward_apply", C, _BWD_NAMES, gamma, save_mean, save_rstd)
     dy = torch.empty_like(y)
-    l = _lib.lib()
-    wsb = l.sph3d_elu_bn_workspace(R, C)
-    ws = _lib.scratch(wsb, y.device)
-    _lib.check(l.sph3d_elu_bn_backward_apply(R, C, _lib.ptr(sums), _lib.ptr(count), _lib.ptr(y), _lib.ptr(dout), _lib.ptr(gamma),
-                                             _lib.ptr(save_mean), _lib.ptr(save_rstd), _lib.ptr(dy), _lib.ptr(ws), wsb,
-                                             _lib.stream_ptr()))
+    ws, wsb = _workspace(R, C, y.device)
+    _lib.check(_lib.lib().sph3d_elu_bn_backward_apply(R, C, _lib.ptr(sums), _lib.ptr(count), _lib.ptr(y), _lib.ptr(dout),
+                                                       _lib.ptr(gamma), _lib.ptr(save_mean), _lib.ptr(save_rstd), _lib.ptr(dy), ws, wsb,
+                                                       _lib.stream_ptr()))
     return dy
 
 
@@ -236,14 +240,29 @@ def _(y, dout, gamma, save_mean, save_rstd, sums, count):
     return torch.empty_like(y)
 
 
-def _sync_fwd(reducer, y, partial, gamma, beta, moving_mean, moving_var):
-    """training-mode forward over all ranks' rows: sums -> reducer -> apply"""
-    sums = elu_bn_forward_sums(y, partial)
-    reducer(sums)
-    return elu_bn_forward_apply(y, sums, gamma, beta, moving_mean, moving_var)
+# ---- the tail of every layer function: the one place that asks whether a reducer is set ------------------------------------------
+def tail_forward(y, partial, gamma, beta, moving_mean, moving_var, training):
+    """out = batch_norm(elu(y)).  partial: the statistics' partial sums [nblk, 2, C] where the producer of y wrote them (training
+    mode only), else None: the statistics pass over y runs.  -> out, saved = (save_mean, save_rstd, count, reducer), what
+    tail_backward needs: count (float64 [1], the global row count) and reducer are None unless a reducer was in force."""
+    reducer = _sync if training else None
+    count = None
+    if reducer is not None:
+        sums = elu_bn_forward_sums(y, partial)
+        reducer(sums)
+        out, save_mean, save_rstd, count = elu_bn_forward_apply(y, sums, gamma, beta, moving_mean, moving_var)
+    elif partial is not None:
+        out, save_mean, save_rstd = _elu_bn_partials_impl(y, partial, gamma, beta, moving_mean, moving_var)
+    else:
+        out, save_mean, save_rstd = _fwd_impl(y, gamma, beta, moving_mean, moving_var, training)
+    return out, (save_mean, save_rstd, count, reducer)
 
 
-def _sync_bwd(reducer, y, dout, gamma, save_mean, save_rstd, count):
+def tail_backward(saved, y, dout, gamma, training):
+    """saved: tail_forward's -> dy, dgamma, dbeta"""
+    save_mean, save_rstd, count, reducer = saved
+    if reducer is None:
+        return _bwd_impl(y, dout, gamma, save_mean, save_rstd, training)
     dgamma, dbeta, sums = elu_bn_backward_sums(y, dout, save_mean, save_rstd)
     reducer(sums)
     return elu_bn_backward_apply(y, dout, gamma, save_mean, save_rstd, sums, count), dgamma, dbeta
@@ -256,12 +275,7 @@ def _sync_bwd(reducer, y, dout, gamma, save_mean, save_rstd, count):
 class _EluBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, moving_mean, moving_var, training):
-        ctx.reducer = _sync if training else None
-        count = None
-        if ctx.reducer is not None:
-            out, save_mean, save_rstd, count = _sync_fwd(ctx.reducer, y, None, gamma, beta, moving_mean, moving_var)
-        else:
-            out, save_mean, save_rstd = _fwd_impl(y, gamma, beta, moving_mean, moving_var, training)
+        out, (save_mean, save_rstd, count, ctx.reducer) = tail_forward(y, None, gamma, beta, moving_mean, moving_var, training)
         ctx.save_for_backward(y, gamma, save_mean, save_rstd, count)
         ctx.training = training
         return out
@@ -269,10 +283,7 @@ class _EluBnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         y, gamma, save_mean, save_rstd, count = ctx.saved_tensors
-        if ctx.reducer is not None:
-            dy, dgamma, dbeta = _sync_bwd(ctx.reducer, y, dout, gamma, save_mean, save_rstd, count)
-        else:
-            dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, ctx.training)
+        dy, dgamma, dbeta = tail_backward((save_mean, save_rstd, count, ctx.reducer), y, dout, gamma, ctx.training)
         return dy, dgamma, dbeta, None, None, None
 
 
@@ -307,10 +318,8 @@ def _gemm_bnstats_impl(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Te
 def _elu_bn_partials_impl(y: torch.Tensor, partial: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
                           moving_mean: torch.Tensor, moving_var: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """training-mode elu_bn whose statistics come from `partial` instead of a pass over y"""
-    _lib.require_device(y, partial)
-    y, partial = _lib.f32(y), _lib.f32(partial)
-    C = y.shape[-1]
-    R = y.numel() // C
+    y, R, C = _rows("elu_bn_partials", y)
+    partial = _on_device(partial)
     _per_channel("elu_bn_partials", C, _FWD_NAMES, gamma, beta, moving_mean, moving_var)
     out = torch.empty_like(y)
     save_mean, save_rstd = torch.empty_like(gamma), torch.empty_like(gamma)
@@ -343,12 +352,7 @@ class _GemmEluBnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, gamma, beta, moving_mean, moving_var):
         y, partial = _gemm_bnstats_impl(x, w, bias)
-        ctx.reducer = _sync
-        count = None
-        if ctx.reducer is not None:
-            out, save_mean, save_rstd, count = _sync_fwd(ctx.reducer, y, partial, gamma, beta, moving_mean, moving_var)
-        else:
-            out, save_mean, save_rstd = _elu_bn_partials_impl(y, partial, gamma, beta, moving_mean, moving_var)
+        out, (save_mean, save_rstd, count, ctx.reducer) = tail_forward(y, partial, gamma, beta, moving_mean, moving_var, True)
         ctx.save_for_backward(x, w, y, gamma, save_mean, save_rstd, count)
         ctx.has_bias = bias is not None
         return out
@@ -357,10 +361,7 @@ class _GemmEluBnFn(torch.autograd.Function):
     def backward(ctx, dout):
         from . import tf_gemm
         x, w, y, gamma, save_mean, save_rstd, count = ctx.saved_tensors
-        if ctx.reducer is not None:
-            dy, dgamma, dbeta = _sync_bwd(ctx.reducer, y, dout, gamma, save_mean, save_rstd, count)
-        else:
-            dy, dgamma, dbeta = _bwd_impl(y, dout, gamma, save_mean, save_rstd, True)
+        dy, dgamma, dbeta = tail_backward((save_mean, save_rstd, count, ctx.reducer), y, dout, gamma, True)
         dx = tf_gemm._pointwise_gemm_impl(dy, w, True) if ctx.needs_input_grad[0] else None
         dw = tf_gemm._pointwise_gemm_tn_impl(x, dy) if ctx.needs_input_grad[1] else None
         db = dy.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None

@@ -1,5 +1,5 @@
 """The ELU + batch-norm tail (csrc/norm.hip), restated:
-  * the launch arithmetic of norm.hip in plain Python, each line with the source line it restates;
+  * the launch arithmetic of norm.hip in plain Python, each line with the function and the variable it restates;
   * FORM_CASES / FORMS: the smallest shape that reaches each distinct launch form, with the predicate that names the form;
   * float64 numpy statements of every quantity the seven entry points leave behind;
   * a float32 numpy restatement of each kernel in the kernel's own operation order, which entitles the bounds to be used on the
@@ -25,10 +25,10 @@ backward sums, at the float32 mean / rstd the kernel was given, zhat = (z - mean
     |Sd_k - Sd|   <= n u sum|dout|
     |Sdz_k - Sdz| <= n u (sum|dout zhat| + W) + W,   W = sum |dout| Z
     dgamma / dbeta are one float32 rounding of the float64 sums: + u |value|.
-statistics from sums: the float64 expressions of norm.hip:203-210 evaluated here, one float32 rounding: u |value| (+ 2^-149).
+statistics from sums: the float64 expressions of norm_fwd_stats evaluated here, one float32 rounding: u |value| (+ 2^-149).
 apply, forward, per element, against the float64 formula AT THE KERNEL'S OWN float32 mean and rstd:
     o = fma(fl(fl(z_k - mean) rstd), gamma, beta):   (E + 3u |z - mean|) rstd |gamma| + u |out|
-apply, backward, per element, at the kernel's float32 statistics and float32 coef (norm.hip:279-282), T = |dout| + |c0| + |zhat c1|:
+apply, backward, per element, at the kernel's float32 statistics and float32 coef (SPH3D_BN_BWD), T = |dout| + |c0| + |zhat c1|:
     inner = fl(fl(dout - c0) - fl(zhat_k c1)): Z |c1| + 3u T;   dz = fl(fl(gamma rstd) inner): |gamma| rstd (Z |c1| + 5u T)
     y <= 0: elu' = fl(z_k + 1) is off by E + u/2, and the product rounds once more:
     |dy_k - dy| <= |gamma| rstd ((Z |c1| + 5u T) + [y <= 0] T (E + u/2)) + u |dy|
@@ -57,61 +57,62 @@ def _cdiv(a, b):
 
 
 # ---- csrc/norm.hip: launch arithmetic --------------------------------------------------------------------------------------------
-K_NORM_MAX_BLOCKS = 1024             # norm.hip:18   kNormMaxBlocks
-K_FIN_LANES = 32                     # norm.hip:91   kFinLanes
-K_FIN_UN = 8                         # norm.hip:100  UN of sum_partials_32x8
-K_REDUCE_UN = 4                      # norm.hip:45   UN of norm_reduce_kernel
-K_APPLY_MAX_BLOCKS = 4096            # norm.hip:330, :384
+K_NORM_MAX_BLOCKS = 1024             # kNormMaxBlocks
+K_FIN_LANES = 32                     # kFinLanes
+K_FIN_UN = 8                         # UN of sum_partials_32x8
+K_REDUCE_UN = 4                      # UN of norm_reduce_kernel
+K_APPLY_MAX_BLOCKS = 4096            # launch_apply: the cap of the grid
+MAX_ROWS = 2 ** 31 - 1024            # kNormMaxRows: R + 1023 is the largest int norm_reduce_kernel forms
 
 
 def supported(R, C):
-    """SPH3D_REQUIRE of every entry point, norm.hip:310"""
-    return R > 0 and C > 0 and C % 4 == 0 and C <= 1024
+    """norm_enter: the dimension check of every entry point"""
+    return 0 < R <= MAX_ROWS and C > 0 and C % 4 == 0 and C <= 1024
 
 
 def norm_blocks(R):
-    """norm.hip:292"""
+    """norm_blocks"""
     return max(1, min(K_NORM_MAX_BLOCKS, _cdiv(R, 32)))
 
 
 def workspace_bytes(R, C):
-    """sph3d_elu_bn_workspace, norm.hip:300: the partials [nblk][2][C] and coef [2][C]"""
+    """sph3d_elu_bn_workspace (NormWorkspace): the partials [nblk][2][C] and coef [2][C]"""
     return 4 * (norm_blocks(R) * 2 * C + 2 * C)
 
 
 def finalize_form(nblk, C):
-    """sum_partials_32x8, norm.hip:101-113, and the finalize grids, norm.hip:321"""
-    return dict(fin_trips=_cdiv(nblk, K_FIN_LANES * K_FIN_UN),                  # :101  k0 = py; k0 < nblk; k0 += 256 (py = 0)
-                fin_idle_py=max(0, K_FIN_LANES - nblk),                         # :101  lanes with py >= nblk never enter
-                fin_ragged=nblk % (K_FIN_LANES * K_FIN_UN) != 0,                # :106  some k >= nblk in the last trip: clamped
-                fin_idle_lanes=_cdiv(C, 32) * 32 - C)                           # :133, :137  c >= C in the last workgroup
+    """sum_partials_32x8: the loop over k0, and the finalize grids (launch_stats)"""
+    return dict(fin_trips=_cdiv(nblk, K_FIN_LANES * K_FIN_UN),                  # k0 = py; k0 < nblk; k0 += 256 (py = 0)
+                fin_idle_py=max(0, K_FIN_LANES - nblk),                         # lanes with py >= nblk never enter
+                fin_ragged=nblk % (K_FIN_LANES * K_FIN_UN) != 0,                # kc: some k >= nblk in the last trip: clamped
+                fin_idle_lanes=_cdiv(C, 32) * 32 - C)                           # c >= C in the last workgroup of a finalize kernel
 
 
 def reduce_form(R, C):
-    """norm_reduce_kernel, norm.hip:29-35, :46-57, :76-77"""
-    nblk = norm_blocks(R)                                                       # :318
-    cg = C >> 2                                                                 # :29
-    rpi = max(1, 256 // cg)                                                     # :30   rows_per_iter
-    rpb = _cdiv(R, nblk)                                                        # :33   rows_per_block
-    used = _cdiv(R, rpb)                                                        # :34   blocks with r0 < R
-    f = dict(nblk=nblk, cg=cg, rows_per_iter=rpi, idle_threads=256 - cg * rpi,  # :32   ty >= rows_per_iter
+    """norm_reduce_kernel: its row ranges, its row loop and its fold"""
+    nblk = norm_blocks(R)                                                       # norm_enter: ws->nblk
+    cg = C >> 2                                                                 # cg
+    rpi = max(1, 256 // cg)                                                     # rows_per_iter
+    rpb = _cdiv(R, nblk)                                                        # rows_per_block
+    used = _cdiv(R, rpb)                                                        # r0: blocks with r0 < R
+    f = dict(nblk=nblk, cg=cg, rows_per_iter=rpi, idle_threads=256 - cg * rpi,  # act: ty >= rows_per_iter
              rows_per_block=rpb, used=used, empty=nblk - used,
-             last_rows=R - (used - 1) * rpb,                                    # :35   r1 = min(r0 + rows_per_block, R)
-             chain=_cdiv(rpb, rpi),                                             # :46   rb = r0 + ty; rb < r1; rows_per_iter apart
-             fold=min(rpi, rpb))                                                # :77   the ty that hold a row
+             last_rows=R - (used - 1) * rpb,                                    # r1 = min(r0 + rows_per_block, R)
+             chain=_cdiv(rpb, rpi),                                             # rb = r0 + ty; rb < r1; rows_per_iter apart
+             fold=min(rpi, rpb))                                                # the fold: the ty that hold a row
     f.update(finalize_form(nblk, C))
     return f
 
 
 def apply_form(R, C):
-    """the apply launches, norm.hip:328-331, and norm_apply_kernel, norm.hip:251-261"""
-    total4 = R * C // 4                                                         # :328
-    blocks = min(K_APPLY_MAX_BLOCKS, _cdiv(total4, 256))                        # :329-330
-    stride = blocks * 256                                                       # :251
-    return dict(total4=total4, blocks=blocks, stride=stride, trips=_cdiv(total4, stride),          # :258
-                cstep=stride % (C >> 2),                                        # :257
-                last_trip=total4 - (_cdiv(total4, stride) - 1) * stride,        # :258  float4 of the last trip
-                tail=total4 % 256)                                              # :258  threads of the last workgroup with work
+    """the apply launches (launch_apply) and norm_apply_kernel's loop"""
+    total4 = R * C // 4                                                         # launch_apply: total4
+    blocks = min(K_APPLY_MAX_BLOCKS, _cdiv(total4, 256))                        # launch_apply: blocks
+    stride = blocks * 256                                                       # stride
+    return dict(total4=total4, blocks=blocks, stride=stride, trips=_cdiv(total4, stride),          # i < total4
+                cstep=stride % (C >> 2),                                        # cstep
+                last_trip=total4 - (_cdiv(total4, stride) - 1) * stride,        # float4 of the last trip
+                tail=total4 % 256)                                              # threads of the last workgroup with work
 
 
 def case_form(R, C):
@@ -256,23 +257,23 @@ def fwd_sums_bound(ref, form):
 
 
 def stats_from_sums(sums, mm_old=None, mv_old=None):
-    """norm_fwd_stats_from_sums, norm.hip:202-212 (= norm_fwd_finalize :138-146), in float64: -> dict of float64 values BEFORE the
+    """norm_fwd_stats, as norm_fwd_stats_from_sums and norm_fwd_finalize call it, in float64: -> dict of float64 values BEFORE the
     float32 rounding (mean, var, rstd, moving_mean, moving_var, count)"""
     sums = f64(sums)
     C = (len(sums) - 1) // 2
     R = sums[2 * C]
-    m = sums[:C] / R                                                            # :203
-    var = np.maximum(sums[C:2 * C] / R - m * m, 0.0)                            # :204-205
-    out = dict(mean=m, var=var, rstd=1.0 / np.sqrt(var + np.float64(EPS)), count=R)           # :206-207
+    m = sums[:C] / R                                                            # m
+    var = np.maximum(sums[C:2 * C] / R - m * m, 0.0)                            # var, clamped
+    out = dict(mean=m, var=var, rstd=1.0 / np.sqrt(var + np.float64(EPS)), count=R)           # mean, rstd
     if mm_old is not None:
         mom = np.float64(MOM)
-        out["moving_mean"] = (1.0 - mom) * f64(mm_old) + mom * m                # :209
-        out["moving_var"] = (1.0 - mom) * f64(mv_old) + mom * var               # :210
+        out["moving_mean"] = (1.0 - mom) * f64(mm_old) + mom * m                # run_mean
+        out["moving_var"] = (1.0 - mom) * f64(mv_old) + mom * var               # run_var
     return out
 
 
 def eval_stats(mm, mv):
-    """norm_eval_stats, norm.hip:155-156 -> float32 save_mean (a copy), float64 rstd before its rounding"""
+    """norm_eval_stats -> float32 save_mean (a copy), float64 rstd before its rounding"""
     return np.asarray(mm, np.float32).copy(), 1.0 / np.sqrt(f64(mv) + np.float64(EPS))
 
 
@@ -398,7 +399,7 @@ F32 = np.float32
 
 
 def elu32(y):
-    """elu1, common.hpp:171, with numpy's float32 exp standing in for __expf"""
+    """elu1 (common.hpp), with numpy's float32 exp standing in for __expf"""
     y = np.asarray(y, F32)
     return np.where(y > 0, y, np.exp(np.minimum(y, F32(0))) - F32(1)).astype(F32)
 
@@ -409,16 +410,16 @@ def fma32(a, b, c):
 
 
 def reduce_f32(form, y, dout=None, mean=None, rstd=None, mutate=None):
-    """norm_reduce_kernel<BWD = dout is not None>, norm.hip:36-85 -> partial [nblk, 2, C] float32.  Per ty a chain over the rows
-    r0 + ty + k rows_per_iter, four per trip (:46-57), the squares by fmaf (:61); then the fold of the ty in order (:77-81)."""
+    """norm_reduce_kernel<BWD = dout is not None> -> partial [nblk, 2, C] float32.  Per ty a chain over the rows
+    r0 + ty + k rows_per_iter, four per trip (the loop over rb), the squares by fmaf; then the fold of the ty in order."""
     R, C = y.shape
     nblk, rpb, rpi = form["nblk"], form["rows_per_block"], form["rows_per_iter"]
     K = K_REDUCE_UN * _cdiv(form["chain"], K_REDUCE_UN)
-    nrows = np.clip(R - np.arange(nblk) * rpb, 0, rpb)                       # :34-35
+    nrows = np.clip(R - np.arange(nblk) * rpb, 0, rpb)                       # r0, r1
     if mutate == REDUCE_MUTATIONS[0]:
         nrows = np.maximum(nrows - 1, 0)
     local = np.arange(K * rpi).reshape(K, rpi)                                # row k rows_per_iter + ty of the block
-    valid = local[None] < nrows[:, None, None]                                # :57   [nblk, K, rpi]
+    valid = local[None] < nrows[:, None, None]                                # rb + u * rows_per_iter < r1   [nblk, K, rpi]
     idx = np.minimum(np.arange(nblk)[:, None, None] * rpb + local[None], R - 1)
     bwd = dout is not None
     a = np.zeros((nblk, rpi, C), F32)
@@ -426,7 +427,7 @@ def reduce_f32(form, y, dout=None, mean=None, rstd=None, mutate=None):
     for k in range(K):
         k0 = k - k % K_REDUCE_UN
         m, rows = valid[:, k], idx[:, k]
-        if mutate == REDUCE_MUTATIONS[1]:                                     # :51 without :57
+        if mutate == REDUCE_MUTATIONS[1]:                                     # the clamp rc without the mask
             rows = np.where(m, rows, idx[:, k0])
             m = valid[:, k0]
         if not m.any():
@@ -452,7 +453,7 @@ def reduce_f32(form, y, dout=None, mean=None, rstd=None, mutate=None):
 
 
 def sum_partials(partial):
-    """sum_partials_32x8, norm.hip:96-122: per lane py the partials py, py + 32, ... in order, then the 32 lanes in order, all in
+    """sum_partials_32x8: per lane py the partials py, py + 32, ... in order, then the 32 lanes in order, all in
     double -> float64 [2, C].  (numpy's float64 additions are the device's: this is the kernel's result bit for bit.)"""
     nblk = partial.shape[0]
     T = _cdiv(nblk, K_FIN_LANES)
@@ -482,20 +483,20 @@ def stats_f32(sums, mm, mv):
 
 
 def channel_of(form, C, mutate=None):
-    """the channel group norm_apply_kernel uses for every float4, norm.hip:255-261 -> int [total4]; cg and beyond: out of range"""
+    """the channel group norm_apply_kernel carries (cq) for every float4 -> int [total4]; cg and beyond: out of range"""
     total4, stride, cg, cstep = form["total4"], form["stride"], C >> 2, form["cstep"]
-    cq = np.arange(min(stride, total4)) % cg                                  # :256
+    cq = np.arange(min(stride, total4)) % cg                                  # cq = i0 % cg
     out = np.empty(total4, np.int64)
     for t in range(form["trips"]):
         n = min(stride, total4 - t * stride)
-        out[t * stride:t * stride + n] = cq[:n]                               # :259
-        cq = cq + cstep                                                       # :260
+        out[t * stride:t * stride + n] = cq[:n]                               # c = cq * 4
+        cq = cq + cstep                                                       # cq += cstep
         if mutate == APPLY_MUTATIONS[0]:
             pass
         elif mutate == APPLY_MUTATIONS[1]:
             cq = np.where(cq > cg, cq - cg, cq)
         else:
-            cq = np.where(cq >= cg, cq - cg, cq)                              # :261
+            cq = np.where(cq >= cg, cq - cg, cq)                              # the wrap
     return out
 
 
@@ -508,14 +509,14 @@ def _per_element(form, C, v, mutate):
 
 
 def apply_fwd_f32(form, y, mean, rstd, gamma, beta, mutate=None):
-    """norm_apply_kernel<false>, norm.hip:269"""
+    """norm_apply_kernel<false>"""
     C = y.shape[1]
     mu, rs, ga, be = (_per_element(form, C, v, mutate) for v in (mean, rstd, gamma, beta))
     return fma32((elu32(y) - mu) * rs, ga, be)
 
 
 def apply_bwd_f32(form, y, dout, gamma, mean, rstd, c0, c1, mutate=None):
-    """norm_apply_kernel<true>, norm.hip:279-282"""
+    """norm_apply_kernel<true>: SPH3D_BN_BWD"""
     C = y.shape[1]
     mu, rs, ga, k0, k1 = (_per_element(form, C, v, mutate) for v in (mean, rstd, gamma, c0, c1))
     z = elu32(y)
@@ -556,7 +557,7 @@ def check_bwd_sums(dgamma, dbeta, sums, y, dout, mean, rstd, form):
 
 
 def coef32(sums, count):
-    """norm_bwd_coef_from_sums, norm.hip:238-239 -> float32 c0, c1"""
+    """norm_bwd_coef, as norm_bwd_coef_from_sums calls it -> float32 c0, c1"""
     C = len(sums) // 2
     c = (f64(sums) / float(count)).astype(F32)
     return c[:C], c[C:]

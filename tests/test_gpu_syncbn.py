@@ -305,6 +305,92 @@ def test_separable_layer_virtual_ranks(dev, fuse):
     _compare_layer(ranks, whole)
 
 
+# ---- the three tails, each plain and under a one-rank reducer ---------------------------------------------------------------------
+def _tail_elu_batch_norm(dev):
+    C = 12
+    y, gamma, beta, dout = _case(C, (33,), dev)
+
+    def run():
+        y1, g1, b1 = (t.clone().requires_grad_(True) for t in (y, gamma, beta))
+        mm, mv = _buffers(C, dev)
+        out = tf_norm.elu_batch_norm(y1, g1, b1, mm, mv, True)
+        out.backward(dout)
+        return [out.detach(), mm, mv, y1.grad, g1.grad, b1.grad]
+
+    return C, run
+
+
+def _tail_gemm_elu_batch_norm(dev):
+    R, Cin, C = 1024, 64, 128                                 # tests/test_gpu_round3.py: test_gemm_bnstats_ops_registered
+    g = torch.Generator(device="cpu").manual_seed(R + Cin)
+    x = (torch.randn(R, Cin, generator=g) * 0.5).to(dev)
+    w = (torch.randn(Cin, C, generator=g) / Cin ** 0.5).to(dev)
+    gamma = (1.0 + 0.1 * torch.randn(C, generator=g)).to(dev)
+    beta = (0.1 * torch.randn(C, generator=g)).to(dev)
+    dout = torch.randn(R, C, generator=g).to(dev)
+
+    def run():
+        xs, ws, gs, bs = (t.clone().requires_grad_(True) for t in (x, w, gamma, beta))
+        mm, mv = _buffers(C, dev)
+        out = tf_norm.gemm_elu_batch_norm(xs, ws, gs, bs, mm, mv)
+        out.backward(dout)
+        return [out.detach(), mm, mv, xs.grad, ws.grad, gs.grad, bs.grad]
+
+    return C, run
+
+
+def _tail_separable(dev):
+    from sph3d_gcn_amd import tf_buildkernel, tf_conv3d, tf_nnquery
+    kind, B, N, M, radius, K, kernel, Cin, r, C = ("uniform", 1, 64, 40, 0.3, 16, [8, 2, 2], 128, 2, 128)      # tests/test_gpu_sepring.py
+    xyz = torch.from_numpy(synth.uniform_cloud(7, B, N, 1.0).copy()).to(dev)
+    q = xyz[:, :M].contiguous()
+    idx, cnt, dst = tf_nnquery.build_sphere_neighbor(xyz, q, radius, None, K)
+    filt = tf_buildkernel.spherical_kernel(xyz, q, idx, cnt, dst, radius, kernel)
+    F = kernel[0] * kernel[1] * kernel[2] + 1
+    g = torch.Generator(device="cpu").manual_seed(Cin * 7 + C)
+    x = torch.randn(B, N, Cin, generator=g).to(dev)
+    dwf = torch.randn(F, Cin, r, generator=g).to(dev)
+    w = (torch.randn(Cin * r, C, generator=g) / (Cin * r) ** 0.5).to(dev)
+    bias = torch.randn(C, generator=g).to(dev)
+    gamma = (1.0 + 0.1 * torch.randn(C, generator=g)).to(dev)
+    beta = (0.1 * torch.randn(C, generator=g)).to(dev)
+    dout = torch.randn(B, M, C, generator=g).to(dev)
+    assert tf_conv3d.separable_train_supported(x, dwf, idx, C)
+
+    def run():
+        xs, fs, ws, cs, gs, bs = (t.clone().requires_grad_(True) for t in (x, dwf, w, bias, gamma, beta))
+        mm, mv = _buffers(C, dev)
+        out = tf_conv3d.separable_conv3d_elu_bn_train(xs, fs, ws, gs, bs, mm, mv, idx, cnt, filt, bias=cs)
+        out.backward(dout)
+        torch.cuda.synchronize()
+        assert _lib.lib().sph3d_separable_conv3d_ring_failures() == 0
+        return [out.detach(), mm, mv, xs.grad, fs.grad, ws.grad, cs.grad, gs.grad, bs.grad]
+
+    return C, run
+
+
+@pytest.mark.parametrize("tail", [_tail_elu_batch_norm, _tail_gemm_elu_batch_norm, _tail_separable],
+                         ids=["elu_batch_norm", "gemm_elu_batch_norm", "separable_conv3d_elu_bn_train"])
+def test_every_tail_under_a_one_rank_reducer_is_the_plain_tail_bit_for_bit(dev, tail):
+    """the reducer of one rank leaves the buffer as it is: it is called once per forward pass with 2C + 1 values and once per backward
+    pass with 2C, and out, both moving statistics and every gradient carry the bits of the call without a reducer"""
+    C, run = tail(dev)
+    calls = []
+
+    def one_rank(buf):
+        assert buf.dtype == torch.float64 and buf.dim() == 1 and buf.is_cuda
+        calls.append(buf.numel())
+
+    plain = run()
+    assert calls == []
+    with tf_norm.sync(one_rank):
+        synced = run()
+    assert calls == [2 * C + 1, 2 * C]
+    assert len(plain) == len(synced) >= 6                      # out, two moving statistics, at least three gradients
+    for i, (a, b) in enumerate(zip(plain, synced)):
+        assert a is not None and torch.equal(a, b), "result %d differs" % i
+
+
 # ---- the registered ops ----------------------------------------------------------------------------------------------------------
 def test_sync_ops_registered(dev):
     checks = ("test_schema", "test_faketensor")
