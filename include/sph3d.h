@@ -1291,6 +1291,41 @@ int sph3d_lovasz_softmax(int B, int N, int C, const float* logits, const long lo
                          float* probs, float* coef, float* class_loss, float* loss, float* dlogits, int* order,
                          sph3d_stream_t stream);
 
+/* the same loss for blocks of up to 2^20 rows: the sort runs in global memory (csrc/lovasz.hip; the host's choices are
+ * csrc/lovasz_plan.hpp's).  The statement, the arguments and the outputs are sph3d_lovasz_softmax's, word for word, `order`
+ * included; scope "batch" of the Python surface is this entry on the call reshaped to one block of B N rows.
+ *   keys      as sph3d_lovasz_softmax: bits(e) | ~n | fg per valid row, 0 otherwise; runs of `tile` keys are sorted in LDS, then
+ *             merged pairwise in ceil(log2(runs)) launches (merge path, 1024 output keys per workgroup).  Valid keys are distinct,
+ *             so the sorted order is the statement's order exactly
+ *   probs, order, coef   the bits sph3d_lovasz_softmax writes wherever both entries cover the shape (g, U, F: the same integers
+ *             and the same fp32 operations)
+ *   class_loss  sum_j e_(j) g_j in this tree: the 1024 positions of a tile by the 6-step butterfly over a wave's lanes, then the
+ *             16 waves in order onto 0.f; the tiles t = l, l + 64, ... in order onto 0.f in lane l of one wave; the 64 lanes by
+ *             the 6-step butterfly.  Longest path: 6 + 15 + (ceil(tiles / 64) - 1) + 6 additions, tiles = ceil(N / tile) tile / 1024
+ *   loss, dlogits   as sph3d_lovasz_softmax
+ * Classes pass through the sort `slab` at a time, so the workspace holds slab B segments of keys (twice), not C B; the counts
+ * G[b,c] are integers, the float reductions run in the fixed order above: the same inputs give the same bits on every run and
+ * for every slab.  No float atomics; no workgroup waits for another.
+ * tile_log2: 0 (the default, 12: 4096 keys, 32 KB of LDS) or 10..14; slab: 0 (the plan's choice: as many classes as keep the
+ * workspace under 128 MB, at least one) or 1..C.  Both exist for tests: forced values reach every merge shape at small N.
+ * workspace: sph3d_lovasz_softmax_large_workspace(B, N, C) bytes (for tile_log2 = slab = 0; a forced call asks the plan), 16-byte
+ * aligned, dead when the call's last kernel has run.  sph3d_lovasz_softmax_large_plan writes SPH3D_LOVASZ_PLAN_FIELDS values:
+ *   tile_log2, tile, runs, npad, passes, mtile, mtiles, slab, slabs, probs_grid, count_grid, sort_lds, merge_lds, grad_grid,
+ *   key_bufs, workspace_bytes, off_keys0, off_keys1, off_tilecnt, off_partial, off_count, off_bad, cap
+ * (csrc/lovasz_plan.hpp: LovaszPlan says what each is; all 0 for B == 0).
+ * N <= 2^20 and C <= 1024: sph3d_lovasz_softmax_large_supported(N, C) -> 1 | 0 on the host.
+ * -> SPH3D_OK; SPH3D_EINVAL for B < 0, N <= 0, C <= 0, B N C > 2^40, B C >= 2^31, B >= 2^16; SPH3D_EUNSUPPORTED for N > 2^20 or
+ * C > 1024; SPH3D_EINVAL for a tile_log2 or slab outside the above, in this order and before the pointers are looked at; then
+ * SPH3D_EINVAL for a null pointer other than inner, dlogits and order, SPH3D_EWORKSPACE for a workspace that is null, too small
+ * or not aligned. */
+#define SPH3D_LOVASZ_PLAN_FIELDS 23
+int sph3d_lovasz_softmax_large_supported(int N, int C);
+size_t sph3d_lovasz_softmax_large_workspace(int B, int N, int C);
+int sph3d_lovasz_softmax_large_plan(int B, int N, int C, int tile_log2, int slab, long long* out);
+int sph3d_lovasz_softmax_large(int B, int N, int C, const float* logits, const long long* label, const float* inner,
+                               long long ignore, float* probs, float* coef, float* class_loss, float* loss, float* dlogits,
+                               int* order, void* workspace, size_t workspace_bytes, int tile_log2, int slab, sph3d_stream_t stream);
+
 /* softmax cross-entropy with class weights, label smoothing and an ignore label, per block, and its gradient with respect to the
  * logits (csrc/xent.hip; the float64 statement is harness/xent.py: xent_reference).  It is not an op of the reference tree.
  * logits [B,N,C] fp32; label [B,N] int32 (label_bits = 32, as the feeds yield them) or int64 (label_bits = 64); inner [B,N] fp32 or

@@ -110,6 +110,10 @@ SIGNATURES = {
     "sph3d_masked_softmax_xent": (_I, [_I, _I, _I] + [_P] * 5 + [_P]),
     "sph3d_lovasz_softmax_supported": (_I, [_I, _I]),
     "sph3d_lovasz_softmax": (_I, [_I, _I, _I] + [_P] * 3 + [_L] + [_P] * 6 + [_P]),
+    "sph3d_lovasz_softmax_large_supported": (_I, [_I, _I]),
+    "sph3d_lovasz_softmax_large_workspace": (_S, [_I] * 3),
+    "sph3d_lovasz_softmax_large_plan": (_I, [_I] * 5 + [_P]),
+    "sph3d_lovasz_softmax_large": (_I, [_I, _I, _I] + [_P] * 3 + [_L] + [_P] * 6 + [_P, _S, _I, _I, _P]),
     "sph3d_softmax_xent_parts": (_I, [_I]),
     "sph3d_softmax_xent_supported": (_I, [_I, _I]),
     "sph3d_softmax_xent_workspace": (_S, [_I] * 3),

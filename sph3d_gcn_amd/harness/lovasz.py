@@ -2,6 +2,9 @@
 (include/sph3d.h: sph3d_lovasz_softmax), the same statement in torch ops, and the loss functions a Trainer takes.
 
 The statement is per block (the paper's per_image=True), as the project's losses are: the batch loss is the sum of the blocks'.
+scope="batch" is the same statement on the call reshaped to ONE block of B * N rows (the paper's per_image=False, its default): row
+index n is then the flat index.  Blocks of more than MAX_N rows, which the batch scope usually is, run on the device through
+sph3d_lovasz_softmax_large (the sort in global memory, up to MAX_N_LARGE rows) when loss() is called with large=True.
 
   valid     row n of block b is valid iff (inner is None or inner[b,n] > 0; NaN > 0 is false) and label[b,n] != ignore
   p         softmax(logits[b,n,:])
@@ -32,6 +35,13 @@ import numpy as np
 import torch
 
 MAX_N = 16384                      # csrc/lovasz.hip: kLovMaxN (sph3d_lovasz_softmax_supported)
+MAX_N_LARGE = 1 << 20              # csrc/lovasz_plan.hpp: kLovLargeMaxN (sph3d_lovasz_softmax_large_supported)
+_SCOPES = ("block", "batch")
+
+
+def _check_scope(scope):
+    if scope not in _SCOPES:
+        raise ValueError("lovasz: scope should be 'block' or 'batch', got %r" % (scope,))
 
 
 def jaccard_gradient(fg_sorted):
@@ -44,13 +54,18 @@ def jaccard_gradient(fg_sorted):
     return np.where(fg, 1.0 / U, (G - F) / den.astype(np.float64))
 
 
-def lovasz_reference(logits, label, inner=None, ignore=-1, probs=None):
+def lovasz_reference(logits, label, inner=None, ignore=-1, probs=None, scope="block"):
     """logits [B,N,C], label [B,N] integer, inner [B,N] or None -> dict of float64 arrays: loss [B], class_loss [B,C] (L; 0 for a
     class that is not present), probs [B,N,C], coef [B,N,C], dlogits [B,N,C], and order [B,C,N] int32 (the row at every sorted
     position of every class, present or not; -1 past n_b), present [B,C] bool, n_valid [B].
     probs: probabilities to take as given, in float32 (see the module's text: the order is that of the bits of the float32 e), or in
-    float64 (the statement as a function of p: the order is that of the float64 e); None: the float64 softmax of logits."""
+    float64 (the statement as a function of p: the order is that of the float64 e); None: the float64 softmax of logits.
+    scope="batch": the statement on the call reshaped to ONE block of B * N rows (the paper's per_image=False): row index n is the
+    flat index, ties break by ascending flat index, and every array of the result has a leading 1."""
+    _check_scope(scope)
     x = np.asarray(logits, np.float64)
+    if scope == "batch":
+        x = x.reshape(1, -1, x.shape[-1])
     B, N, C = x.shape
     label = np.asarray(label).reshape(B, N).astype(np.int64)
     valid = label != ignore
@@ -105,9 +120,13 @@ def lovasz_reference(logits, label, inner=None, ignore=-1, probs=None):
     return out
 
 
-def lovasz_torch(pred, label, inner_label=None, ignore=-1):
-    """the statement in torch ops, on any device and in pred's dtype, differentiable in pred: -> loss [B].  The fallback for CPU
-    tensors and for blocks of more than MAX_N points, and the baseline the kernels are measured against."""
+def lovasz_torch(pred, label, inner_label=None, ignore=-1, scope="block"):
+    """the statement in torch ops, on any device and in pred's dtype, differentiable in pred: -> loss [B] ([1] for scope="batch":
+    the call reshaped to one block of B * N rows).  The fallback for CPU tensors and for blocks the kernels do not cover, and the
+    baseline the kernels are measured against."""
+    _check_scope(scope)
+    if scope == "batch":
+        pred = pred.reshape(1, -1, pred.shape[-1])
     B, N, C = pred.shape
     label = label.reshape(B, N).long()
     valid = label != ignore
@@ -138,19 +157,33 @@ def lovasz_torch(pred, label, inner_label=None, ignore=-1):
     return loss + nan * p.sum((1, 2))
 
 
-def loss(pred, label, inner_label=None, ignore=-1):
-    """the batch loss (the sum of the blocks' losses): the kernels for device tensors with N <= MAX_N, lovasz_torch otherwise"""
+def loss(pred, label, inner_label=None, ignore=-1, scope="block", large=False):
+    """the batch loss: the sum of the blocks' losses (scope="block"), or the loss of the call as one block of B * N rows
+    (scope="batch", the paper's per_image=False).  Device tensors go to the kernels where tf_loss.supported says so (N <= MAX_N rows
+    per block); with large=True also to the global-memory sort where tf_loss.supported_large says so (N <= MAX_N_LARGE);
+    lovasz_torch otherwise.  large is an opt-in: without it the dispatch, and the bits, are what they were before it existed."""
+    _check_scope(scope)
     B, N, C = pred.shape
+    if scope == "batch":
+        pred = pred.reshape(1, B * N, C)
+        B, N = 1, B * N
+        label = label.reshape(B, N)
+        inner_label = inner_label.reshape(B, N) if inner_label is not None else None
     if pred.is_cuda:
         from .. import tf_loss
         if tf_loss.supported(N, C):
             return tf_loss.lovasz_softmax(pred, label, inner_label, ignore).sum()
+        if large and tf_loss.supported_large(N, C):
+            return tf_loss.lovasz_softmax_large(pred, label, inner_label, ignore).sum()
     return lovasz_torch(pred, label, inner_label, ignore).sum()
 
 
-def with_xent(xent_fn, weight=1.0):
-    """-> loss_fn(pred, label, *rest) = xent_fn(pred, label, *rest) + weight * loss(pred, label, *rest[:1]): a Trainer's loss_fn for
-    the segmentation lines (S3DIS / ScanNet hand it (pred, label, inner_label); ShapeNet and RueMonge (pred, label))"""
+def with_xent(xent_fn, weight=1.0, scope="block", large=False):
+    """-> loss_fn(pred, label, *rest) = xent_fn(pred, label, *rest) + weight * loss(pred, label, *rest[:1], scope=scope, large=large):
+    a Trainer's loss_fn for the segmentation lines (S3DIS / ScanNet hand it (pred, label, inner_label); ShapeNet and RueMonge
+    (pred, label))"""
+    _check_scope(scope)
+
     def loss_fn(pred, label, *rest):
-        return xent_fn(pred, label, *rest) + weight * loss(pred, label, *rest[:1])
+        return xent_fn(pred, label, *rest) + weight * loss(pred, label, *rest[:1], scope=scope, large=large)
     return loss_fn

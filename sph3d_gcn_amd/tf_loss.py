@@ -6,6 +6,10 @@ present in the block.  One call computes the losses AND the gradient with respec
 scaling by the upstream gradient.  N <= 16384 points per block (``supported(N, C)``); harness/lovasz.py: loss() falls back to the
 torch statement above that.
 
+``lovasz_softmax_large(pred, label, inner_label=None, ignore=-1, scope="block") -> [B]`` ([1] for scope="batch"): the same loss with
+the sort in global memory (include/sph3d.h: sph3d_lovasz_softmax_large), for blocks of up to 2^20 rows and for the batch
+reduction (``supported_large(N, C)``).  An opt-in: harness/lovasz.py: loss(..., large=True) dispatches to it.
+
 ``softmax_xent(pred, label, inner_label=None, class_weight=None, label_smoothing=0.0, ignore=None, normalize="count",
 scope="block", return_counts=False) -> [B]`` ([1] for scope="batch"): the softmax cross-entropy with class weights, label smoothing
 and an ignore label (include/sph3d.h: sph3d_softmax_xent; csrc/xent.hip; the float64 statement is harness/xent.py: xent_reference).
@@ -61,6 +65,58 @@ def lovasz_softmax(pred, label, inner_label=None, ignore=-1):
     # (grad mode is off inside forward(), and needs_input_grad ignores no_grad: the question is asked here)
     want_grad = torch.is_grad_enabled() and pred.requires_grad
     return _LovaszSoftmaxFn.apply(pred, label, inner_label, ignore, want_grad)
+
+
+def supported_large(N, C):
+    return bool(_lib.lib().sph3d_lovasz_softmax_large_supported(int(N), int(C)))
+
+
+class _LovaszSoftmaxLargeFn(torch.autograd.Function):
+    """_LovaszSoftmaxFn through sph3d_lovasz_softmax_large: the sort's workspace follows probs, coef and class_loss in the scratch"""
+
+    @staticmethod
+    def forward(ctx, pred, label, inner, ignore, want_grad):
+        B, N, C = pred.shape
+        l = _lib.lib()
+        loss = torch.empty((B,), dtype=torch.float32, device=pred.device)
+        words = B * N * C
+        head = (4 * (2 * words + B * C) + 255) & ~255
+        nbytes = l.sph3d_lovasz_softmax_large_workspace(B, N, C)
+        ws = _lib.scratch(head + nbytes, pred.device)
+        base = ws.data_ptr() if ws is not None else 0
+        # (evaluation / no_grad: the losses only, no [B, N, C] gradient)
+        dlogits = torch.empty_like(pred) if want_grad else None
+        _lib.check(l.sph3d_lovasz_softmax_large(B, N, C, _lib.ptr(pred), _lib.ptr(label), _lib.ptr(inner), int(ignore), base,
+                                                base + 4 * words, base + 8 * words, _lib.ptr(loss), _lib.ptr(dlogits), None,
+                                                base + head, nbytes, 0, 0, _lib.stream_ptr()))
+        if dlogits is not None:
+            ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g[:, None, None], None, None, None, None
+
+
+def lovasz_softmax_large(pred, label, inner_label=None, ignore=-1, scope="block"):
+    """lovasz_softmax for blocks of up to 2^20 rows (``supported_large(N, C)``; include/sph3d.h: sph3d_lovasz_softmax_large): the
+    sort runs in global memory.  scope="batch": the call is one block of B * N rows (the paper's per_image=False).
+    -> loss [B] float32 ([1] for batch scope)"""
+    tensors = (pred, label) if inner_label is None else (pred, label, inner_label)
+    _lib.require_device(*tensors)
+    if scope not in ("block", "batch"):
+        raise ValueError("lovasz_softmax_large: scope should be 'block' or 'batch', got %r" % (scope,))
+    B, N, C = pred.shape
+    if scope == "batch":
+        pred = pred.reshape(1, B * N, C)
+        B, N = 1, B * N
+    pred = _lib.f32(pred)
+    label = label.reshape(B, N).long().contiguous()
+    inner = inner_label.reshape(B, N).float().contiguous() if inner_label is not None else None
+    # (grad mode is off inside forward(), and needs_input_grad ignores no_grad: the question is asked here)
+    want_grad = torch.is_grad_enabled() and pred.requires_grad
+    return _LovaszSoftmaxLargeFn.apply(pred, label, inner, ignore, want_grad)
 
 
 # ---- the S3DIS / ScanNet / RueMonge training loss: mean cross-entropy over a block's inner points -------------------------------

@@ -6,7 +6,10 @@ A measurement, not a test (tests/test_gpu_lovasz.py holds the outputs to the sta
 median of 9 alternating pairs.  The three launches' own times are a kernel trace's business:
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/exp_lovasz.py --op-only
 runs the op alone (forward + backward, 20 calls per shape after 3) for that.
-usage: python tools/exp_lovasz.py [--op-only] [--skip-steps]"""
+--large measures the global-memory sort (tf_loss.lovasz_softmax_large) against lovasz_torch at 16 x 65536 x 21 (block scope) and at
+the batch reductions of 32 x 2048 x 50, 16 x 8192 x 13 and 16 x 8192 x 7, and against the LDS sort at 16 x 16384 x 13, the same way
+with 3 rounds.
+usage: python tools/exp_lovasz.py [--op-only] [--skip-steps] [--large]"""
 import os
 import statistics
 import sys
@@ -97,8 +100,35 @@ def steps():
     print("train_step %8.3f | %8.3f" % (statistics.median(times[0]), statistics.median(times[1])), flush=True)
 
 
+def large():
+    """the global-memory sort (tf_loss.lovasz_softmax_large) against lovasz_torch where the LDS sort does not reach, and against the
+    LDS sort at its own largest shape (the price of the global path)"""
+    from sph3d_gcn_amd import _lib
+    print("== large entry, device us per call (median of 3 alternating rounds): forward | forward + backward; workspace bytes")
+    cases = (((16, 65536, 21), "block"), ((32, 2048, 50), "batch"), ((16, 8192, 13), "batch"), ((16, 8192, 7), "batch"),
+             ((16, 16384, 13), "block"))
+    for (B, N, C), scope in cases:
+        pred, label, inner = inputs(B, N, C)
+        cands = [("lovasz large", lambda p, l, i, s=scope: tf_loss.lovasz_softmax_large(p, l, i, scope=s))]
+        if tf_loss.supported(N, C) and scope == "block":
+            cands.append(("lovasz kernels (LDS)", tf_loss.lovasz_softmax))
+        cands.append(("lovasz_torch", lambda p, l, i, s=scope: lovasz.lovasz_torch(p, l, i, scope=s)))
+        times = {name: ([], []) for name, _ in cands}
+        for _ in range(3):
+            for name, fn in cands:
+                times[name][0].append(timed(lambda: fwd(fn, pred, label, inner)))
+                times[name][1].append(timed(lambda: fwd_bwd(fn, pred, label, inner)))
+        b, n = (1, B * N) if scope == "batch" else (B, N)
+        ws = _lib.lib().sph3d_lovasz_softmax_large_workspace(b, n, C)
+        for name, _ in cands:
+            print("%d x %d x %d %-5s  %-22s %9.1f | %9.1f   workspace %d" % (B, N, C, scope, name, statistics.median(times[name][0]),
+                                                                            statistics.median(times[name][1]), ws), flush=True)
+
+
 if __name__ == "__main__":
-    if "--op-only" in sys.argv:
+    if "--large" in sys.argv:
+        large()
+    elif "--op-only" in sys.argv:
         op_only()
     else:
         ops()
