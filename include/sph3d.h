@@ -941,6 +941,31 @@ int sph3d_feed_assemble(int B, int num_point, int num_blocks, long long total_ro
                         const int* block_ids, unsigned long long seed, unsigned long long step, int augment, float* points,
                         int* label, int* inner, int* index, sph3d_stream_t stream);
 
+/* ---- training crops drawn from whole scenes on the device: one launch cuts a batch of B crops out of a resident pool of
+ * column-sorted scenes (harness/cropfeed.py states the pool and the draws in numpy; csrc/cropfeed.hip).  A scene's rows are sorted
+ * by the column col = ix n_y + iy of an xy grid of n_x x n_y cells (ties in original order), so the rows of cells (ix, y0 .. y1)
+ * are one contiguous range.  The pool, all on the device:
+ *   rows [T,8] fp32       the scenes' sorted rows back to back: xyz, rgb, label, a column that is not read (16-byte aligned)
+ *   column [T] int32      the column of every row
+ *   col_start [C] int32   per scene n_x n_y + 1 words: the first row (within the scene) of every column, then n
+ *   scene_tab [S,5] int64 per scene: its first row in rows, its first word in col_start, n_x, n_y, n
+ * scene_ids [B] int32 (device): the scene of every cloud.  Per cloud b, ck its key (csrc/feed_draws.hpp): attempt a < attempts
+ * centres a window on the column (cx, cy) of row mulhi(hi32(draw(ck, 40, a)), n): ix in [max(0, cx - outer_half),
+ * min(n_x - 1, cx + outer_half)], iy likewise; its members are the rows of its strips in ascending ix, then in stored order, T_a of
+ * them.  The first attempt with T_a >= min_points is taken, else the one with the largest T_a (the lowest a on a tie).  With T
+ * members, slot j takes member sph3d_feed_assemble's sample of (ck, T, num_point) names; inner = 1 iff the row's cell is within
+ * inner_half of (cx, cy) on both axes; `augment` is sph3d_feed_assemble's rule by thirds of B.
+ * -> points [B,num_point,6] fp32, label / inner [B,num_point] int32, index [B,num_point] int32 (nullable): the row within the
+ * scene's stored order, crop [B,4] int32: scene id, centre row, attempt, T.  A scene id outside [0, S) or a scene_tab row that does
+ * not describe rows of the pool reads nothing: zeros, index -1, crop -1.  Integer outputs are pure functions of the arguments; no
+ * atomics, no workspace.  SPH3D_EINVAL: null or misaligned pointers, B num_point > 2^31 - 1, B > 65535, 2 outer_half + 1 > 256,
+ * inner_half outside [0, outer_half], attempts outside [1, 8], min_points < 1. */
+int sph3d_cropfeed_assemble(int B, int num_point, int num_scenes, long long total_rows, long long total_cols, const float* rows,
+                            const int* column, const int* col_start, const long long* scene_tab, const int* scene_ids,
+                            unsigned long long seed, unsigned long long step, int augment, int inner_half, int outer_half,
+                            int attempts, int min_points, float* points, int* label, int* inner, int* index, int* crop,
+                            sph3d_stream_t stream);
+
 /* ---- overlap-voting evaluation of the segmentation nets on the device (s3dis_seg/evaluate_s3dis_with_overlap.py:253-286 the
  * per-pass sample counts and coverage, :301-302 the vote, :314-325 arg-max and the per-class counts; the ScanNet script,
  * evaluate_scannet_withoverlap.py:280, differs in the coverage threshold).  A batch is B blocks of the pool sph3d_feed_assemble

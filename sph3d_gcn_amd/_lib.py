@@ -126,6 +126,7 @@ SIGNATURES = {
     "sph3d_train_metrics": (_I, [_I] * 3 + [_P] * 4 + [_I] + [_P] * 3 + [_P]),
     "sph3d_dropout_keyed": (_I, [_I, _L, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _L, _I, ctypes.c_uint, _F, _P]),
     "sph3d_feed_assemble": (_I, [_I, _I, _I, ctypes.c_longlong, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I] + [_P] * 5),
+    "sph3d_cropfeed_assemble": (_I, [_I, _I, _I, _L, _L] + [_P] * 5 + [ctypes.c_ulonglong, ctypes.c_ulonglong] + [_I] * 5 + [_P] * 5 + [_P]),
     "sph3d_objfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),
     "sph3d_blockfeed_assemble": (_I, [_I, _I, _I, _L, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _I, _P] + [_P] * 4 + [_P]),
     "sph3d_facadefeed_assemble": (_I,[_I, _I, _I, _L, _P, _P, _P, _P, ctypes.c_ulonglong, ctypes.c_ulonglong, _P] + [_P] * 3 + [_P]),

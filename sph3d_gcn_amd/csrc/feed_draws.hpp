@@ -1,4 +1,4 @@
-// feed_draws.hpp — the counter-based draws the feed kernels share (feed.hip, objfeed.hip, scanfeed.hip); harness/feed.py states
+// feed_draws.hpp — the counter-based draws the feed kernels share (feed.hip, objfeed.hip, scanfeed.hip, cropfeed.hip); harness/feed.py states
 // them in numpy.
 //
 //   cloud key   ck = mix(mix(mix(seed + G) + step + G) + b + G)           mix = the splitmix64 finaliser, G = 0x9e3779b97f4a7c15
@@ -21,7 +21,8 @@ enum : unsigned long long { kFeedPerm = 1, kFeedRepl = 2, kFeedTurn = 3, kFeedTi
                             kFeedAugGate = 32 /* counter = the gate's bit */, kFeedAugScale = 33 /* counter = axis */,
                             kFeedAugField = 34 /* + pass, 0 <= pass < 2; counter = the packed node */,
                             kFeedAugContrast = 36, kFeedAugCtrans = 37 /* counter = channel */,
-                            kFeedAugCnoise = 38 /* counters 2 slot, 2 slot + 1 */ };
+                            kFeedAugCnoise = 38 /* counters 2 slot, 2 slot + 1 */,
+                            kFeedCrop = 40 /* counter = the attempt: cropfeed.hip */ };
 constexpr int kFeedDropoutLayers = 16;
 
 __host__ __device__ __forceinline__ unsigned long long feed_mix(unsigned long long z)

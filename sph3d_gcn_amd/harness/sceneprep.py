@@ -564,3 +564,33 @@ def prepare_scenes(raw_scenes, h=0.03, block=1.5, stride=0.75, context=0.3, thre
         scene_of_block += [s] * P
         p0 += P
     return feed.BlockPool.from_device(rows, offsets, sizes, index, scene_of_block), scenes
+
+
+def prepare_training_scenes(raw_scenes, h=0.03, cell=0.05, max_cells=DEFAULT_MAX_CELLS, max_columns=None, device=None,
+                            keep_host=False):
+    """From scanned rooms to the pool harness/cropfeed.py's CropFeed draws training crops from -> cropfeed.ScenePool.
+
+        pool = sceneprep.prepare_training_scenes([(full_xyz, full_rgb, full_label), ...])
+        feed = cropfeed.CropFeed(pool, 16, 8192, seed=1)
+
+    raw_scenes: as prepare_scenes takes them.  Per scene: voxelize (cell edge h), the label of the nearest full point and
+    normalise, all on the device as in prepare_scenes — without the block split; the normalised voxel cloud is then copied to
+    the host ONCE and put into stored order by cropfeed.column_sort_reference (cell edge `cell`).  A scene equals
+    voxel_reference -> nearest_reference labels -> normalise_reference -> column_sort_reference bit for bit.  Two host
+    synchronisations per scene: the grid's header, the copy."""
+    import torch
+    from . import cropfeed
+    if not raw_scenes:
+        raise ValueError("prepare_training_scenes: no scenes")
+    dev = torch.device(device if device is not None else "cuda:0")
+    up = lambda a, dt: a.to(dev) if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    scenes = []
+    for full_xyz, full_rgb, full_label in raw_scenes:
+        fx, fc, fl = up(full_xyz, _F32), up(full_rgb, _F32), up(full_label, np.int32)
+        vx, vc, _count, _vop, box = voxelize(fx, fc, h, max_cells, want_box=True)                 # synchronisation 1
+        vl = voxel_labels(fx, fl, vx)
+        nx, nc = normalise(vx, vc, box)
+        nx_h, nc_h, vl_h = to_host(nx, nc, vl)                                                    # synchronisation 2
+        scenes.append(cropfeed.sort_scene(nx_h, nc_h, vl_h, cell,
+                                          cropfeed.DEFAULT_MAX_COLUMNS if max_columns is None else max_columns))
+    return cropfeed.ScenePool(scenes, dev, cell, keep_host)
